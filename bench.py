@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: trajectory-steps/s of the HK loop on the synthetic 60-mode anharmonic-AS model.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--ntraj n_per_gpu | --ntraj-total n]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--ntraj n_per_gpu | --ntraj-total n] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch: (C_auto, k_ic, RK4 step + prefactor) for all
 trajectories (the loop body of reference cli.py:401-436).  Workload = BASELINE.json configs[1]:
@@ -371,6 +371,22 @@ def wall_to_full_ct(pot, omega, q0, dt, E0, n, dev, nt=2000):
             "wall_to_1e-3_standard_error_s_extrapolated": (wall - (t1 - t0)) * (se / 1e-3) ** 2}
 
 
+def dump_outputs(directory, prop, cauto, kic, n_sample=128):
+    """--dump-outputs DIR: what the timed loop handed its caller, as float64 .npy files, so that two builds can be compared
+    output for output (the inputs are seeded: the same arguments give the same inputs).
+      C_auto.npy, k_ic.npy  (K, 2) re, im of the correlation functions of every timed step (the last row is the last step's)
+      state_sample.npy      (2D + 4D^2 + 1, n_sample) the state after the last step in the reference's layout (rows q, p, Mqq,
+                            Mqp, Mpq, Mpp, S; prop.y) for a fixed sample of this rank's trajectories (sorted, seed 0): 15 MB at D = 60"""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "C_auto.npy"), np.stack((cauto.real, cauto.imag), axis=1).astype(np.float64))
+    np.save(os.path.join(directory, "k_ic.npy"), np.stack((kic.real, kic.imag), axis=1).astype(np.float64))
+    pick = np.sort(np.random.default_rng(0).choice(prop.ntraj, size=min(n_sample, prop.ntraj), replace=False))
+    y = prop.y
+    sample = y[:, torch.from_numpy(pick).to(y.device)].cpu().numpy()
+    del y
+    np.save(os.path.join(directory, "state_sample.npy"), sample.astype(np.float64))
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 
 def launch_check():
@@ -408,6 +424,8 @@ def parse_args(argv=None):
     ap.add_argument("--config", choices=["1", "3", "3hk", "5"], default=None,
                     help="run ONLY that BASELINE configuration's side measurement (for one rocprofv3 summary per configuration: "
                          "1 = 5-mode AS at n = 1e5, 3 = methylium WM at n = 1e5, 5 = 30-atom sGDML at n = 1e4) and print its JSON")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (C_auto, k_ic, a fixed sample of the final state) as DIR/*.npy")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -490,6 +508,8 @@ def main():
     wall = float(tmax.item())
     cauto, kic = prop.finalize_slots(slots, prop.t - K * dt, dt, E0)
     assert np.isfinite(cauto).all() and np.isfinite(kic).all(), "NaN in correlation functions"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, prop, cauto, kic)
     # who took part: backend of the process group and the device every rank ran on (so that a scaling record shows that
     # RCCL -- torch's "nccl" backend on ROCm -- saw N ranks on N different GPUs)
     me = {"rank": rank, "device": str(dev), "gpu": torch.cuda.get_device_name(dev), "trajectories": n,

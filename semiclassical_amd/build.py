@@ -72,7 +72,8 @@ def build(force=False, verbose=True, extra=(), out=None, more_sources=(), jobs=N
         return LIB
     srcs = sources() + list(more_sources)
     tag = hashlib.sha256(" ".join(extra).encode()).hexdigest()[:8] if extra else ""
-    jobs = jobs or min(len(srcs), max(1, (os.cpu_count() or 2) - 1))
+    # one hipcc per source, bounded by the CPUs this process may use (a shared host shows more than it grants) and MAX_JOBS
+    jobs = jobs or min(len(srcs), len(os.sched_getaffinity(0)), int(os.environ.get("MAX_JOBS") or 16))
     with ThreadPoolExecutor(jobs) as pool:
         objs = list(pool.map(lambda s: _compile(s, extra, tag, verbose), srcs))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -132,12 +132,10 @@ def test_potential_torch_protocol_matches_oracle():
 
 def test_fchk_reader_methylium():
     """zero-point energy, rank of Gamma_0 and adiabatic gap quoted in SURVEY.md section 8c"""
-    ref_dir = "/root/reference/tests/DATA/examples/methylium_AH"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("reference data not present on this machine")
     from semiclassical_amd import units
     from semiclassical_amd.readers import FormattedCheckpointFile
-    with open(os.path.join(ref_dir, "opt_freq_s1.fchk")) as f:
+    # the reference's methylium_AH/opt_freq_s1.fchk, stored as data (tests/golden/fchk/)
+    with open(os.path.join(ROOT, "tests", "golden", "fchk", "methylium_s1.fchk")) as f:
         s1 = FormattedCheckpointFile(f)
     x0, G0, ezpt = s1.vibrational_groundstate()
     assert abs(ezpt - 0.0247324) < 1e-6

@@ -13,7 +13,10 @@ TOL = 1e-11
 
 @pytest.mark.parametrize("name", cases.HK_CASES + cases.WM_CASES + cases.GDML_CASES)
 def test_oracle_matches_reference(name):
-    g = cases.load(name)
+    cases.on_one_float_path(name, _oracle_matches)
+
+
+def _oracle_matches(g):
     pot = cases.oracle_potential(g)
     prop = cases.oracle_propagator(g)
     nt, dt, E0 = int(g["nt"]), float(g["dt"]), float(g["E0"])
@@ -84,13 +87,15 @@ def test_sym_sqrtm():
 
 def test_gdml_oracle_matches_reference_predictor():
     """E, grad, Hessian of the sGDML restatement vs GDMLPredict.forward of the reference (golden)"""
-    g = cases.load("gdml_coumarin_eval")
     gd = orc.GDMLOracle(cases.load("gdml_coumarin_model"))
-    e, grad, hess = gd.forward(torch.from_numpy(g["r"]))
-    assert cases.rel_err(e.numpy(), g["energy"]) < 1e-14
-    assert cases.rel_err(grad.numpy(), g["grad"]) < 1e-12
-    assert cases.rel_err(hess.numpy(), g["hess"]) < 1e-12
-    assert torch.allclose(hess, hess.transpose(1, 2), atol=1e-10)        # reference tests/test_gdml_predictor.py:90-122
+
+    def check(g):
+        e, grad, hess = gd.forward(torch.from_numpy(g["r"]))
+        assert cases.rel_err(e.numpy(), g["energy"]) < 1e-14
+        assert cases.rel_err(grad.numpy(), g["grad"]) < 1e-12
+        assert cases.rel_err(hess.numpy(), g["hess"]) < 1e-12
+        assert torch.allclose(hess, hess.transpose(1, 2), atol=1e-10)    # reference tests/test_gdml_predictor.py:90-122
+    cases.on_one_float_path("gdml_coumarin_eval", check)
 
 
 def test_gdml_sum_conditioning():
