@@ -37,7 +37,7 @@ extern "C" {
 
 /* Bumped on every change of a struct layout or a function signature below.  semiclassical_amd/_lib.py refuses a
  * library whose sc_abi_version() or struct sizes differ from its own declarations. */
-#define SC_ABI_VERSION        17
+#define SC_ABI_VERSION        18
 
 #define SC_OK                 0
 #define SC_ERR_BAD_ARGUMENT  -1
@@ -316,12 +316,29 @@ int sc_hk_run(const sc_potential *pot, const sc_state *st, const sc_hk_consts *h
  * after it (HermanKlukPropagator.run does, with two batched products); (q, p, S), the correlation terms and the energy guard are
  * in the original coordinates as in sc_hk_run.  Per lane and step 8 D multiply-adds replace the 8 D^2 of the product with Phi. */
 /* mono[i][p] <- left[p] . mono[i][p] . right[p] for the four blocks p = qq, qp, pq, pp of every trajectory (left, right: [4][D][D],
- * row-major state, D <= 16): the change of basis in front of and behind sc_hk_run_modal. */
+ * row-major state, D <= 64): the change of basis in front of and behind sc_hk_run_modal / sc_hk_step_modal.  D <= 16 and
+ * 16 < D <= 64 are two kernels (ABI 18 widened the range; the results for D <= 16 are those of ABI 17 bit for bit). */
 int sc_mono_similarity(const sc_state *st, const double *left, const double *right, void *stream);
 int sc_hk_run_modal_supported(const sc_potential *pot, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0);
 int sc_hk_run_modal(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
                     const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
                     double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog, void *stream);
+
+/* One HK time step for a CONSTANT dense Hessian (SC_POT_HARMONIC_DENSE) at 16 < D <= 64 with the monodromy blocks of the state in
+ * NORMAL-MODE coordinates (ABI 18).  Same contract as sc_hk_step (replaces _rk4_step + EquationsOfMotion.f, propagators.py:86-119,
+ * 313-383, and _prefactor + _track_signs_of_sqrt, propagators.py:951-1052; energy_partials[sc_step_grid()]; mode 0 = step +
+ * prefactor, 1 = prefactor only with tracker initialisation), except that
+ *   - st->mono holds Mqq~, Mqp~, Mpq~, Mpp~ (row-major, the transformation of sc_hk_run_modal above; the caller converts with
+ *     sc_mono_similarity) and the step multiplies row a of the plane pairs (Mqq~, Mpq~), (Mqp~, Mpp~) by the 2 x 2 matrix
+ *     mode_prop[a] = (phi_qq, phi_qp, phi_pq, phi_pp)_a;
+ *   - hk holds the transformed constants L1 A, L2 B, A^-1 R1, B^-1 R2 (dense: diag = 0, real_lr = 1; d' <= D; diagonal width
+ *     matrices are passed as dense diagonal L, R);
+ *   - (q, p, S) stay Cartesian.
+ * The prefactor is formed from the new blocks on chip by FP64 matrix-core products; the determinant is a pivoted LU.
+ * sc_hk_step_modal_supported: 1 if the combination is held (else the call fails with SC_ERR_UNSUPPORTED). */
+int sc_hk_step_modal_supported(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk);
+int sc_hk_step_modal(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, double dt, int32_t mode,
+                     const double *mode_prop, double *energy_partials, void *stream);
 
 /* Walton-Manolopoulos: Filinov matrix A (eqn 50), its inverse and determinant, Gt/Gti/CQQ/M (57-78), the second
  * inverse and determinant, the trackers of sqrt(detA), sqrt(detM) and the per-trajectory terms of eqns (85), (100),

@@ -50,13 +50,53 @@ __global__ __launch_bounds__(256) void mono_similarity_kernel(double *mono, int6
     }
 }
 
+// The same for 16 < D <= 64: one workgroup per (trajectory, block) at a time, everything it multiplies staged in LDS (3 D^2 doubles,
+// 62 KB at D = 51: two workgroups per CU).  T = M . right with the block and `right` in LDS, then left . T with `left` loaded
+// into the buffer `right` occupied.  Vector ALUs: it runs once per change of basis, off the per-step hot path of HK.
+__global__ __launch_bounds__(256) void mono_similarity_wide_kernel(double *mono, int64_t n, int D, const double *left, const double *right) {
+    extern __shared__ double2 smem2[];
+    const int DD = D * D, tid = threadIdx.x;
+    double *sM = (double *)smem2, *sC = sM + DD, *sT = sC + DD;
+    for (int64_t item = blockIdx.x; item < 4 * n; item += gridDim.x) {
+        const int p = (int)(item & 3);
+        double *M = mono + item * (int64_t)DD;              // block p of trajectory item / 4
+        __syncthreads();
+        for (int e = tid; e < DD; e += 256) { sM[e] = M[e]; sC[e] = right[p * DD + e]; }
+        __syncthreads();
+        for (int e = tid; e < DD; e += 256) {
+            const int i = e / D, j = e - i * D;
+            double acc = 0.0;
+            for (int k = 0; k < D; ++k) acc = fma(sM[i * D + k], sC[k * D + j], acc);
+            sT[e] = acc;
+        }
+        __syncthreads();
+        for (int e = tid; e < DD; e += 256) sC[e] = left[p * DD + e];
+        __syncthreads();
+        for (int e = tid; e < DD; e += 256) {
+            const int i = e / D, j = e - i * D;
+            double acc = 0.0;
+            for (int k = 0; k < D; ++k) acc = fma(sC[i * D + k], sT[k * D + j], acc);
+            M[e] = acc;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int sc_mono_similarity(const sc_state *st, const double *left, const double *right, void *stream) {
     if (!st || !st->mono || !left || !right) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_mono_similarity: null argument");
-    if (st->dim < 1 || st->dim > 16) return sc_fail(SC_ERR_UNSUPPORTED, "sc_mono_similarity: D=%d outside 1..16", st->dim);
+    if (st->dim < 1 || st->dim > 64) return sc_fail(SC_ERR_UNSUPPORTED, "sc_mono_similarity: D=%d outside 1..64", st->dim);
     if (int rq = sc_require_rowmajor(st, "sc_mono_similarity")) return rq;
     if (st->n <= 0) return SC_OK;
+    if (st->dim > 16) {
+        const int64_t items = 4 * st->n;
+        const int grid = (int)(items < 4096 ? items : 4096);
+        const size_t lds = (size_t)3 * st->dim * st->dim * sizeof(double);
+        if (hipFuncSetAttribute((const void *)mono_similarity_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return sc_check_launch("sc_mono_similarity (LDS attribute)");
+        hipLaunchKernelGGL(mono_similarity_wide_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, st->mono, st->n, st->dim, left, right);
+        return sc_check_launch("sc_mono_similarity");
+    }
     const int grid = (int)(st->n < 8192 ? st->n : 8192);
     hipLaunchKernelGGL(mono_similarity_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, st->mono, st->n, st->dim, left, right);
     return sc_check_launch("sc_mono_similarity");

@@ -224,6 +224,10 @@ class HermanKlukPropagator(object):
         # two time steps per visit (sc_hk_step_multi: an intermediate determinant cannot be repaired after the fact).
         self._blocks_structurally_diagonal = True
         self._multi = None
+        # normal-mode constants of the modal step (sc_hk_step_modal) depend on U (Gamma_0): rebuilt for every new state.
+        # _modal_basis: the constants whose A, B the monodromy blocks are expressed in, None = Cartesian (the identity of t = 0 is
+        # the identity in both bases)
+        self._modal_step_cache, self._modal_basis = {}, None
 
         self._prepare()
         self.t = 0.0
@@ -304,12 +308,14 @@ class HermanKlukPropagator(object):
             e0.record()
         if hasattr(potential, "_gdml_model"):
             self._blocks_structurally_diagonal = False
+            self._leave_modal()
             self._sync_dense_mono(leave_diagonal=True)
             self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
             nblocks = self._launch_dense_step(potential, dt, s)
         elif not hasattr(potential, "_descriptor") or self.dim > 64:
             # no device descriptor, or beyond the fused kernels' D <= 64: the potential's own torch code + dense path
             self._blocks_structurally_diagonal = False
+            self._leave_modal()
             self._sync_dense_mono(leave_diagonal=True)
             self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
             nblocks = self._launch_generic_step(potential, dt, s)
@@ -318,10 +324,20 @@ class HermanKlukPropagator(object):
                 desc = self._potential_descriptor(potential, dt)
             if desc.kind not in (_lib.SC_POT_MORSE, _lib.SC_POT_HARMONIC_SEP, _lib.SC_POT_EPS_MORSE):
                 self._blocks_structurally_diagonal = False          # a dense Hessian couples the rows
-            if self._shortcut_applies(desc):
+            modal = self._modal_step_constants(potential, desc, dt)
+            if modal is not None:
+                # constant dense Hessian, 16 < D <= 64: the blocks stay in normal-mode coordinates between such steps
+                self._sync_dense_mono(leave_diagonal=True)
+                self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
+                self._enter_modal(modal)
+                with self._timed("hk_step_modal"):
+                    check(lib.sc_hk_step_modal(desc, self._state, modal["hk"], dt, 0, ptr(modal["phi"]), ptr(self._epart), s))
+            elif self._shortcut_applies(desc):
+                self._leave_modal()
                 check(lib.sc_hk_step_diag(desc, self._state, self._hk, ptr(self._mdiag), dt, 0, ptr(self._epart), s))
                 self._mono_stale = True
             else:
+                self._leave_modal()
                 self._sync_dense_mono(leave_diagonal=True)
                 self._set_mono_layout(self._fast_path_layout(desc))
                 with self._timed("hk_step"):
@@ -613,7 +629,9 @@ class HermanKlukPropagator(object):
         if fused and self._whole_loop_applies(desc):
             # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run)
             self._run_whole_loop(desc, dt, nt, slots, potential)
-        elif use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing:
+        elif (use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing
+              and self._modal_step_constants(potential, desc, dt) is None):
+            # (the normal-mode step runs the plain loop: its first step may change the basis of the blocks)
             self._run_graph(potential, dt, nt, desc, slots)
         else:
             pairs = fused and nt >= 2 and self._multi_applies(desc)
@@ -681,7 +699,59 @@ class HermanKlukPropagator(object):
         left, right = modal["stacks"][forward]
         check(lib.sc_mono_similarity(self._state, ptr(left), ptr(right), self._stream()))
 
+    # step() / run() with a constant dense Hessian and these D take the normal-mode step kernel (sc_hk_step_modal)
+    modal_step_dims = (17, 64)
+
+    def _modal_step_constants(self, potential, desc, dt):
+        """transformed prefactor constants, per-mode step matrices and the change of basis for sc_hk_step_modal, or None where it
+        does not apply.  Diagonal widths enter as dense diagonal L, R (L1 = diag st, L2 = diag 1/st, R1 = diag 1/si, R2 = diag si)."""
+        lo, hi = self.modal_step_dims
+        if (desc.kind != _lib.SC_POT_HARMONIC_DENSE or not lo <= self.dim <= hi or not hasattr(potential, "_normal_modes")
+                or not (self._pre.diag or self._hk.real_lr)):
+            return None
+        key = (float(dt), potential.hess0.numpy().tobytes(), potential._masses.numpy().tobytes())      # the VALUES: edited in place = new key
+        hit = self._modal_step_cache.get(key)
+        if hit is None:
+            A, B, Ainv, Binv, phi = potential._normal_modes(dt)
+            if self._pre.diag:
+                st, si = self._pre.st.numpy(), self._pre.si.numpy()
+                L1, L2, R1, R2, dprime = np.diag(st), np.diag(1.0 / st), np.diag(1.0 / si), np.diag(si), self.dim
+            else:
+                L1, L2, R1, R2 = (m.real.numpy() for m in (self._pre.L1, self._pre.L2, self._pre.R1, self._pre.R2))
+                dprime = self._pre.dprime
+            dev = self.device
+            t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+            consts = [t((L1 @ A).astype(np.complex128)), t((L2 @ B).astype(np.complex128)),
+                      t((Ainv @ R1).astype(np.complex128)), t((Binv @ R2).astype(np.complex128))]
+            hk = sc_hk_consts(dim=self.dim, dprime=dprime, diag=0, real_lr=1,
+                              L1=ptr(consts[0]), L2=ptr(consts[1]), R1=ptr(consts[2]), R2=ptr(consts[3]))
+            probe = sc_state.from_buffer_copy(self._state)
+            probe.mono_layout = _lib.SC_MONO_ROWMAJOR
+            ok = bool(lib.sc_hk_step_modal_supported(desc, probe, hk))
+            hit = {"ok": ok, "hk": hk, "consts": consts, "phi": t(phi), "A": t(A), "B": t(B), "Ainv": t(Ainv), "Binv": t(Binv),
+                   "basis": key[1:]}
+            self._modal_step_cache.clear()             # the basis the blocks are in stays alive in _modal_basis
+            self._modal_step_cache[key] = hit
+        return hit if hit["ok"] else None
+
+    def _enter_modal(self, modal):
+        """bring the monodromy blocks into the normal-mode coordinates of `modal` (from Cartesian or from another basis)"""
+        cur = self._modal_basis
+        if cur is not None and cur["basis"] == modal["basis"]:
+            self._modal_basis = modal
+            return
+        self._leave_modal()
+        self._to_normal_modes(modal, forward=True)
+        self._modal_basis = modal
+
+    def _leave_modal(self):
+        """monodromy blocks back to Cartesian coordinates (everything but sc_hk_step_modal reads and writes them there)"""
+        if self._modal_basis is not None:
+            self._to_normal_modes(self._modal_basis, forward=False)
+            self._modal_basis = None
+
     def _run_whole_loop(self, desc, dt, nt, slots, potential=None):
+        self._leave_modal()
         if desc.kind not in (_lib.SC_POT_MORSE, _lib.SC_POT_HARMONIC_SEP, _lib.SC_POT_EPS_MORSE):
             self._blocks_structurally_diagonal = False
         self._sync_dense_mono(leave_diagonal=True)
@@ -740,6 +810,7 @@ class HermanKlukPropagator(object):
             self._multi = bufs
         m = self._multi
         s = self._stream()
+        self._leave_modal()
         self._sync_dense_mono(leave_diagonal=True)
         self._set_mono_layout(_lib.SC_MONO_TILED16)
         m["state_mid"].mono_layout = _lib.SC_MONO_TILED16
@@ -804,6 +875,7 @@ class HermanKlukPropagator(object):
         out = torch.empty((2 * d + 4 * d * d + 1, n), dtype=F64, device=self.device)
         self._sync_dense_mono()
         self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
+        self._leave_modal()
         check(lib.sc_state_to_reference(self._state, ptr(out), self._stream()))
         return out
 
@@ -812,7 +884,8 @@ class HermanKlukPropagator(object):
         value = torch.as_tensor(value, dtype=F64).to(self.device).contiguous()
         d, n = self.dim, self.ntraj
         assert value.shape == (2 * d + 4 * d * d + 1, n)
-        self._state.mono_layout = _lib.SC_MONO_ROWMAJOR          # everything in mono is overwritten
+        self._state.mono_layout = _lib.SC_MONO_ROWMAJOR          # everything in mono is overwritten ...
+        self._modal_basis = None                                 # ... with Cartesian blocks
         check(lib.sc_state_from_reference(ptr(value), self._state, self._stream()))
         torch.cuda.current_stream(self.device).synchronize()     # `value` may be a temporary
         self._corr_step = -1
@@ -844,6 +917,7 @@ class HermanKlukPropagator(object):
         # (n, D, D) -> (D, D, n) views
         self._sync_dense_mono()
         self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
+        self._leave_modal()
         return tuple(self._mono[:, k].permute(1, 2, 0) for k in range(4))
 
     def semiclassical_prefactor(self):
@@ -1100,6 +1174,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         self._wm_step, self._wm_has_nac = self._nsteps, has_nac
 
     def _after_prefactor(self, track):
+        self._leave_modal()                 # sc_wm_correlate reads Cartesian blocks; the next modal step converts forward again
         self._wm_launch(track)
 
     def _export(self):
