@@ -405,7 +405,13 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         double *sg_out = ks == KS - 1 ? A.st.sgn + tr : MA.sgn_mid + ((int64_t)ks * A.st.n + tr);
         if (tl < 16) lu_partial_products<NR>(detbuf[par], tl);
         if (ks == KS - 1 && tl == 0 && (*weak & 1) && A.st.flags && !skip_lu) {
-            A.st.flags[tr] = 1;                  // c2 / sgn are left to the fully pivoted fallback
+            // c2 / sgn are left to the fully pivoted fallback, which tracks against the state's c2 / sgn: after an
+            // intermediate sub-step those are two steps old, so hand it this sub-step's predecessor (c2_mid / sgn_mid)
+            if (KS > 1) {
+                c2[tr] = *c2_in;
+                A.st.sgn[tr] = *sg_in;
+            }
+            A.st.flags[tr] = 1;
             atomicAdd(&A.st.flags[A.st.n], 1);   // lets the fix-up launch return at once when nothing was flagged
         } else if (tl == 0) {
             if (KS > 1 && ks < KS - 1 && (*weak & 1) && !skip_lu) atomicAdd(MA.unrepaired, 1);
