@@ -428,7 +428,9 @@ int sc_wm_grid_sum(const double *qp, const double *coef, const double *cqq, cons
 
 /* O(n^2) pair sum behind WaltonManolopoulosPropagator.norm() (propagators.py:1484-1575), from the per-trajectory
  * export of sc_wm_correlate and its projections cqqp [n][d'][d'] = U^T CQQ U, dvecp [n][d'] = U^T dvec (complex),
- * U [D][d'] real.  partials [sc_wm_pair_sum_tiles(n)][4] for sc_reduce_slot.  D <= 64, d' <= 16. */
+ * U [D][d'] real.  partials [sc_wm_pair_sum_tiles(n)][4] for sc_reduce_slot.  D <= 512, d' <= 96: D <= 64 with d' <= 16
+ * takes one thread per pair, every other shape one wavefront per pair (bordered matrix in LDS, partial pivoting,
+ * det(D'/2pi) as mantissa x 2^e); larger shapes return SC_ERR_UNSUPPORTED. */
 int64_t sc_wm_pair_sum_tiles(int64_t n);
 /* The same pair sum over bras i of one set of trajectories and kets j of another (a rank's shard against the gathered
  * ensemble: norm() across ranks); partials [sc_wm_pair_sum_rect_tiles(ni, nj)][4]. */

@@ -530,6 +530,167 @@ __global__ __launch_bounds__(256) void wm_pair_sum_kernel(WmPairArgs A) {
     }
 }
 
+// The same pair sum for 16 < d' <= 96 or 64 < D <= 512: one wavefront per pair, NW = blockDim.x / 64 wavefronts per tile
+// of 16 x 16 pairs (one partial-sum slot per tile, as above).  Each wavefront owns an LDS region holding the bordered
+// (d'+1) x (d'+1) matrix
+//     [ D'   b' ]
+//     [ b'^T  0 ]       row stride `stride` (odd, in complex elements)
+// and eliminates its first d' columns with partial pivoting among the first d' rows.  The corner then holds the Schur
+// complement -b'^T D'^-1 b', so no back substitution is needed; row swaps among the first d' rows leave it unchanged.
+// Lane r updates rows r+k+1 and r+k+65 of step k; the pivot row is a broadcast LDS read.  det(D'/2pi) is kept as
+// mantissa x 2^e so that det^-1/2 exp(...) is formed in log space (det(D'/2pi) falls below 1e-300 at d' ~ 60).
+// Before the matrix is filled, the region holds w = C_j dQ [D complex] and dQ [D doubles].
+#define WMW_MAXD 512
+#define WMW_MAXDP 96
+
+// LDS operations of one wavefront execute in order; the fences keep the compiler from moving them across the sync
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(256) void wm_pair_sum_wide_kernel(WmPairArgs A, int stride, int region) {
+    extern __shared__ double2 smem2[];
+    __shared__ double red[8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, D = A.D, dp = A.dp;
+    cplx *M = smem2 + (size_t)wave * region;
+    cplx *w = M;
+    double *dq = (double *)(M + D);
+    const unsigned tiles_j = (unsigned)((A.n + 15) / 16);     // the host keeps the tile count below 2^31
+    const int64_t i0 = (int64_t)(blockIdx.x / tiles_j) * 16, j0 = (int64_t)(blockIdx.x % tiles_j) * 16;
+    // The closing det^-1/2 exp(...) of a pair is formed by one lane, after the loop: the c-th finished pair of this
+    // wavefront (c < 256 / nw <= 256) is kept by lane c % 64 in slot c / 64.  (Evaluated inside the loop, the constants
+    // of exp / sincos / sqrt would be hoisted into SGPRs held through the elimination.)
+    cplx pex[4], pmant[4], pv[4];
+    double pexpo[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { pex[b] = c_make(0.0, 0.0); pmant[b] = c_make(1.0, 0.0); pv[b] = c_make(0.0, 0.0); pexpo[b] = 0.0; }
+    int done = 0;
+    for (int pr = wave; pr < 256; pr += nw) {
+        const int64_t i = i0 + (pr >> 4), j = j0 + (pr & 15);
+        if (i >= A.ni || j >= A.n) continue;
+        const double *Qi = A.qp_i + i * 2 * D, *Qj = A.qp + j * 2 * D;
+        const cplx *Cj = (const cplx *)A.cqq + j * (int64_t)D * D, *dj = (const cplx *)A.dvec + j * D;
+        const cplx *Cpi = (const cplx *)A.cqqp_i + i * (int64_t)dp * dp, *Cpj = (const cplx *)A.cqqp + j * (int64_t)dp * dp;
+        const cplx *dpi = (const cplx *)A.dvecp_i + i * dp, *dpj = (const cplx *)A.dvecp + j * dp;
+        wave_lds_sync();                                      // the previous pair's last reads of the region are done
+        for (int a = lane; a < D; a += 64) dq[a] = Qj[a] - Qi[a];
+        wave_lds_sync();
+        // w = C_j dQ (lane a: rows a, a+64, ...); this lane's share of -1/2 dQ^T C_j dQ - d_j . dQ (summed over the
+        // wavefront only at the end: a wave-uniform value here would hold SGPRs through the elimination)
+        cplx exl = c_make(0.0, 0.0);
+        for (int a = lane; a < D; a += 64) {
+            cplx s = c_make(0.0, 0.0);
+            const cplx *row = Cj + (int64_t)a * D;
+#pragma unroll 1
+            for (int c = 0; c < D; ++c) { const double q = dq[c]; s.x = fma(row[c].x, q, s.x); s.y = fma(row[c].y, q, s.y); }
+            w[a] = s;
+            const double q = dq[a];
+            exl.x = fma(q, -0.5 * s.x - dj[a].x, exl.x); exl.y = fma(q, -0.5 * s.y - dj[a].y, exl.y);
+        }
+        wave_lds_sync();
+        // b'_r = (U^T w)_r + conj(d'_i)_r + (d'_j)_r for rows r = lane, lane + 64
+        cplx bq[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = lane + 64 * h;
+            cplx s = c_make(0.0, 0.0);
+            if (r < dp) {
+                s = c_make(dpi[r].x + dpj[r].x, -dpi[r].y + dpj[r].y);
+#pragma unroll 1
+                for (int a = 0; a < D; ++a) { const double u = A.U[a * dp + r]; s.x = fma(u, w[a].x, s.x); s.y = fma(u, w[a].y, s.y); }
+            }
+            bq[h] = s;
+        }
+        wave_lds_sync();                                      // w is overwritten by the matrix from here on
+        for (int r = 0; r < dp; ++r)
+            for (int l = lane; l < dp; l += 64)
+                M[r * stride + l] = c_make(Cpi[r * dp + l].x + Cpj[r * dp + l].x, -Cpi[r * dp + l].y + Cpj[r * dp + l].y);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = lane + 64 * h;
+            if (r < dp) { M[r * stride + dp] = bq[h]; M[dp * stride + r] = bq[h]; }
+        }
+        if (lane == 0) M[dp * stride + dp] = c_make(0.0, 0.0);
+        wave_lds_sync();
+        cplx mant = c_make(1.0, 0.0);                         // det(D'/2pi) = mant * 2^expo
+        int expo = 0;
+        bool singular = false;
+        for (int k = 0; k < dp; ++k) {
+            // pivot among rows k..d'-1 (two candidates per lane)
+            const int r0 = k + lane, r1 = k + lane + 64;
+            const double m0 = r0 < dp ? c_abs2(M[r0 * stride + k]) : -1.0;
+            const double m1 = r1 < dp ? c_abs2(M[r1 * stride + k]) : -1.0;
+            const bool take1 = m1 > m0;
+            const int piv = wave_pivot_row(take1 ? m1 : m0, take1 ? r1 : r0, r0 < dp);
+            if (piv != k) {
+                for (int l = k + lane; l <= dp; l += 64) {
+                    const cplx t = M[k * stride + l];
+                    M[k * stride + l] = M[piv * stride + l];
+                    M[piv * stride + l] = t;
+                }
+                mant = c_make(-mant.x, -mant.y);
+                wave_lds_sync();
+            }
+            const cplx p = M[k * stride + k];
+            if (p.x == 0.0 && p.y == 0.0) { singular = true; break; }
+            mant = c_scale(c_mul(mant, p), 1.0 / (2.0 * 3.14159265358979323846));
+            int e;
+            frexp(fmax(fabs(mant.x), fabs(mant.y)), &e);
+            mant = c_make(ldexp(mant.x, -e), ldexp(mant.y, -e));
+            expo += e;
+            const cplx ip = c_inv(p);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int r = k + 1 + lane + 64 * h;          // rows k+1..d' (row d' is b'^T)
+                if (r <= dp) {
+                    const cplx f = c_mul(M[r * stride + k], ip);
+#pragma unroll 1
+                    for (int l = k + 1; l <= dp; ++l) M[r * stride + l] = c_fnma(f, M[k * stride + l], M[r * stride + l]);
+                }
+            }
+            wave_lds_sync();
+        }
+        if (singular) continue;
+        const cplx bib = M[dp * stride + dp];                 // -b'^T D'^-1 b'
+        const cplx ex = c_make(wave_sum(exl.x) - 0.5 * bib.x, wave_sum(exl.y) - 0.5 * bib.y);
+        if (lane == (done & 63)) {
+            const cplx v = c_mul(c_conj(((const cplx *)A.coef_i)[i]), ((const cplx *)A.coef)[j]);
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (b == done >> 6) { pex[b] = ex; pmant[b] = mant; pexpo[b] = expo; pv[b] = v; }
+        }
+        ++done;
+    }
+    // det^-1/2 exp(ex) = exp(ex - e ln2 / 2) / sqrt(mant): 2^e is real positive, so the principal branch of sqrt(det) is
+    // that of sqrt(mant).  Empty slots add 0 * 1.
+    cplx acc = c_make(0.0, 0.0);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const cplx ol = c_mul(c_inv(c_sqrt(pmant[b])), c_exp(c_make(pex[b].x - 0.5 * pexpo[b] * 0.69314718055994530942, pex[b].y)));
+        acc = c_fma(pv[b], ol, acc);
+    }
+    acc = c_make(wave_sum(acc.x), wave_sum(acc.y));
+    if (lane == 0) { red[2 * wave] = acc.x; red[2 * wave + 1] = acc.y; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double re = 0.0, im = 0.0;
+        for (int v = 0; v < nw; ++v) { re += red[2 * v]; im += red[2 * v + 1]; }
+        A.partials[(size_t)blockIdx.x * 4 + 0] = re;
+        A.partials[(size_t)blockIdx.x * 4 + 1] = im;
+        A.partials[(size_t)blockIdx.x * 4 + 2] = 0.0;
+        A.partials[(size_t)blockIdx.x * 4 + 3] = 0.0;
+    }
+}
+
+// LDS region of one wavefront of wm_pair_sum_wide_kernel (complex elements) and its odd row stride
+static int wmw_stride(int dp) { return (dp + 1) | 1; }
+static int wmw_region(int D, int dp) {
+    const int mat = (dp + 1) * wmw_stride(dp), vec = D + (D + 1) / 2;
+    return mat > vec ? mat : vec;
+}
+
 }  // namespace
 
 extern "C" int64_t sc_wm_pair_sum_tiles(int64_t n) {
@@ -544,13 +705,26 @@ extern "C" int sc_wm_pair_sum_rect(const double *qp_i, const double *coef_i, con
                                    int32_t dprime, double *partials, void *stream) {
     if (!qp_i || !coef_i || !cqqp_i || !dvecp_i || !qp_j || !coef_j || !cqq_j || !dvec_j || !cqqp_j || !dvecp_j || !U || !partials)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_wm_pair_sum: null argument");
-    if (D < 1 || D > WMN_MAXD || dprime < 1 || dprime > WMN_MAXDP || dprime > D)
-        return sc_fail(SC_ERR_UNSUPPORTED, "sc_wm_pair_sum: D=%d d'=%d outside D <= %d, d' <= %d", D, dprime, WMN_MAXD, WMN_MAXDP);
+    if (D < 1 || D > WMW_MAXD || dprime < 1 || dprime > WMW_MAXDP || dprime > D)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_wm_pair_sum: D=%d d'=%d outside 1 <= d' <= D, D <= %d, d' <= %d", D, dprime,
+                       WMW_MAXD, WMW_MAXDP);
     if (ni <= 0 || nj <= 0) return SC_OK;
     const int64_t tiles = sc_wm_pair_sum_rect_tiles(ni, nj);
     if (tiles > 0x7fffffff) return sc_fail(SC_ERR_UNSUPPORTED, "sc_wm_pair_sum: %lld x %lld pairs need more than 2^31 tiles", (long long)ni, (long long)nj);
     WmPairArgs a{qp_i, coef_i, cqqp_i, dvecp_i, qp_j, coef_j, cqq_j, dvec_j, cqqp_j, dvecp_j, U, ni, nj, D, dprime, partials};
-    hipLaunchKernelGGL(wm_pair_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    hipStream_t s = (hipStream_t)stream;
+    if (D <= WMN_MAXD && dprime <= WMN_MAXDP) {
+        hipLaunchKernelGGL(wm_pair_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a);
+        return sc_check_launch("sc_wm_pair_sum");
+    }
+    // one wavefront per pair, up to 4 per tile as the LDS allows (d' = 96: one region of 147 KB)
+    const int stride = wmw_stride(dprime), region = wmw_region(D, dprime);
+    const size_t per_wave = (size_t)region * sizeof(cplx);
+    const int nw = (int)std::min<size_t>(4, (160 * 1024 - 64) / per_wave);
+    const size_t bytes = per_wave * nw;
+    if (hipFuncSetAttribute((const void *)wm_pair_sum_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        return sc_check_launch("sc_wm_pair_sum (LDS attribute)");
+    hipLaunchKernelGGL(wm_pair_sum_wide_kernel, dim3((unsigned)tiles), dim3(64 * nw), bytes, s, a, stride, region);
     return sc_check_launch("sc_wm_pair_sum");
 }
 
