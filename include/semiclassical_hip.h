@@ -281,6 +281,29 @@ int sc_hk_correlate(const sc_state *st, const sc_overlap_consts *ovl_t0, const s
                     const double *vi, const double *probi, const double *nacq, double mc_norm,
                     double *cq_out, double *kq_out, double *partials, void *stream);
 
+/* ---- Monte-Carlo second moments (standard errors of C_auto and k_ic) -----------------------------------------------------
+ * Every entry point with a trailing moments argument does what the one without it does -- same launches, C and k bit for bit --
+ * and in addition forms, per time step, the six sums over the trajectories
+ *     S_rr(C) = sum (Re cq_i)^2, S_ii(C) = sum (Im cq_i)^2, S_ri(C) = sum Re cq_i Im cq_i, and the same three of kq_i
+ * (cq_i, kq_i as defined at sc_hk_correlate: weight included, dynamical phase not), in a fixed summation order.  NULL there
+ * gives the old launch.  The host rotates them by the phase and forms the standard errors (propagators.py, finalize_moments).
+ *   sc_hk_correlate_m   moment_partials[sc_correlate_grid()][6]
+ *   sc_term_moments     the six sums of exported terms cq[n], kq[n] (complex; kq may be NULL: its sums are 0) into
+ *                       moment_partials[sc_term_moments_grid(n)][6] -- for the Walton-Manolopoulos terms of sc_wm_correlate
+ *                       (a pass of its own, not fused into the WM kernels) and for k_ic terms the caller forms itself
+ *                       (position-dependent couplings)
+ *   sc_reduce_moments   moments[0..5] = sum of n_rows partial rows
+ *   sc_reduce_slot_moments_at   ONE launch: the slot sums of sc_reduce_slot_at into row *cursor of slots[.][5], the moment sums
+ *                       into row *cursor of moments[.][6], then *cursor += 1 (the graph-captured loop of run(use_graph=True)) */
+int sc_hk_correlate_m(const sc_state *st, const sc_overlap_consts *ovl_t0, const sc_nac_consts *nc,
+                      const double *vi, const double *probi, const double *nacq, double mc_norm,
+                      double *cq_out, double *kq_out, double *partials, double *moment_partials, void *stream);
+int sc_term_moments_grid(int64_t n);
+int sc_term_moments(const double *cq, const double *kq, int64_t n, double *moment_partials, void *stream);
+int sc_reduce_moments(const double *moment_partials, int32_t n_rows, double *moments, void *stream);
+int sc_reduce_slot_moments_at(const double *corr_partials, int32_t n_corr, const double *moment_partials, int32_t n_mom,
+                              double *slots, double *moments, int64_t *cursor, void *stream);
+
 /* slot[0..3] = sum of correlate partials, slot[4] = (sum of energy partials)/n_energy.
  * Deterministic (fixed summation order).  Either partial buffer may be NULL (its slots are left untouched). */
 int sc_reduce_slot(const double *corr_partials, int32_t n_corr, const double *energy_partials, int32_t n_energy_blocks,
@@ -307,6 +330,13 @@ int sc_hk_run(const sc_potential *pot, const sc_state *st, const sc_hk_consts *h
               const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
               double dt, int32_t nsteps, double *partials, double *slots_out, double *elog, void *stream);
 
+/* sc_hk_run / sc_hk_run_modal with the per-step second moments (see sc_hk_correlate_m) in moments_out[nsteps][6]; `partials` then
+ * holds sc_hk_run_scratch_doubles(n, D, nsteps, 1) doubles (with moments = 0: the 5 * sc_hk_run_slots * nsteps of sc_hk_run). */
+int64_t sc_hk_run_scratch_doubles(int64_t n, int32_t dim, int32_t nsteps, int32_t moments);
+int sc_hk_run_m(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
+                const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
+                double dt, int32_t nsteps, double *partials, double *slots_out, double *elog, double *moments_out, void *stream);
+
 /* sc_hk_run for a CONSTANT dense Hessian with the monodromy blocks of the state in NORMAL-MODE coordinates (round 4).  RK4 of a
  * linear system commutes with a change of basis: with W = m^-1/2 H m^-1/2 = U diag(lambda) U^T, A = m^-1/2 U, B = m^1/2 U and
  *     Mqq~ = A^-1 Mqq A,  Mqp~ = A^-1 Mqp B,  Mpq~ = B^-1 Mpq A,  Mpp~ = B^-1 Mpp B
@@ -323,6 +353,10 @@ int sc_hk_run_modal_supported(const sc_potential *pot, const sc_hk_consts *hk, c
 int sc_hk_run_modal(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
                     const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
                     double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog, void *stream);
+int sc_hk_run_modal_m(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
+                      const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
+                      double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
+                      double *moments_out, void *stream);
 
 /* One HK time step for a CONSTANT dense Hessian (SC_POT_HARMONIC_DENSE) at 16 < D <= 64 with the monodromy blocks of the state in
  * NORMAL-MODE coordinates (ABI 18).  Same contract as sc_hk_step (replaces _rk4_step + EquationsOfMotion.f, propagators.py:86-119,

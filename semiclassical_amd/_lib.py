@@ -104,7 +104,21 @@ SIGNATURES = {
     "sc_nac_initial": (C.c_int, [P(sc_nac_consts), c_double_p, C.c_int64, c_double_p, C.c_void_p]),
     "sc_hk_correlate": (C.c_int, [P(sc_state), P(sc_overlap_consts), P(sc_nac_consts), c_double_p, c_double_p,
                                   c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "sc_hk_correlate_m": (C.c_int, [P(sc_state), P(sc_overlap_consts), P(sc_nac_consts), c_double_p, c_double_p,
+                                    c_double_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "sc_term_moments_grid": (C.c_int, [C.c_int64]),
+    "sc_term_moments": (C.c_int, [c_double_p, c_double_p, C.c_int64, c_double_p, C.c_void_p]),
+    "sc_reduce_moments": (C.c_int, [c_double_p, C.c_int32, c_double_p, C.c_void_p]),
+    "sc_reduce_slot_moments_at": (C.c_int, [c_double_p, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p,
+                                            C.c_void_p]),
     "sc_hk_run_slots": (C.c_int, [C.c_int64, C.c_int32]),
+    "sc_hk_run_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "sc_hk_run_m": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), P(sc_overlap_consts), P(sc_nac_consts), c_double_p,
+                              c_double_p, c_double_p, C.c_double, C.c_double, C.c_int32, c_double_p, c_double_p, c_double_p,
+                              c_double_p, C.c_void_p]),
+    "sc_hk_run_modal_m": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), P(sc_overlap_consts), P(sc_nac_consts),
+                                    c_double_p, c_double_p, c_double_p, C.c_double, C.c_double, C.c_int32, c_double_p, c_double_p,
+                                    c_double_p, c_double_p, c_double_p, C.c_void_p]),
     "sc_hk_run_supported": (C.c_int, [P(sc_potential), P(sc_hk_consts), P(sc_overlap_consts)]),
     "sc_hk_run": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), P(sc_overlap_consts), P(sc_nac_consts), c_double_p,
                             c_double_p, c_double_p, C.c_double, C.c_double, C.c_int32, c_double_p, c_double_p, c_double_p,

@@ -104,12 +104,44 @@ struct CorrArgs {
     double *cq_out, *kq_out, *partials;
 };
 
+// the same plus the second-moment partials [grid][6] of sc_hk_correlate_m: sums of (Re cq)^2, (Im cq)^2, Re cq Im cq, then the
+// same of kq.  A separate type so that the kernels without moments keep their argument block.
+struct CorrMomArgs : CorrArgs {
+    double *mpart;
+};
+template <bool MOM> struct CorrArgsOf { using type = CorrArgs; };
+template <> struct CorrArgsOf<true> { using type = CorrMomArgs; };
+
+// per-lane second moments of one trajectory's terms (fma: the products are not rounded twice)
+__device__ __forceinline__ void add_moments(double (&m)[6], cplx cq, cplx kq) {
+    m[0] = fma(cq.x, cq.x, m[0]); m[1] = fma(cq.y, cq.y, m[1]); m[2] = fma(cq.x, cq.y, m[2]);
+    m[3] = fma(kq.x, kq.x, m[3]); m[4] = fma(kq.y, kq.y, m[4]); m[5] = fma(kq.x, kq.y, m[5]);
+}
+
+// workgroup sums of the six moment accumulators into mpart[blockIdx.x][6], in a fixed order (after the wavefront sums of
+// the main accumulators, which keep their own order)
+__device__ __forceinline__ void store_moments(double (&m)[6], double (&wmom)[4][6], double *mpart, int nw) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) m[i] = wave_sum(m[i]);
+    if (lane == 0) { for (int i = 0; i < 6; ++i) wmom[wave][i] = m[i]; }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double s = 0;
+        for (int w = 0; w < nw; ++w) s += wmom[w][threadIdx.x];
+        mpart[(size_t)blockIdx.x * 6 + threadIdx.x] = s;
+    }
+}
+
 // A wavefront takes 16 consecutive trajectories: their exponent sums are reduced one after the other (lane = mode) and
 // parked in lanes 0..15, then those 16 lanes evaluate the scalar tails -- complex exp, sqrt, the phase, the weight --
 // side by side.  (One trajectory per pass left 63 lanes idle during a tail that is longer than the reductions.)
-__global__ __launch_bounds__(256) void hk_correlate_kernel(CorrArgs A) {
+template <bool MOM>
+__global__ __launch_bounds__(256) void hk_correlate_kernel(typename CorrArgsOf<MOM>::type A) {
     extern __shared__ double smem[];
     __shared__ double wsum[4][4];
+    __shared__ double wmom[MOM ? 4 : 1][6];
+    double mom[6] = {0, 0, 0, 0, 0, 0};
     constexpr int B = 16;
     const int D = A.st.dim, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     double *dvec = smem + (size_t)wave * 2 * D;
@@ -166,13 +198,15 @@ __global__ __launch_bounds__(256) void hk_correlate_kernel(CorrArgs A) {
             cq = c_scale(cq, w);
             acc[0] += cq.x; acc[1] += cq.y;
             if (A.cq_out) ((cplx *)A.cq_out)[tr] = cq;
+            cplx kq = c_make(0.0, 0.0);
             if (A.has_nac) {
                 const cplx nacQ = c_make(A.nc.n2 + mR, -(A.nc.p0n1 + mG) / SC_HBAR);
-                cplx kq = c_mul(c_mul(nacQ, ((const cplx *)A.nacq)[tr]), cq);
+                kq = c_mul(c_mul(nacQ, ((const cplx *)A.nacq)[tr]), cq);
                 kq = c_scale(kq, 1.0 / (SC_HBAR * SC_HBAR));
                 acc[2] += kq.x; acc[3] += kq.y;
                 if (A.kq_out) ((cplx *)A.kq_out)[tr] = kq;
             }
+            if constexpr (MOM) add_moments(mom, cq, kq);
         }
     }
 #pragma unroll
@@ -184,6 +218,7 @@ __global__ __launch_bounds__(256) void hk_correlate_kernel(CorrArgs A) {
         for (int w = 0; w < nw; ++w) s += wsum[w][threadIdx.x];
         A.partials[(size_t)blockIdx.x * 4 + threadIdx.x] = s;
     }
+    if constexpr (MOM) store_moments(mom, wmom, A.mpart, nw);
 }
 
 // Dense (or rank-deficient) width matrices, D <= 16 -- methylium with the reference's Cartesian widths: ONE trajectory per
@@ -194,8 +229,11 @@ __global__ __launch_bounds__(256) void hk_correlate_kernel(CorrArgs A) {
 // lanes evaluate the scalar tails (complex exp, sqrt, phase, weight) side by side.  Replaces, for these shapes, the branch
 // of hk_correlate_kernel that runs one trajectory per wavefront pass with 12 of 64 lanes and re-reads A, B, C from memory
 // per trajectory (0.67 ms per step at n = 1e5, three times the step kernel).
-__global__ __launch_bounds__(256) void hk_correlate_rows16_kernel(CorrArgs A) {
+template <bool MOM>
+__global__ __launch_bounds__(256) void hk_correlate_rows16_kernel(typename CorrArgsOf<MOM>::type A) {
     __shared__ double wsum[4][4];
+    __shared__ double wmom[MOM ? 4 : 1][6];
+    double mom[6] = {0, 0, 0, 0, 0, 0};
     const int D = A.st.dim, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = tid & 15, g = (tid >> 4) & 3;
     const bool own = r < D, nac = A.has_nac != 0;
     double rowA[16], rowB[16], rowC[16];
@@ -256,13 +294,15 @@ __global__ __launch_bounds__(256) void hk_correlate_rows16_kernel(CorrArgs A) {
             cq = c_scale(cq, w);
             acc[0] += cq.x; acc[1] += cq.y;
             if (A.cq_out) ((cplx *)A.cq_out)[tr] = cq;
+            cplx kq = c_make(0.0, 0.0);
             if (nac) {
                 const cplx nacQ = c_make(A.nc.n2 + m[4], -(A.nc.p0n1 + m[5]) / SC_HBAR);
-                cplx kq = c_mul(c_mul(nacQ, ((const cplx *)A.nacq)[tr]), cq);
+                kq = c_mul(c_mul(nacQ, ((const cplx *)A.nacq)[tr]), cq);
                 kq = c_scale(kq, 1.0 / (SC_HBAR * SC_HBAR));
                 acc[2] += kq.x; acc[3] += kq.y;
                 if (A.kq_out) ((cplx *)A.kq_out)[tr] = kq;
             }
+            if constexpr (MOM) add_moments(mom, cq, kq);
         }
     }
 #pragma unroll
@@ -274,6 +314,7 @@ __global__ __launch_bounds__(256) void hk_correlate_rows16_kernel(CorrArgs A) {
         for (int w = 0; w < 4; ++w) sum += wsum[w][threadIdx.x];
         A.partials[(size_t)blockIdx.x * 4 + threadIdx.x] = sum;
     }
+    if constexpr (MOM) store_moments(mom, wmom, A.mpart, 4);
 }
 
 struct ReduceArgs {
@@ -301,6 +342,52 @@ __global__ __launch_bounds__(256) void reduce_slot_kernel(ReduceArgs A) {
         if (A.cpart) for (int k = 0; k < 4; ++k) slot[k] = v[k];
         if (A.epart) slot[4] = v[4] / A.n_energy;
     }
+}
+
+// moment partials [nrows][6] summed in a fixed order into moments[6], or into row *cursor of moments[.][6]; with `cpart` the
+// correlation partials of the same step go to row *cursor of slots[.][5] in the same launch, and the cursor advances once
+struct ReduceMomArgs {
+    const double *mpart;
+    int nmom;
+    double *moments;
+    const double *cpart;
+    int ncorr;
+    double *slots;
+    long long *cursor;
+};
+
+__global__ __launch_bounds__(256) void reduce_moments_kernel(ReduceMomArgs A) {
+    __shared__ double red[40];
+    double v[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = threadIdx.x; i < A.nmom; i += blockDim.x)
+        for (int k = 0; k < 6; ++k) v[k] += A.mpart[(size_t)i * 6 + k];
+    if (A.cpart)
+        for (int i = threadIdx.x; i < A.ncorr; i += blockDim.x)
+            for (int k = 0; k < 4; ++k) v[6 + k] += A.cpart[(size_t)i * 4 + k];
+    block_sum<10>(v, red);
+    if (threadIdx.x == 0) {
+        double *mom = A.moments, *slot = A.slots;
+        if (A.cursor) { mom += 6 * *A.cursor; slot += 5 * *A.cursor; *A.cursor += 1; }
+        for (int k = 0; k < 6; ++k) mom[k] = v[k];
+        if (A.cpart) for (int k = 0; k < 4; ++k) slot[k] = v[6 + k];
+    }
+}
+
+// second moments of exported per-trajectory terms cq[n], kq[n] (complex; kq may be NULL: its three sums are 0) into
+// mpart[blockIdx.x][6]: thread-strided sums, then the workgroup's in a fixed order
+__global__ __launch_bounds__(256) void term_moments_kernel(const double *cq, const double *kq, int64_t n, double *mpart) {
+    __shared__ double red[24];
+    double v[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double cr = cq[2 * i], ci = cq[2 * i + 1];
+        v[0] = fma(cr, cr, v[0]); v[1] = fma(ci, ci, v[1]); v[2] = fma(cr, ci, v[2]);
+        if (kq) {
+            const double kr = kq[2 * i], ki = kq[2 * i + 1];
+            v[3] = fma(kr, kr, v[3]); v[4] = fma(ki, ki, v[4]); v[5] = fma(kr, ki, v[5]);
+        }
+    }
+    block_sum<6>(v, red);
+    if (threadIdx.x < 6) mpart[(size_t)blockIdx.x * 6 + threadIdx.x] = v[threadIdx.x];
 }
 
 __global__ __launch_bounds__(256) void energy_guard_kernel(const double *epart, int nblk, double n, double *elog) {
@@ -380,24 +467,68 @@ extern "C" int sc_nac_initial(const sc_nac_consts *nc, const double *zi, int64_t
     return sc_check_launch("sc_nac_initial");
 }
 
-extern "C" int sc_hk_correlate(const sc_state *st, const sc_overlap_consts *ovl_t0, const sc_nac_consts *nc,
-                               const double *vi, const double *probi, const double *nacq, double mc_norm,
-                               double *cq_out, double *kq_out, double *partials, void *stream) {
+extern "C" int sc_hk_correlate_m(const sc_state *st, const sc_overlap_consts *ovl_t0, const sc_nac_consts *nc,
+                                 const double *vi, const double *probi, const double *nacq, double mc_norm,
+                                 double *cq_out, double *kq_out, double *partials, double *moment_partials, void *stream) {
     if (!st || !ovl_t0 || !vi || !probi || !partials)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_correlate: null argument");
     if (nc && !nacq) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_correlate: nac constants without nacq");
     if (ovl_t0->dim != st->dim) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_correlate: dimension mismatch");
-    CorrArgs a;
+    CorrMomArgs a;
     a.st = *st; a.oc = *ovl_t0; a.has_nac = nc != nullptr;
     if (nc) a.nc = *nc; else a.nc = sc_nac_consts{};
     a.vi = vi; a.probi = probi; a.nacq = nacq; a.mc_norm = mc_norm;
     a.cq_out = cq_out; a.kq_out = kq_out; a.partials = partials;
-    if (!ovl_t0->diag && st->dim <= 16)
-        hipLaunchKernelGGL(hk_correlate_rows16_kernel, dim3(sc_correlate_grid(st->n, st->dim)), dim3(256), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(hk_correlate_kernel, dim3(sc_correlate_grid(st->n, st->dim)), dim3(256),
-                           wave_scratch_bytes(st->dim, ovl_t0->diag), (hipStream_t)stream, a);
+    a.mpart = moment_partials;
+    const CorrArgs &plain = a;
+    const dim3 grid(sc_correlate_grid(st->n, st->dim));
+    const hipStream_t s = (hipStream_t)stream;
+    if (!ovl_t0->diag && st->dim <= 16) {
+        if (moment_partials) hipLaunchKernelGGL(hk_correlate_rows16_kernel<true>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(hk_correlate_rows16_kernel<false>, grid, dim3(256), 0, s, plain);
+    } else {
+        const size_t lds = wave_scratch_bytes(st->dim, ovl_t0->diag);
+        if (moment_partials) hipLaunchKernelGGL(hk_correlate_kernel<true>, grid, dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(hk_correlate_kernel<false>, grid, dim3(256), lds, s, plain);
+    }
     return sc_check_launch("sc_hk_correlate");
+}
+
+extern "C" int sc_hk_correlate(const sc_state *st, const sc_overlap_consts *ovl_t0, const sc_nac_consts *nc,
+                               const double *vi, const double *probi, const double *nacq, double mc_norm,
+                               double *cq_out, double *kq_out, double *partials, void *stream) {
+    return sc_hk_correlate_m(st, ovl_t0, nc, vi, probi, nacq, mc_norm, cq_out, kq_out, partials, nullptr, stream);
+}
+
+// rows of moment partials sc_term_moments writes: one workgroup per 4096 terms (16 per thread), at most 1024
+extern "C" int sc_term_moments_grid(int64_t n) {
+    int64_t blocks = (n + 4095) / 4096;
+    if (blocks < 1) blocks = 1;
+    return (int)(blocks < 1024 ? blocks : 1024);
+}
+
+extern "C" int sc_term_moments(const double *cq, const double *kq, int64_t n, double *moment_partials, void *stream) {
+    if (!cq || !moment_partials) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_term_moments: null argument");
+    if (n <= 0) return SC_OK;
+    hipLaunchKernelGGL(term_moments_kernel, dim3(sc_term_moments_grid(n)), dim3(256), 0, (hipStream_t)stream, cq, kq, n,
+                       moment_partials);
+    return sc_check_launch("sc_term_moments");
+}
+
+extern "C" int sc_reduce_moments(const double *moment_partials, int32_t n_rows, double *moments, void *stream) {
+    if (!moment_partials || !moments) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_reduce_moments: null argument");
+    ReduceMomArgs a{moment_partials, n_rows, moments, nullptr, 0, nullptr, nullptr};
+    hipLaunchKernelGGL(reduce_moments_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return sc_check_launch("sc_reduce_moments");
+}
+
+extern "C" int sc_reduce_slot_moments_at(const double *corr_partials, int32_t n_corr, const double *moment_partials,
+                                         int32_t n_mom, double *slots, double *moments, int64_t *cursor, void *stream) {
+    if (!corr_partials || !moment_partials || !slots || !moments || !cursor)
+        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_reduce_slot_moments_at: null argument");
+    ReduceMomArgs a{moment_partials, n_mom, moments, corr_partials, n_corr, slots, (long long *)cursor};
+    hipLaunchKernelGGL(reduce_moments_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    return sc_check_launch("sc_reduce_slot_moments_at");
 }
 
 extern "C" int sc_reduce_slot(const double *corr_partials, int32_t n_corr, const double *energy_partials,

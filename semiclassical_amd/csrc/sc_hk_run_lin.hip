@@ -39,7 +39,7 @@ struct RunLinLayout {
 // MODAL (round 4, sc_hk_run_modal): the monodromy blocks of the state are in NORMAL-MODE coordinates (the caller transformed them and
 // the prefactor constants), where the step matrix is 2 x 2 per mode: row a of the blocks is multiplied by (phi_qq, phi_qp; phi_pq,
 // phi_pp)_a -- 8 D plain multiply-adds per lane and step instead of the 8 D^2 broadcast multiply-adds of the product with Phi.
-template <int D, int DP, bool DIAG, bool MODAL>
+template <int D, int DP, bool DIAG, bool MODAL, bool MOM>
 __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) void hk_run_lin_kernel(RunArgs R) {
     typedef RunLinLayout<D, DP, DIAG> L;
     constexpr int W = 2 * D, DD = D * D, N = DIAG ? D : DP;
@@ -313,6 +313,7 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
             if (c2.x < 0.0 && det.x < 0.0 && c2.y * det.y < 0.0) sgn = -sgn;       // branch tracker (propagators.py:1045-1047)
             c2 = det;
             // ---- this wavefront's share of step k: one writer per slot ----
+            if constexpr (MOM) run_moments_share<MOM>(R, v5, head, k, slot, lane);
 #pragma unroll
             for (int i = 0; i < 5; ++i) v5[i] = wave_sum(head ? v5[i] : 0.0);
             if (lane == 0) {
@@ -341,28 +342,39 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
     }
 }
 
-template <int D, int DP, bool DIAG, bool MODAL>
+template <int D, int DP, bool DIAG, bool MODAL, bool MOM>
 int launch_one(const RunArgs &a, int grid, hipStream_t s) {
     const size_t lds = RunLinLayout<D, DP, DIAG>::bytes;
-    if (hipFuncSetAttribute((const void *)hk_run_lin_kernel<D, DP, DIAG, MODAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
+    if (hipFuncSetAttribute((const void *)hk_run_lin_kernel<D, DP, DIAG, MODAL, MOM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
         return sc_check_launch("sc_hk_run (LDS attribute)");
-    hipLaunchKernelGGL((hk_run_lin_kernel<D, DP, DIAG, MODAL>), dim3(grid), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((hk_run_lin_kernel<D, DP, DIAG, MODAL, MOM>), dim3(grid), dim3(256), lds, s, a);
     const int rc = sc_check_launch("sc_hk_run (constant-Hessian whole-loop kernel)");
     return rc == SC_OK ? 1 : rc;
 }
+
+// this file is compiled twice: on its own with the kernels of sc_hk_run (MOM = false), and included by sc_hk_run_lin_m.hip with
+// SC_RUN_MOMENTS_TU defined for those of sc_hk_run_m (MOM = true) -- a translation unit of their own, so that the instantiations
+// without moments are compiled exactly as before
+#ifdef SC_RUN_MOMENTS_TU
+#define SC_RUNLIN_MOM true
+#define SC_RUNLIN_ENTRY sc_launch_run_lin_m
+#else
+#define SC_RUNLIN_MOM false
+#define SC_RUNLIN_ENTRY sc_launch_run_lin_plain
+#endif
 template <int D, int DP, bool DIAG>
 int launch(const RunArgs &a, int grid, hipStream_t s, int do_launch) {
     if (a.mode_prop) {
         if constexpr (DIAG) return 0;            // the transformed prefactor constants are dense: no modal kernel for diagonal widths
-        else return do_launch ? launch_one<D, DP, DIAG, true>(a, grid, s) : 1;
+        else return do_launch ? launch_one<D, DP, DIAG, true, SC_RUNLIN_MOM>(a, grid, s) : 1;
     }
-    return do_launch ? launch_one<D, DP, DIAG, false>(a, grid, s) : 1;
+    return do_launch ? launch_one<D, DP, DIAG, false, SC_RUNLIN_MOM>(a, grid, s) : 1;
 }
 
 }  // namespace
 
-int sc_launch_run_lin(const RunArgs &a, int grid, hipStream_t s, int do_launch) {
+int SC_RUNLIN_ENTRY(const RunArgs &a, int grid, hipStream_t s, int do_launch) {
     const int D = a.step.st.dim, dp = a.step.hk.dprime;
     const bool diag = a.step.hk.diag != 0;
     if (!diag && !a.step.hk.real_lr) return 0;
@@ -373,3 +385,9 @@ int sc_launch_run_lin(const RunArgs &a, int grid, hipStream_t s, int do_launch) 
 #undef SC_RUNLIN_CASE
     return 0;
 }
+
+#ifndef SC_RUN_MOMENTS_TU
+int sc_launch_run_lin(const RunArgs &a, int grid, hipStream_t s, int do_launch, bool moments) {
+    return moments && do_launch ? sc_launch_run_lin_m(a, grid, s, do_launch) : sc_launch_run_lin_plain(a, grid, s, do_launch);
+}
+#endif

@@ -29,7 +29,7 @@ __device__ __forceinline__ double sum_row_heads(double v, bool head) { return wa
 #ifndef SC_RUN_OCC
 #define SC_RUN_OCC 2
 #endif
-template <int DP, int KIND>
+template <int DP, int KIND, bool MOM>
 __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R) {
     const StepArgs &A = R.step;
     const int D = A.st.dim, DD = D * D, tid = threadIdx.x, lane = tid & 63, r = tid & 15, grp = tid >> 4, wave = tid >> 6;
@@ -152,6 +152,7 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
             if (c2.x < 0.0 && det.x < 0.0 && c2.y * det.y < 0.0) sgn = -sgn;       // branch tracker (propagators.py:1045-1047)
             c2 = det;
             // ---- this wavefront's share of step k: one writer per slot ----
+            if constexpr (MOM) run_moments_share<MOM>(R, v5, head, k, slot, lane);
 #pragma unroll
             for (int i = 0; i < 5; ++i) v5[i] = sum_row_heads(v5[i], head);
             if (lane == 0) {
@@ -180,6 +181,7 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
     }
 }
 
+#ifndef SC_RUN_MOMENTS_TU
 // slots of one step added in a fixed order -> out[k][0..3], mean <T+V> of the step -> out[k][4]
 __global__ __launch_bounds__(256) void hk_run_reduce_kernel(const double *partials, int slots, double n_traj, double *out) {
     __shared__ double red[32];
@@ -192,6 +194,20 @@ __global__ __launch_bounds__(256) void hk_run_reduce_kernel(const double *partia
     }
     block_sum<5>(v, red);
     if (threadIdx.x < 5) out[(size_t)k * 5 + threadIdx.x] = threadIdx.x < 4 ? v[threadIdx.x] : v[4] / n_traj;
+}
+
+// moment slots of one step added in a fixed order -> out[k][0..5]
+__global__ __launch_bounds__(256) void hk_run_reduce_moments_kernel(const double *mpart, int slots, double *out) {
+    __shared__ double red[24];
+    const int k = blockIdx.x;
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < slots; i += 256) {
+        const double *pp = mpart + ((size_t)k * slots + i) * 6;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) v[j] += pp[j];
+    }
+    block_sum<6>(v, red);
+    if (threadIdx.x < 6) out[(size_t)k * 6 + threadIdx.x] = v[threadIdx.x];
 }
 
 // the energy guard over the steps of a fused run, in order (propagators.py:385-398; sc_energy_guard step by step)
@@ -207,7 +223,30 @@ __global__ void hk_run_guard_kernel(const double *out, int nsteps, double *elog)
     elog[0] = last; elog[1] = prev; elog[2] = worst; elog[3] = count;
 }
 
+#endif  // SC_RUN_MOMENTS_TU
+
 }  // namespace
+
+#ifdef SC_RUN_MOMENTS_TU
+// this file is compiled twice: on its own with the kernels of sc_hk_run (MOM = false), and included by sc_hk_run_sep16_m.hip with
+// SC_RUN_MOMENTS_TU defined for those of sc_hk_run_m (MOM = true) -- a translation unit of their own, so that the instantiations
+// without moments are compiled exactly as before
+int sc_launch_run_sep16_m(const RunArgs &a, int grid, hipStream_t s, int kind, int D) {
+#define SC_RUN_K(DP_, KIND_) hipLaunchKernelGGL((hk_run_sep16_kernel<DP_, KIND_, true>), dim3(grid), dim3(256), 0, s, a)
+#define SC_RUN(DP_)                                                                     \
+    do {                                                                                \
+        if (kind == SC_POT_MORSE) SC_RUN_K(DP_, SC_POT_MORSE);                          \
+        else if (kind == SC_POT_HARMONIC_SEP) SC_RUN_K(DP_, SC_POT_HARMONIC_SEP);       \
+        else SC_RUN_K(DP_, SC_POT_EPS_MORSE);                                           \
+    } while (0)
+    if (D <= 4) SC_RUN(4);
+    else if (D <= 8) SC_RUN(8);
+    else SC_RUN(12);
+#undef SC_RUN
+#undef SC_RUN_K
+    return sc_check_launch("sc_hk_run_m (fused steps)");
+}
+#else
 
 extern "C" int sc_hk_run_slots(int64_t n, int32_t dim) {
     (void)dim;
@@ -235,12 +274,27 @@ extern "C" int sc_hk_run_supported(const sc_potential *pot, const sc_hk_consts *
 
 static int run_whole_loop(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
                           const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                          double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog, void *stream);
+                          double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
+                          double *moments_out, void *stream);
+
+extern "C" int64_t sc_hk_run_scratch_doubles(int64_t n, int32_t dim, int32_t nsteps, int32_t moments) {
+    if (nsteps <= 0) return 0;
+    return (int64_t)(moments ? 11 : 5) * sc_hk_run_slots(n, dim) * (int64_t)nsteps;
+}
 
 extern "C" int sc_hk_run(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
                          const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
                          double dt, int32_t nsteps, double *partials, double *slots_out, double *elog, void *stream) {
-    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, nullptr, partials, slots_out, elog, stream);
+    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, nullptr, partials, slots_out, elog, nullptr,
+                          stream);
+}
+
+extern "C" int sc_hk_run_m(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
+                           const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
+                           double dt, int32_t nsteps, double *partials, double *slots_out, double *elog, double *moments_out,
+                           void *stream) {
+    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, nullptr, partials, slots_out, elog,
+                          moments_out, stream);
 }
 
 extern "C" int sc_hk_run_modal_supported(const sc_potential *pot, const sc_hk_consts *hk, const sc_overlap_consts *ovl) {
@@ -252,16 +306,26 @@ extern "C" int sc_hk_run_modal(const sc_potential *pot, const sc_state *st, cons
                                const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
                                double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
                                void *stream) {
+    return sc_hk_run_modal_m(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, mode_prop, partials, slots_out, elog,
+                             nullptr, stream);
+}
+
+extern "C" int sc_hk_run_modal_m(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
+                                 const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
+                                 double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
+                                 double *moments_out, void *stream) {
     if (!mode_prop) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run_modal: null mode_prop");
     if (!pot || !hk || !ovl_t0 || !sc_hk_run_modal_supported(pot, hk, ovl_t0))
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_run_modal: needs a constant dense Hessian and dense real prefactor constants at an "
                        "instantiated shape D <= 16 (use sc_hk_run)");
-    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, mode_prop, partials, slots_out, elog, stream);
+    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, mode_prop, partials, slots_out, elog,
+                          moments_out, stream);
 }
 
 static int run_whole_loop(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
                           const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                          double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog, void *stream) {
+                          double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
+                          double *moments_out, void *stream) {
     if (!pot || !st || !hk || !ovl_t0 || !vi || !probi || !partials || !slots_out || !elog)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run: null argument");
     if (nc && !nacq) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run: nac constants without nacq");
@@ -284,32 +348,45 @@ static int run_whole_loop(const sc_potential *pot, const sc_state *st, const sc_
     a.vi = vi; a.probi = probi; a.nacq = nacq; a.mc_norm = mc_norm; a.nsteps = nsteps; a.partials = partials;
     a.slots = sc_hk_run_slots(st->n, st->dim);
     a.mode_prop = mode_prop;
-    if (hipMemsetAsync(partials, 0, sizeof(double) * 5 * (size_t)a.slots * (size_t)nsteps, s) != hipSuccess)
+    const bool mom = moments_out != nullptr;
+    if (hipMemsetAsync(partials, 0, sizeof(double) * (size_t)sc_hk_run_scratch_doubles(st->n, st->dim, nsteps, mom), s) != hipSuccess)
         return sc_check_launch("sc_hk_run (partials)");
     const int grid = a.slots / 4, D = st->dim;
     if (lin) {
-        int rc = sc_launch_run_lin(a, grid, s, 1);
+        int rc = sc_launch_run_lin(a, grid, s, 1, mom);
         if (rc < 0) return rc;
         if (rc == 0) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_run: shape D=%d d'=%d not instantiated", D, hk->dprime);
         hipLaunchKernelGGL(hk_run_reduce_kernel, dim3(nsteps), dim3(256), 0, s, partials, a.slots, (double)st->n, slots_out);
+        if (mom)
+            hipLaunchKernelGGL(hk_run_reduce_moments_kernel, dim3(nsteps), dim3(256), 0, s, partials + (size_t)5 * a.slots * nsteps,
+                               a.slots, moments_out);
         hipLaunchKernelGGL(hk_run_guard_kernel, dim3(1), dim3(64), 0, s, slots_out, nsteps, elog);
         return sc_check_launch("sc_hk_run (reduction)");
     }
-#define SC_RUN_K(DP_, KIND_) hipLaunchKernelGGL((hk_run_sep16_kernel<DP_, KIND_>), dim3(grid), dim3(256), 0, s, a)
+#define SC_RUN_K(DP_, KIND_) hipLaunchKernelGGL((hk_run_sep16_kernel<DP_, KIND_, false>), dim3(grid), dim3(256), 0, s, a)
 #define SC_RUN(DP_)                                                                     \
     do {                                                                                \
         if (pot->kind == SC_POT_MORSE) SC_RUN_K(DP_, SC_POT_MORSE);                     \
         else if (pot->kind == SC_POT_HARMONIC_SEP) SC_RUN_K(DP_, SC_POT_HARMONIC_SEP);  \
         else SC_RUN_K(DP_, SC_POT_EPS_MORSE);                                           \
     } while (0)
-    if (D <= 4) SC_RUN(4);
-    else if (D <= 8) SC_RUN(8);
-    else SC_RUN(12);
+    int rc;
+    if (mom) {
+        rc = sc_launch_run_sep16_m(a, grid, s, pot->kind, D);
+    } else {
+        if (D <= 4) SC_RUN(4);
+        else if (D <= 8) SC_RUN(8);
+        else SC_RUN(12);
+        rc = sc_check_launch("sc_hk_run (fused steps)");
+    }
 #undef SC_RUN
 #undef SC_RUN_K
-    int rc = sc_check_launch("sc_hk_run (fused steps)");
     if (rc) return rc;
     hipLaunchKernelGGL(hk_run_reduce_kernel, dim3(nsteps), dim3(256), 0, s, partials, a.slots, (double)st->n, slots_out);
+    if (mom)
+        hipLaunchKernelGGL(hk_run_reduce_moments_kernel, dim3(nsteps), dim3(256), 0, s, partials + (size_t)5 * a.slots * nsteps,
+                           a.slots, moments_out);
     hipLaunchKernelGGL(hk_run_guard_kernel, dim3(1), dim3(64), 0, s, slots_out, nsteps, elog);
     return sc_check_launch("sc_hk_run (reduction)");
 }
+#endif  // SC_RUN_MOMENTS_TU

@@ -177,29 +177,43 @@ class RcclCommunicator(object):
             self.handle = None
 
 
-def flush_correlations(slots, group=None, comm=None):
+def flush_correlations(slots, moments=None, group=None, comm=None):
     """sum the raw per-step correlation sums over all ranks, in place (columns 0..3 of ``slots``).
 
     Column 4 (reserved) is left rank-local.  A single collective per call.  With the ``gloo`` backend a
     device tensor is staged through the host (gloo reduces host memory); with ``nccl`` (RCCL) the
     reduction runs on the device buffers directly.  ``comm``: an ``RcclCommunicator`` -- the same single
     all-reduce through the C-ABI's ``sc_flush_allreduce`` instead of torch.distributed.
+    ``moments``: the (nt, 6) second-moment sums of ``run(..., moments=...)``, summed in place as well -- packed into the
+    same buffer, so that the flush stays one collective.
     """
+    nt = slots.shape[0]
+
+    def packed():
+        if moments is None:
+            return slots[:, :4].contiguous()
+        return torch.cat((slots[:, :4], moments[:nt, :6]), dim=1).contiguous()
+
+    def unpack(buf):
+        slots[:, :4] = buf[:, :4]
+        if moments is not None:
+            moments[:nt, :6] = buf[:, 4:10]
+
     if comm is not None:
-        buf = slots[:, :4].contiguous()
+        buf = packed()
         comm.all_reduce_sum(buf)
-        slots[:, :4] = buf
+        unpack(buf)
         return slots
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return slots
-    buf = slots[:, :4].contiguous()
+    buf = packed()
     if buf.is_cuda and dist.get_backend(group) == "gloo":
         host = buf.cpu()
         dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
         buf.copy_(host)
     else:
         dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
-    slots[:, :4] = buf
+    unpack(buf)
     return slots
 
 

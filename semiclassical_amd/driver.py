@@ -23,7 +23,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import broadening, potentials, propagators, rates, readers, units
+from . import broadening, hostmath, potentials, propagators, rates, readers, units
 from .units import hbar
 
 logger = logging.getLogger(__name__)
@@ -132,14 +132,32 @@ class CorrelationStore(object):
             f"Time steps in {self.path} differ. Delete the old file or change the grid for time propagation."
         assert previous['propagator'] == propagator_name, "Data produced with different propagators cannot be added."
 
-    def add_batch(self, autocorrelation, ic_correlation, ntraj):
-        """fold the means over ``ntraj`` new trajectories into the stored means"""
+    ERROR_KEYS = ('autocorrelation_error', 'ic_correlation_error', 'autocorrelation_second_moment', 'ic_correlation_second_moment')
+
+    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None):
+        """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
+        per-sample second moments (rows (S_rr, S_ii, S_ri) times the batch size, phase applied) of the batch, folded the same
+        way; the standard errors of the pooled means follow from them.  Files and batches that do not both carry them lose
+        the error keys (with a warning): errors over only part of the stored trajectories would be wrong."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
         stored['autocorrelation'] = (ntraj * autocorrelation + done * stored['autocorrelation']) / total
         stored['ic_correlation'] = (ntraj * ic_correlation + done * stored['ic_correlation']) / total
         stored['trajectories'] = total
+        have = 'autocorrelation_second_moment' in stored
+        if second_moments is not None and (have or done == 0):
+            for name, new in zip(('autocorrelation', 'ic_correlation'), second_moments):
+                key = name + '_second_moment'
+                pooled = (ntraj * new + done * stored[key]) / total if have else np.asarray(new, dtype=np.float64)
+                stored[key] = pooled
+                stored[name + '_error'] = hostmath.standard_errors(stored[name], pooled / total, total)
+        elif have or second_moments is not None:
+            logger.warning("standard errors dropped from %s: %s", self.path,
+                           "the stored trajectories have no second moments" if second_moments is not None else
+                           "this task does not compute them (\"standard_errors\": true)")
+            for key in self.ERROR_KEYS:
+                stored.pop(key, None)
         stored.pop('ic_rate', None)          # a rate computed from the old correlation function is stale now
         logger.info(f"<phi(0)|phi(0)>= {stored['autocorrelation'][0]}")
         assert abs(stored['autocorrelation'][0] - 1.0) < 1.0e-3
@@ -158,13 +176,15 @@ def make_propagator(task, Gamma_0, device):
     return propagators.HermanKlukPropagator(Gamma_0, Gamma_0, device=device)
 
 
-def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True):
+def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False):
     """C_auto(t), k_ic(t) of one batch of trajectories: the device loop leaves the raw per-step sums in a device buffer,
     ``flush`` (None on a single rank) adds the buffers of all ranks -- ONE all-reduce per batch, SURVEY 8e -- and the host
     applies the dynamical phase.  ``norm_every`` > 0 logs the wavefunction norm (the O(n^2) convergence diagnostic of
     cli.py:424-429) at every norm_every-th step by cutting the device loop there; with ``across_ranks`` it is the norm of
-    the whole sharded batch (a collective: every rank calls it, ``log`` says who prints)."""
+    the whole sharded batch (a collective: every rank calls it, ``log`` says who prints).  ``errors``: also the per-sample
+    second moments (M_C, M_k) of the batch, (nt, 3) each (see CorrelationStore.add_batch), flushed in the same collective."""
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
+    moments = torch.zeros((nt, 6), dtype=torch.float64, device=propagator.device) if errors else None
     length = norm_every if norm_every > 0 else nt
     pieces = []
     for first in range(0, nt, length):
@@ -174,13 +194,23 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
                 logger.info(f" time/fs= {times[first] * units.autime_to_fs}  norm= {norm:9.6f}")
         count = min(length, nt - first)
         pieces.append((first, count, propagator.t))
-        propagator.run(setup.potential, dt, count, slots=slots[first:first + count])
+        propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
+                       moments=None if moments is None else moments[first:first + count])
     if flush is not None:
-        flush(slots)
+        if moments is None:
+            flush(slots)
+        else:
+            flush(slots, moments)
     propagator.synchronize()                      # raises the energy-conservation error of this rank's trajectories
-    parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
+    if moments is None:
+        parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
+                 for first, count, t0 in pieces]
+        return tuple(np.concatenate(part) for part in zip(*parts))
+    parts = [propagator.phased_moments(slots[first:first + count], moments[first:first + count], t0, dt, setup.zero_point_energy)
              for first, count, t0 in pieces]
-    return tuple(np.concatenate(part) for part in zip(*parts))
+    C, k, mC, mk = (np.concatenate(part) for part in zip(*parts))
+    n = propagator._ntraj_norm
+    return C, k, n * mC, n * mk
 
 
 def run_semiclassical_dynamics(task, device='cuda', comm=None):
@@ -234,7 +264,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     device_seed = int(seed_all) if seed_all is not None else int.from_bytes(os.urandom(8), 'little')
 
     if comm is not None:
-        flush = lambda slots: Dm.flush_correlations(slots, comm=comm)
+        flush = lambda slots, moments=None: Dm.flush_correlations(slots, moments, comm=comm)
     elif world > 1:
         flush = Dm.flush_correlations
     else:
@@ -253,13 +283,14 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
             zi, probi = propagator.draw_initial_conditions(setup.q0, setup.p0, setup.Gamma_0, per_batch)
             propagator.set_initial_conditions(setup.q0, setup.p0, setup.Gamma_0, zi[:, mine], probi[mine],
                                               ntraj_total=per_batch)
-        autocorrelation, ic_correlation = propagate_batch(propagator, setup, dt, nt, times,
-                                                          norm_every=task.get('calc_norm_every', 0), flush=flush,
-                                                          across_ranks=world > 1 and comm is None, log=writer)
+        errors = bool(task.get('standard_errors', False))
+        out = propagate_batch(propagator, setup, dt, nt, times, norm_every=task.get('calc_norm_every', 0), flush=flush,
+                              across_ranks=world > 1 and comm is None, log=writer, errors=errors)
+        autocorrelation, ic_correlation = out[:2]
         assert not np.isnan(autocorrelation).any(), f"encountered NaN's in autocorrelation : {autocorrelation}"
         assert not np.isnan(ic_correlation).any(), f"encountered NaN's in IC correlation : {ic_correlation}"
         if writer:
-            store.add_batch(autocorrelation, ic_correlation, per_batch)
+            store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:] if errors else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -181,3 +181,27 @@ class WMConstants(object):
         self.Bq = Bq.contiguous()
         self.inv_scale_a = 1.0 / (2.0 * math.sqrt(alpha * beta))
         self.inv_two_pi = 1.0 / (2.0 * np.pi)
+
+
+def rotate_second_moments(m3, theta):
+    """second moments (S_rr, S_ii, S_ri) of complex terms c_i -> those of c_i e^{i theta} (rows of m3 (..., 3), theta (...,)).
+    Exact for a phase shared by every term: the 2 x 2 matrix [[S_rr, S_ri], [S_ri, S_ii]] is conjugated by the rotation."""
+    m3 = np.asarray(m3, dtype=np.float64)
+    c, s = np.cos(theta), np.sin(theta)
+    rr, ii, ri = m3[..., 0], m3[..., 1], m3[..., 2]
+    return np.stack((c * c * rr - 2.0 * c * s * ri + s * s * ii,
+                     s * s * rr + 2.0 * c * s * ri + c * c * ii,
+                     c * s * (rr - ii) + (c * c - s * s) * ri), axis=-1)
+
+
+def standard_errors(mean, m3, ntraj):
+    """sigma_Re + i sigma_Im of a Monte-Carlo mean = sum_i c_i with weights 1/N inside c_i, from the sums m3 = (S_rr, S_ii, S_ri)
+    of the same terms:  sigma_Re = sqrt(max(N S_rr - (Re mean)^2, 0) / (N - 1)), sigma_Im likewise; NaN for N = 1"""
+    mean = np.asarray(mean, dtype=np.complex128)
+    m3 = np.asarray(m3, dtype=np.float64)
+    n = float(ntraj)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        den = (n - 1.0) if n > 1 else np.nan
+        sr = np.sqrt(np.maximum(n * m3[..., 0] - mean.real ** 2, 0.0) / den)
+        si = np.sqrt(np.maximum(n * m3[..., 1] - mean.imag ** 2, 0.0) / den)
+    return sr + 1j * si

@@ -206,6 +206,9 @@ class HermanKlukPropagator(object):
         self._gcorr = lib.sc_correlate_grid(n, d)
         self._epart = torch.zeros(self._gstep, dtype=F64, device=dev)
         self._cpart = torch.zeros((self._gcorr, 4), dtype=F64, device=dev)
+        self._gterm = lib.sc_term_moments_grid(n)
+        # second-moment partials (standard errors): rows of sc_hk_correlate_m or of sc_term_moments
+        self._mpart = torch.zeros((max(self._gcorr, self._gterm), 6), dtype=F64, device=dev)
         self._cq = torch.zeros(n, dtype=C128, device=dev)
         self._kq = torch.zeros(n, dtype=C128, device=dev)
         self._slot = torch.zeros(8, dtype=F64, device=dev)
@@ -544,30 +547,50 @@ class HermanKlukPropagator(object):
     def _mc_norm(self):
         return self._ntraj_norm * (2 * np.pi * hbar) ** self.dim
 
-    def _reduce_into(self, partials, count, slot_ptr, cursor):
-        """sums of the per-workgroup partials into the slot at `slot_ptr`, or into row *cursor of the slot buffer"""
+    def _reduce_into(self, partials, count, slot_ptr, cursor, mom_ptr=None, mom_rows=None):
+        """sums of the per-workgroup partials into the slot at `slot_ptr`, or into row *cursor of the slot buffer; with `mom_ptr`
+        also the six moment sums of the first `mom_rows` rows of self._mpart into the moment row there (with a cursor: the same
+        launch, one advance)"""
+        s = self._stream()
         if cursor is None:
-            check(lib.sc_reduce_slot(ptr(partials), count, None, 0, 1.0, C_void(slot_ptr), self._stream()))
+            check(lib.sc_reduce_slot(ptr(partials), count, None, 0, 1.0, C_void(slot_ptr), s))
+            if mom_ptr is not None:
+                check(lib.sc_reduce_moments(ptr(self._mpart), mom_rows, C_void(mom_ptr), s))
+        elif mom_ptr is None:
+            check(lib.sc_reduce_slot_at(ptr(partials), count, C_void(slot_ptr), ptr(cursor), s))
         else:
-            check(lib.sc_reduce_slot_at(ptr(partials), count, C_void(slot_ptr), ptr(cursor), self._stream()))
+            check(lib.sc_reduce_slot_moments_at(ptr(partials), count, ptr(self._mpart), mom_rows, C_void(slot_ptr),
+                                                C_void(mom_ptr), ptr(cursor), s))
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None):
+    def _term_moments(self, has_k):
+        """moment partials of the exported per-trajectory terms _cq (and _kq) into self._mpart; returns their row count"""
+        check(lib.sc_term_moments(ptr(self._cq), ptr(self._kq) if has_k else None, self.ntraj, ptr(self._mpart), self._stream()))
+        return self._gterm
+
+    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None, mom_ptr=None):
         """per-trajectory terms + their sums for the current state into the 5-double slot at `slot_ptr` (`slot_row`: the same
         five doubles as a tensor, needed when the k_ic sum is formed by torch: position-dependent couplings; `state`: another
-        view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi)"""
+        view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi; `mom_ptr`: the six second-moment
+        sums go to the 6 doubles there, formed inside the correlate kernel)"""
         s = self._stream()
         nac = self._nac
         generic = getattr(self, "_nac_generic", None) is not None
         per_trajectory = per_trajectory or generic
+        in_kernel = mom_ptr is not None and not generic
         with self._timed("hk_correlate"):
-            check(lib.sc_hk_correlate(self._state if state is None else state, self._ovl_t0, nac, ptr(self._vi), ptr(self.probi),
-                                      ptr(self._nacq) if nac is not None else None, self._mc_norm(),
-                                      ptr(self._cq) if per_trajectory else None,
-                                      ptr(self._kq) if per_trajectory else None, ptr(self._cpart), s))
-        self._reduce_into(self._cpart, self._gcorr, slot_ptr, cursor)
+            check(lib.sc_hk_correlate_m(self._state if state is None else state, self._ovl_t0, nac, ptr(self._vi), ptr(self.probi),
+                                        ptr(self._nacq) if nac is not None else None, self._mc_norm(),
+                                        ptr(self._cq) if per_trajectory else None,
+                                        ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
+                                        ptr(self._mpart) if in_kernel else None, s))
+        self._reduce_into(self._cpart, self._gcorr, slot_ptr, cursor, mom_ptr if in_kernel else None, self._gcorr)
         if generic:
             assert slot_row is not None and cursor is None
             self._generic_kic(slot_row)
+            if mom_ptr is not None:
+                # k_ic terms formed by torch (position-dependent couplings): the moments of the exported terms
+                rows = self._term_moments(True)
+                check(lib.sc_reduce_moments(ptr(self._mpart), rows, C_void(mom_ptr), s))
 
     def _correlate_current(self, need_nac):
         if self._corr_step == self._nsteps and (self._corr_has_nac or not need_nac):
@@ -595,7 +618,7 @@ class HermanKlukPropagator(object):
         k = complex(self._slot_host[2], self._slot_host[3])
         return k * np.exp(1j / hbar * self.t * energy0_es)
 
-    def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False):
+    def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False):
         """The caller loop of cli.py:401-436 on the device: ``nt`` times (C_auto, k_ic, step), no host sync.
 
         Returns ``(autocorrelation[nt], ic_correlation[nt])`` as complex NumPy arrays.  With ``slots`` (a
@@ -612,37 +635,52 @@ class HermanKlukPropagator(object):
         Separable potentials with diagonal width matrices and 16 < D <= 64 advance TWO time steps per launch while the monodromy
         blocks are known to be diagonal (``sc_hk_step_multi``: the second step's reads come from the memory-side cache; results
         bit-identical to one launch per step; ``pair_steps = False`` switches it off).
+
+        Standard errors: ``moments`` (a contiguous float64 device tensor (>= nt, 6), parallel to ``slots``) receives per step the
+        sums over the trajectories of (Re c_i)^2, (Im c_i)^2, Re c_i Im c_i of the C_auto terms, then the same of the k_ic terms,
+        without the dynamical phase (``finalize_moments`` applies it and forms the errors).  With ``slots=None`` and
+        ``standard_errors=True`` the return value is ``(C, k, sigma_C, sigma_k)``, sigma = sigma_Re + i sigma_Im of each step.
+        C and k are the same bit for bit with or without moments.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
         dt = float(dt)
         self._remember_nac(potential)
         own = slots is None
+        if standard_errors and not own:
+            raise ValueError("standard_errors=True returns the errors of run()'s own slots: pass moments= together with slots")
         if own:
             slots = torch.zeros((nt, 5), dtype=F64, device=self.device)
+            if standard_errors and moments is None:
+                moments = torch.zeros((nt, 6), dtype=F64, device=self.device)
         else:
             self._check_slots(slots, nt)
+        if moments is not None:
+            self._check_slots(moments, nt, width=6, name="moments")
         t0 = self.t
         base = slots.data_ptr()
+        mbase = None if moments is None else moments.data_ptr()
+        mrow = (lambda k: None) if mbase is None else (lambda k: mbase + 48 * k)
         fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model") and self.dim <= 64
                  and self._nac_generic is None)
         desc = self._potential_descriptor(potential, dt) if fused else None
         if fused and self._whole_loop_applies(desc):
             # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run)
-            self._run_whole_loop(desc, dt, nt, slots, potential)
+            self._run_whole_loop(desc, dt, nt, slots, potential, moments)
         elif (use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing
               and self._modal_step_constants(potential, desc, dt) is None):
             # (the normal-mode step runs the plain loop: its first step may change the basis of the blocks)
-            self._run_graph(potential, dt, nt, desc, slots)
+            self._run_graph(potential, dt, nt, desc, slots, mbase)
         else:
             pairs = fused and nt >= 2 and self._multi_applies(desc)
             k = 0
             while k < nt:
-                self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k])
+                self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k], mom_ptr=mrow(k))
                 if pairs and k + 1 < nt:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
-                    self._launch_correlate(base + 40 * (k + 1), per_trajectory=False, state=self._multi["state_mid"])
+                    self._launch_correlate(base + 40 * (k + 1), per_trajectory=False, state=self._multi["state_mid"],
+                                           mom_ptr=mrow(k + 1))
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -654,7 +692,21 @@ class HermanKlukPropagator(object):
         if not own:
             return None
         self.synchronize()
+        if standard_errors:
+            return self.finalize_slots(slots, t0, dt, energy0_es) + self.finalize_moments(slots, moments, t0, dt, energy0_es,
+                                                                                          self._ntraj_norm)
         return self.finalize_slots(slots, t0, dt, energy0_es)
+
+    def standard_errors(self, energy0_es=0.0):
+        """(sigma_C, sigma_k) of the current step: the Monte-Carlo standard errors sigma_Re + i sigma_Im of autocorrelation() and
+        ic_correlation() at this time (the step-by-step counterpart of run(..., standard_errors=True)).  sigma_k is 0 until the
+        coupling is known (call ic_correlation(potential) first).  Synchronises."""
+        slot = torch.zeros((1, 5), dtype=F64, device=self.device)
+        mom = torch.zeros((1, 6), dtype=F64, device=self.device)
+        self._launch_correlate(slot.data_ptr(), slot_row=slot[0], mom_ptr=mom.data_ptr())
+        self.synchronize()
+        sc, sk = self.finalize_moments(slot, mom, self.t, 0.0, energy0_es, self._ntraj_norm)
+        return complex(sc[0]), complex(sk[0])
 
     _whole_loop_ok = True           # WM needs its own per-step kernel between the steps
 
@@ -750,18 +802,18 @@ class HermanKlukPropagator(object):
             self._to_normal_modes(self._modal_basis, forward=False)
             self._modal_basis = None
 
-    def _run_whole_loop(self, desc, dt, nt, slots, potential=None):
+    def _run_whole_loop(self, desc, dt, nt, slots, potential=None, moments=None):
         self._leave_modal()
         if desc.kind not in (_lib.SC_POT_MORSE, _lib.SC_POT_HARMONIC_SEP, _lib.SC_POT_EPS_MORSE):
             self._blocks_structurally_diagonal = False
         self._sync_dense_mono(leave_diagonal=True)
         self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
-        nslots = lib.sc_hk_run_slots(self.ntraj, self.dim)
-        # per-step partial sums of every wavefront: 40 nslots bytes per step; long runs go in launches of <= 512 steps
+        # per-step partial sums of every wavefront: 40 sc_hk_run_slots bytes per step; long runs go in launches of <= 512 steps
         # (<= 84 MB of partials at 4096 slots, reused: the launches are ordered on the stream), the state stays on the device
         # in between and is read / written once per launch (<= 1 KB per trajectory at D <= 12: negligible against 512 steps)
         chunk = min(nt, 512)
-        partials = torch.empty((chunk, nslots, 5), dtype=F64, device=self.device)
+        mom = moments is not None
+        partials = torch.empty(lib.sc_hk_run_scratch_doubles(self.ntraj, self.dim, chunk, int(mom)), dtype=F64, device=self.device)
         nac = self._nac
         modal = self._modal_constants(potential, desc, dt) if nt >= self.normal_modes_from else None
         if modal is not None:
@@ -770,10 +822,14 @@ class HermanKlukPropagator(object):
             k = min(chunk, nt - k0)
             tail = (ptr(partials), slots.data_ptr() + 40 * k0, ptr(self._elog), self._stream())
             head = (self._ovl_t0, nac, ptr(self._vi), ptr(self.probi), ptr(self._nacq) if nac is not None else None, self._mc_norm(), dt, k)
+            if mom:
+                tail = tail[:3] + (C_void(moments.data_ptr() + 48 * k0), tail[3])
             if modal is not None:
-                check(lib.sc_hk_run_modal(desc, self._state, modal["hk"], *head, ptr(modal["phi"]), *tail))
+                run = lib.sc_hk_run_modal_m if mom else lib.sc_hk_run_modal
+                check(run(desc, self._state, modal["hk"], *head, ptr(modal["phi"]), *tail))
             else:
-                check(lib.sc_hk_run(desc, self._state, self._hk, *head, *tail))
+                run = lib.sc_hk_run_m if mom else lib.sc_hk_run
+                check(run(desc, self._state, self._hk, *head, *tail))
         if modal is not None:
             self._to_normal_modes(modal, forward=False)
         self._run_scratch = partials          # alive until the stream has consumed it
@@ -827,13 +883,13 @@ class HermanKlukPropagator(object):
             check(lib.sc_energy_guard(C_void(m["epart"].data_ptr() + 8 * sub * self._gstep), self._gstep, float(n), ptr(self._elog), s))
         self._nsteps += 2
 
-    def _run_graph(self, potential, dt, nt, desc, slots):
+    def _run_graph(self, potential, dt, nt, desc, slots, mbase=None):
         """first iteration eagerly (lazy set-up, layout conversion), then one captured iteration replayed nt - 1 times"""
         base = slots.data_ptr()
         cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
 
         def iteration():
-            self._launch_correlate(base, per_trajectory=False, cursor=cursor)
+            self._launch_correlate(base, per_trajectory=False, cursor=cursor, mom_ptr=mbase)
             self._launch_step(potential, dt, desc=desc, remembered=True)
         iteration()
         graph = torch.cuda.CUDAGraph()
@@ -851,11 +907,11 @@ class HermanKlukPropagator(object):
             self._wm_step = self._nsteps      # the WM terms of the current state were produced by the last replay
         self._graph = graph                  # keeps the captured launch parameters alive until the work has run
 
-    def _check_slots(self, slots, nt):
-        """the kernels write 5 doubles at slots + 40 k for k < nt: refuse anything that is not exactly that buffer"""
-        if not (isinstance(slots, torch.Tensor) and slots.dtype == F64 and slots.dim() == 2 and slots.shape[1] == 5
+    def _check_slots(self, slots, nt, width=5, name="slots"):
+        """the kernels write `width` doubles at slots + 8 width k for k < nt: refuse anything that is not exactly that buffer"""
+        if not (isinstance(slots, torch.Tensor) and slots.dtype == F64 and slots.dim() == 2 and slots.shape[1] == width
                 and slots.shape[0] >= nt and slots.is_contiguous() and slots.device == self.device):
-            raise ValueError(f"slots has to be a contiguous float64 tensor of shape (>= {nt}, 5) on {self.device}, got "
+            raise ValueError(f"{name} has to be a contiguous float64 tensor of shape (>= {nt}, {width}) on {self.device}, got "
                              f"{getattr(slots, 'dtype', type(slots))} {tuple(getattr(slots, 'shape', ()))} on "
                              f"{getattr(slots, 'device', '?')}")
 
@@ -866,6 +922,23 @@ class HermanKlukPropagator(object):
         times = t0 + hostmath.time_grid(raw.shape[0], dt)
         phase = np.exp(1j / hbar * times * energy0_es)
         return (raw[:, 0] + 1j * raw[:, 1]) * phase, (raw[:, 2] + 1j * raw[:, 3]) * phase
+
+    @staticmethod
+    def phased_moments(slots, moments, t0, dt, energy0_es):
+        """(C', k', M_C', M_k'): the phased means of finalize_slots and the second-moment sums (S_rr, S_ii, S_ri) of the phased
+        terms, rows (nt, 3) -- the rotation is exact because the phase is the same for every trajectory"""
+        C, k = HermanKlukPropagator.finalize_slots(slots, t0, dt, energy0_es)
+        m = moments.detach().cpu().numpy() if isinstance(moments, torch.Tensor) else np.asarray(moments)
+        m = m[:C.shape[0]]
+        theta = (t0 + hostmath.time_grid(C.shape[0], dt)) * energy0_es / hbar
+        return C, k, hostmath.rotate_second_moments(m[:, 0:3], theta), hostmath.rotate_second_moments(m[:, 3:6], theta)
+
+    @staticmethod
+    def finalize_moments(slots, moments, t0, dt, energy0_es, ntraj_norm):
+        """standard errors (sigma_C, sigma_k) of the phased means, sigma_Re + i sigma_Im per step, from the raw slot sums and the
+        moment sums of run(..., moments=...) (summed over ranks when sharded); ntraj_norm = N of the Monte-Carlo weight 1/N"""
+        C, k, mC, mk = HermanKlukPropagator.phased_moments(slots, moments, t0, dt, energy0_es)
+        return hostmath.standard_errors(C, mC, ntraj_norm), hostmath.standard_errors(k, mk, ntraj_norm)
 
     # ------------------------------------------------------------------ data access (reference :914-948)
     @property
@@ -1238,13 +1311,18 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         Dm.all_reduce_sum(slot, group)
         return float(torch.sqrt(slot[0]).item())
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None):
+    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, mom_ptr=None):
         # the per-trajectory terms were produced together with the prefactor; recompute (with the stored branch
         # signs, no tracking) only if the coupling vector was not known at that time
         knows_nac = self._wm_nac_bufs is not None or self._wm_nac_traj is not None
         if self._wm_step != self._nsteps or (knows_nac and not self._wm_has_nac):
             self._wm_launch(0)
-        self._reduce_into(self._wpart, self._gwm, slot_ptr, cursor)
+        rows = None
+        if mom_ptr is not None:
+            # sc_wm_correlate exports every trajectory's terms exactly once (register kernel or its pivoted re-run): their moments,
+            # in a pass of its own (not fused into the WM kernels)
+            rows = self._term_moments(self._wm_has_nac)
+        self._reduce_into(self._wpart, self._gwm, slot_ptr, cursor, mom_ptr, rows)
 
     def _correlate_current(self, need_nac):
         if self._corr_step == self._nsteps and (self._corr_has_nac or not need_nac):
