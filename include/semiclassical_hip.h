@@ -391,14 +391,25 @@ int sc_wm_correlate(const sc_state *st, const sc_wm_consts *wc, const double *zi
                     double mc_norm, int32_t track, int32_t has_nac, double *cq_out, double *kq_out,
                     double *partials, void *stream);
 
-/* partner atoms per atom the sGDML kernel instantiated for a molecule of n_atoms atoms holds (8, 16, 20, 24 or 32);
- * -1 beyond 48 atoms, which sc_gdml_eval / sc_gdml_stage refuse */
+/* partner atoms per atom the single-workgroup sGDML kernels (one workgroup per geometry, everything in LDS and registers)
+ * instantiated for a molecule of n_atoms atoms hold (8, 16, 20, 24, 32, 40 or 48); -1 beyond 48 atoms, where
+ * sc_gdml_eval / sc_gdml_stage take the multi-kernel route with caller-owned scratch instead */
 int sc_gdml_row_len(int32_t n_atoms);
+/* largest molecule sc_gdml_eval / sc_gdml_stage accept (170 atoms: 3N <= 510); beyond it they return SC_ERR_UNSUPPORTED */
+int sc_gdml_max_atoms(void);
+/* bytes of the `scratch` sc_gdml_eval_scratch / sc_gdml_stage_scratch need for a model of n_atoms atoms and n_train (permutation-expanded) training
+ * points: 0 for n_atoms <= 48; above, a fixed batch of geometries (the calls walk n in batches, so the size does not
+ * depend on n); -1 beyond sc_gdml_max_atoms() */
+int64_t sc_gdml_scratch_bytes(int32_t n_atoms, int32_t n_train);
 
 /* E - origin [n], dE/dr [n][3N], d2E/drdr [n][3N][3N] of the sGDML model at the geometries r [n][3N].
  * Replaces GDMLPredict.forward / MolecularGDMLPotential.harmonic_approximation (gdml_predictor.py:96-250). */
 int sc_gdml_eval(const sc_gdml_model *g, const double *r, int64_t n, double *energy, double *grad, double *hess,
                  void *stream);
+/* the same with caller-owned device scratch of sc_gdml_scratch_bytes(n_atoms, n_train) bytes (one buffer per stream: the
+ * call writes it), required beyond 48 atoms and NULL allowed where that size is 0; sc_gdml_eval = scratch NULL */
+int sc_gdml_eval_scratch(const sc_gdml_model *g, double *scratch, const double *r, int64_t n, double *energy, double *grad,
+                         double *hess, void *stream);
 
 /* One RK4 stage (stage = 0..3) of (q, p, S) on the sGDML surface: stage point from the previous slope, potential
  * evaluation, slopes, stage Hessian -> sc->hess; stage 3 also writes the new (q, p, S) and the per-workgroup sums of
@@ -414,6 +425,9 @@ int sc_stage_consume(const sc_state *st, const sc_dense_scratch *sc, const doubl
                      const double *grad, double dt, int32_t stage, double *energy_partials, void *stream);
 int sc_gdml_stage(const sc_gdml_model *g, const sc_state *st, const sc_dense_scratch *sc, double dt, int32_t stage,
                   double *energy_partials, void *stream);
+/* sc_gdml_stage with caller-owned device scratch (as sc_gdml_eval_scratch) */
+int sc_gdml_stage_scratch(const sc_gdml_model *g, double *scratch, const sc_state *st, const sc_dense_scratch *sc, double dt,
+                          int32_t stage, double *energy_partials, void *stream);
 
 /* RK4 of the four monodromy blocks with the four stage Hessians hess[n][4][D][D] (each used as A[i][k] = hess[k][i];
  * the built-in potentials produce symmetric images), then the HK prefactor (diagonal or dense/rank-deficient width

@@ -142,8 +142,14 @@ SIGNATURES = {
     "sc_wm_pair_sum": (C.c_int, [c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                  C.c_int64, C.c_int32, C.c_int32, c_double_p, C.c_void_p]),
     "sc_gdml_row_len": (C.c_int, [C.c_int32]),
+    "sc_gdml_max_atoms": (C.c_int, []),
+    "sc_gdml_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "sc_gdml_eval": (C.c_int, [P(sc_gdml_model), c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p,
                                C.c_void_p]),
+    "sc_gdml_eval_scratch": (C.c_int, [P(sc_gdml_model), c_double_p, c_double_p, C.c_int64, c_double_p, c_double_p,
+                                       c_double_p, C.c_void_p]),
+    "sc_gdml_stage_scratch": (C.c_int, [P(sc_gdml_model), c_double_p, P(sc_state), P(sc_dense_scratch), C.c_double,
+                                        C.c_int32, c_double_p, C.c_void_p]),
     "sc_dense_grid": (C.c_int, [C.c_int64]),
     "sc_gdml_stage": (C.c_int, [P(sc_gdml_model), P(sc_state), P(sc_dense_scratch), C.c_double, C.c_int32,
                                 c_double_p, C.c_void_p]),

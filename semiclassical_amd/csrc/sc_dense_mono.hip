@@ -729,15 +729,19 @@ struct StageArgs2 {
     double dt;
     int stage;
     double *epart;
+    // trajectories t0 <= tr < t1 (V, grad, r_out indexed by tr - t0); accumulate: epart[] += instead of = (the sGDML route
+    // beyond 48 atoms walks the trajectories in batches, sc_gdml_large.hip)
+    int64_t t0, t1;
+    int accumulate;
 };
 
 __global__ __launch_bounds__(256) void stage_point_kernel(StageArgs2 A) {
     const int D = A.st.dim, s = A.stage;
     const double c = (s == 0) ? 0.0 : (s == 3 ? A.dt : 0.5 * A.dt);
-    const int64_t total = A.st.n * D;
+    const int64_t total = (A.t1 - A.t0) * D;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t tr = e / D;
-        const int i = (int)(e - tr * D);
+        const int64_t tr = A.t0 + e / D;
+        const int i = (int)(e - (tr - A.t0) * D);
         A.r_out[e] = A.st.qp[tr * 2 * D + i] + (s ? c * A.sc.kprev[tr * 2 * D + i] : 0.0);
     }
 }
@@ -748,10 +752,10 @@ __global__ __launch_bounds__(256) void stage_consume_kernel(StageArgs2 A) {
     const double h6 = dt / 6.0;
     __shared__ double wsum[4];
     double esum = 0.0;
-    for (int64_t tr = (int64_t)blockIdx.x * 4 + wave; tr < A.st.n; tr += (int64_t)gridDim.x * 4) {
+    for (int64_t tr = A.t0 + (int64_t)blockIdx.x * 4 + wave; tr < A.t1; tr += (int64_t)gridDim.x * 4) {
         double *qp = A.st.qp + tr * 2 * D;
         double *kprev = A.sc.kprev + tr * 2 * D, *ksum = A.sc.ksum + tr * 2 * D;
-        const double *g = A.grad + tr * D;
+        const double *g = A.grad + (tr - A.t0) * D;
         double tk = 0.0;
         for (int i = lane; i < D; i += 64) {
             const double ps = qp[D + i] + (s ? c * kprev[D + i] : 0.0);       // momentum at the stage point
@@ -764,14 +768,17 @@ __global__ __launch_bounds__(256) void stage_consume_kernel(StageArgs2 A) {
         }
         tk = wave_sum(tk);
         if (lane == 0) {
-            const double e = A.V[tr], ds = tk - e, acc = (s ? A.sc.ssum[tr] : 0.0) + w * ds;
+            const double e = A.V[tr - A.t0], ds = tk - e, acc = (s ? A.sc.ssum[tr] : 0.0) + w * ds;
             if (s < 3) A.sc.ssum[tr] = acc;
             else { A.st.act[tr] += h6 * acc; esum += tk + e; }
         }
     }
     if (lane == 0) wsum[wave] = esum;
     __syncthreads();
-    if (threadIdx.x == 0 && A.epart && s == 3) A.epart[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (threadIdx.x == 0 && A.epart && s == 3) {
+        const double sum = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        A.epart[blockIdx.x] = A.accumulate ? A.epart[blockIdx.x] + sum : sum;
+    }
 }
 
 }  // namespace
@@ -782,15 +789,31 @@ extern "C" int sc_mono_phase_clock(unsigned long long *buf) {
 }
 #endif
 
+// trajectories [t0, t1) of the state; r_out / V / grad hold rows 0 .. t1 - t0 - 1.  sc_stage_consume_range keeps the grid of
+// all n trajectories, so that energy_partials has sc_dense_grid(n) rows whichever range it is called with; batches after the
+// first (accumulate != 0) add to them.
+int sc_stage_point_range(const sc_state *st, const sc_dense_scratch *sc, double dt, int stage, double *r_out, int64_t t0,
+                         int64_t t1, hipStream_t stream) {
+    StageArgs2 a{*st, *sc, nullptr, nullptr, nullptr, r_out, dt, stage, nullptr, t0, t1, 0};
+    const int64_t blocks = ((t1 - t0) * st->dim + 255) / 256;
+    hipLaunchKernelGGL(stage_point_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, a);
+    return sc_check_launch("sc_stage_point");
+}
+
+int sc_stage_consume_range(const sc_state *st, const sc_dense_scratch *sc, const double *inv_mass, const double *V,
+                           const double *grad, double dt, int stage, double *energy_partials, int64_t t0, int64_t t1,
+                           int accumulate, hipStream_t stream) {
+    StageArgs2 a{*st, *sc, inv_mass, V, grad, nullptr, dt, stage, energy_partials, t0, t1, accumulate};
+    hipLaunchKernelGGL(stage_consume_kernel, dim3(sc_dense_grid(st->n)), dim3(256), 0, stream, a);
+    return sc_check_launch("sc_stage_consume");
+}
+
 extern "C" int sc_stage_point(const sc_state *st, const sc_dense_scratch *sc, double dt, int32_t stage, double *r_out,
                               void *stream) {
     if (!st || !sc || !sc->kprev || !r_out) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_stage_point: null argument");
     if (stage < 0 || stage > 3) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_stage_point: stage %d", stage);
     if (st->n <= 0) return SC_OK;
-    StageArgs2 a{*st, *sc, nullptr, nullptr, nullptr, r_out, dt, stage, nullptr};
-    const int64_t blocks = (st->n * st->dim + 255) / 256;
-    hipLaunchKernelGGL(stage_point_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, a);
-    return sc_check_launch("sc_stage_point");
+    return sc_stage_point_range(st, sc, dt, stage, r_out, 0, st->n, (hipStream_t)stream);
 }
 
 extern "C" int sc_stage_consume(const sc_state *st, const sc_dense_scratch *sc, const double *inv_mass, const double *V,
@@ -799,9 +822,7 @@ extern "C" int sc_stage_consume(const sc_state *st, const sc_dense_scratch *sc, 
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_stage_consume: null argument");
     if (stage < 0 || stage > 3) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_stage_consume: stage %d", stage);
     if (st->n <= 0) return SC_OK;
-    StageArgs2 a{*st, *sc, inv_mass, V, grad, nullptr, dt, stage, energy_partials};
-    hipLaunchKernelGGL(stage_consume_kernel, dim3(sc_dense_grid(st->n)), dim3(256), 0, (hipStream_t)stream, a);
-    return sc_check_launch("sc_stage_consume");
+    return sc_stage_consume_range(st, sc, inv_mass, V, grad, dt, stage, energy_partials, 0, st->n, 0, (hipStream_t)stream);
 }
 
 int sc_launch_dense_any(const sc_state *st, const sc_hk_consts *hk, const double *inv_mass, const double *hess,

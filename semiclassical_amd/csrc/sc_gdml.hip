@@ -606,17 +606,24 @@ extern "C" int sc_gdml_row_len(int32_t n_atoms) {
     return -1;
 }
 
+int sc_gdml_large_check(const sc_gdml_model *g, const double *scratch, const char *who);                           // sc_gdml_large.hip
+int sc_gdml_large_eval(const sc_gdml_model *g, double *scratch, const double *r, int64_t n, double *energy, double *grad, double *hess,
+                       hipStream_t s);
+int sc_gdml_large_stage(const sc_gdml_model *g, double *scratch, const sc_state *st, const sc_dense_scratch *sc, double dt, int stage,
+                        double *energy_partials, hipStream_t s);
+
 namespace {
 
-int check_model(const sc_gdml_model *g, const char *who) {
+int check_model(const sc_gdml_model *g, const double *scratch, const char *who) {
     if (!g || !g->xs_train || !g->jx_alphas || !g->pair_k || !g->pair_l)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "%s: null model field", who);
-    if (g->n_atoms > 48) return sc_fail(SC_ERR_UNSUPPORTED, "%s: %d atoms (the instantiated kernels hold up to 48: four threads keep the "
-                                        "Jacobian coefficients of an atom's partners in registers, a workgroup the chunk's rows in LDS)", who, g->n_atoms);
     if (((uintptr_t)g->xs_train | (uintptr_t)g->jx_alphas) & 15)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "%s: xs_train / jx_alphas must be 16-byte aligned", who);
     if (g->n_desc != g->n_atoms * (g->n_atoms - 1) / 2)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "%s: descriptor size %d does not match %d atoms", who, g->n_desc, g->n_atoms);
+    // beyond 48 atoms: the multi-kernel route of sc_gdml_large.hip (four threads keep the Jacobian coefficients of an atom's
+    // partners in registers and a workgroup the chunk's rows in LDS only up to 48 atoms)
+    if (g->n_atoms > 48) return sc_gdml_large_check(g, scratch, who);
     if (gdml_lds_doubles(g->n_atoms, g->n_desc) * 8 > 160 * 1024)
         return sc_fail(SC_ERR_UNSUPPORTED, "%s: model (N=%d) needs more than 160 KiB of LDS", who, g->n_atoms);
     {
@@ -632,10 +639,16 @@ int check_model(const sc_gdml_model *g, const char *who) {
 
 extern "C" int sc_gdml_eval(const sc_gdml_model *g, const double *r, int64_t n, double *energy, double *grad,
                             double *hess, void *stream) {
-    int rc = check_model(g, "sc_gdml_eval");
+    return sc_gdml_eval_scratch(g, nullptr, r, n, energy, grad, hess, stream);
+}
+
+extern "C" int sc_gdml_eval_scratch(const sc_gdml_model *g, double *scratch, const double *r, int64_t n, double *energy,
+                                    double *grad, double *hess, void *stream) {
+    int rc = check_model(g, scratch, "sc_gdml_eval");
     if (rc) return rc;
     if (!r || !energy || !grad || !hess) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_gdml_eval: null argument");
     if (n <= 0) return SC_OK;
+    if (g->n_atoms > 48) return sc_gdml_large_eval(g, scratch, r, n, energy, grad, hess, (hipStream_t)stream);
     const size_t lds = gdml_lds_doubles(g->n_atoms, g->n_desc) * 8;
     EvalArgs a{*g, r, n, energy, grad, hess};
     const int grid = (int)(n < 1024 ? n : 1024);
@@ -668,7 +681,12 @@ extern "C" int sc_dense_grid(int64_t n) { return (int)(n < 512 ? (n > 0 ? n : 1)
 
 extern "C" int sc_gdml_stage(const sc_gdml_model *g, const sc_state *st, const sc_dense_scratch *sc, double dt,
                              int32_t stage, double *energy_partials, void *stream) {
-    int rc = check_model(g, "sc_gdml_stage");
+    return sc_gdml_stage_scratch(g, nullptr, st, sc, dt, stage, energy_partials, stream);
+}
+
+extern "C" int sc_gdml_stage_scratch(const sc_gdml_model *g, double *scratch, const sc_state *st, const sc_dense_scratch *sc,
+                                     double dt, int32_t stage, double *energy_partials, void *stream) {
+    int rc = check_model(g, scratch, "sc_gdml_stage");
     if (rc) return rc;
     if (!st || !sc || !sc->hess || !sc->kprev || !sc->ksum || !sc->ssum)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_gdml_stage: null argument");
@@ -676,6 +694,7 @@ extern "C" int sc_gdml_stage(const sc_gdml_model *g, const sc_state *st, const s
     if (stage < 0 || stage > 3) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_gdml_stage: stage %d", stage);
     if (st->dim > 512) return sc_fail(SC_ERR_UNSUPPORTED, "sc_gdml_stage: D=%d > 512", st->dim);
     if (st->n <= 0) return SC_OK;
+    if (g->n_atoms > 48) return sc_gdml_large_stage(g, scratch, st, sc, dt, stage, energy_partials, (hipStream_t)stream);
     const size_t lds = gdml_lds_doubles(g->n_atoms, g->n_desc) * 8;
     StageArgs a{*g, *st, *sc, dt, stage, energy_partials};
 #define SC_GDML_STAGE(TH_, HN_, CH_, MT_, NB_)                                                                                      \

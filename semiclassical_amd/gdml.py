@@ -33,7 +33,9 @@ class MolecularGDMLPotential(_MolecularPotentialBase):
         self._jx_alphas = expand(torch.tensor(np.asarray(model['R_d_desc_alpha'], dtype=np.float64)))
         self._sig, self._c, self._std = int(model['sig']), float(model['c']), float(model.get('std', 1))
         self._n_atoms = int(n_atoms)
-        assert lib.sc_gdml_row_len(self._n_atoms) > 0, "the sGDML kernels hold molecules of up to 48 atoms"
+        if self._n_atoms > lib.sc_gdml_max_atoms():
+            raise ValueError(f"sGDML model of {self._n_atoms} atoms: the sGDML kernels hold molecules of at most "
+                             f"{lib.sc_gdml_max_atoms()} atoms")
         k, l = torch.tril_indices(n_atoms, n_atoms, offset=-1)
         self._pair_k, self._pair_l = k.to(torch.int32).contiguous(), l.to(torch.int32).contiguous()
         self._default_device = device
@@ -55,6 +57,10 @@ class MolecularGDMLPotential(_MolecularPotentialBase):
             self._model_cache[key] = (m, bufs)
         return self._model_cache[key][0]
 
+    def scratch_bytes(self):
+        """bytes of the scratch an evaluation needs (0 up to 48 atoms); one buffer per stream"""
+        return lib.sc_gdml_scratch_bytes(self._n_atoms, self._xs_train.shape[0])
+
     def harmonic_approximation(self, r):
         """V (n,), grad (D, n), hess (D, D, n) for positions r (D, n) -- evaluated on the GPU"""
         dev = r.device if r.is_cuda else torch.device(self._default_device)
@@ -63,9 +69,12 @@ class MolecularGDMLPotential(_MolecularPotentialBase):
         e = torch.empty(n, dtype=torch.float64, device=dev)
         g = torch.empty((n, D), dtype=torch.float64, device=dev)
         h = torch.empty((n, D, D), dtype=torch.float64, device=dev)
+        need = self.scratch_bytes()
+        # the scratch belongs to this call, not to the cached model block: two streams never share it
+        scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev) if need > 0 else None
         with torch.cuda.device(dev):
-            check(lib.sc_gdml_eval(self._gdml_model(dev), ptr(rt), n, ptr(e), ptr(g), ptr(h),
-                                   torch.cuda.current_stream(dev).cuda_stream))
+            check(lib.sc_gdml_eval_scratch(self._gdml_model(dev), ptr(scratch), ptr(rt), n, ptr(e), ptr(g), ptr(h),
+                                           torch.cuda.current_stream(dev).cuda_stream))
         out = (e, g.t(), h.permute(1, 2, 0))
         return tuple(x.to(r.device) for x in out)
 

@@ -385,20 +385,29 @@ class HermanKlukPropagator(object):
 
     def _launch_dense_step(self, potential, dt, s):
         """unfused RK4 step for a dense, position-dependent Hessian: four stage kernels + the monodromy kernel"""
-        self._dense_scratch()
+        self._dense_scratch(potential)
         with torch.cuda.device(self.device):
             model = potential._gdml_model(self.device)
         for stage in range(4):
             with self._timed("gdml_stage"):
-                check(lib.sc_gdml_stage(model, self._state, self._dense, dt, stage, ptr(self._epart), s))
+                check(lib.sc_gdml_stage_scratch(model, ptr(self._gdml_scratch), self._state, self._dense, dt, stage,
+                                                ptr(self._epart), s))
         with self._timed("dense_mono_step"):
             check(lib.sc_dense_mono_step(self._state, self._hk, model.inv_mass, ptr(self._dense_bufs[0]),
                                          self._mono_sums_ptr(), dt, 0, s))
         return self._gdense
 
-    def _dense_scratch(self):
-        """scratch of the unfused dense path: stage Hessians, slopes of the previous stage, weighted slope sums"""
+    def _dense_scratch(self, gdml=None):
+        """scratch of the unfused dense path: stage Hessians, slopes of the previous stage, weighted slope sums; with an
+        sGDML potential ``gdml`` also the scratch of sc_gdml_stage (beyond 48 atoms, ``self._gdml_scratch``)"""
         n, d = self.ntraj, self.dim
+        if gdml is not None:
+            need = gdml.scratch_bytes()
+            have = getattr(self, "_gdml_scratch", None)
+            if need > 0 and (have is None or have.numel() * 8 < need):
+                self._gdml_scratch = torch.empty((need + 7) // 8, dtype=F64, device=self.device)
+            elif need == 0 and have is None:
+                self._gdml_scratch = None
         if getattr(self, "_dense", None) is None:
             dev = self.device
             bufs = [torch.empty((n, 4, d, d), dtype=F64, device=dev), torch.zeros((n, 2 * d), dtype=F64, device=dev),
