@@ -74,6 +74,7 @@ class sc_dense_scratch(C.Structure):
 
 
 SC_POT_MORSE, SC_POT_HARMONIC_SEP, SC_POT_EPS_MORSE, SC_POT_HARMONIC_DENSE = 1, 2, 3, 4
+SEPARABLE_KINDS = (SC_POT_MORSE, SC_POT_HARMONIC_SEP, SC_POT_EPS_MORSE)      # sc_pot_is_separable (csrc/sc_common.h)
 SC_MONO_ROWMAJOR, SC_MONO_TILED16 = 0, 1
 
 # every symbol include/semiclassical_hip.h declares: name -> (restype, argtypes)

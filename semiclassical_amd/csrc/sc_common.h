@@ -143,6 +143,11 @@ struct StepArgs {
     int npart;          // entries of epart the energy guard adds up (sc_step_grid); kernels with fewer workgroups clear the rest
 };
 
+// diagonal Hessian: every mode is its own one-dimensional problem (sep_eval below)
+__host__ __device__ __forceinline__ bool sc_pot_is_separable(int kind) {
+    return kind == SC_POT_MORSE || kind == SC_POT_HARMONIC_SEP || kind == SC_POT_EPS_MORSE;
+}
+
 // V, dV/dx, d2V/dx2 of one mode of a separable potential
 __device__ __forceinline__ void sep_eval(int kind, double c0, double c1, double x, double &v, double &g, double &h) {
     if (kind == SC_POT_MORSE) {                    // c0 = a, c1 = De
@@ -177,6 +182,64 @@ __device__ __forceinline__ void rk4_pair(double &u, double &v, double im, double
     double k4u = v4 * im, k4v = -h4 * u4;
     u = u + h6 * (k1u + 2.0 * k2u + 2.0 * k3u + k4u);
     v = v + h6 * (k1v + 2.0 * k2v + 2.0 * k3v + k4v);
+}
+
+// The physics of one HK step for a separable potential with diagonal width matrices, defined ONCE: every route calls these,
+// so the routes agree bit for bit in them by construction.  Do not reorder an operation here: results would change everywhere.
+//
+// RK4 of one mode (q_a, p_a) with the reference's stage formula (propagators.py:86-119, 313-383): q and p advance in place;
+// te[0..3] = T - V at the four stage points, te[4] = T + V at the k4 point (:380, quirk Q2), h1..h4 = d2V/dx2 at the stage points
+__device__ __forceinline__ void sep_mode_rk4(int kind, double c0, double c1, double im, double dt, double &q, double &p,
+                                             double (&te)[5], double &h1, double &h2, double &h3, double &h4) {
+    const double hh = 0.5 * dt, h6 = dt / 6.0;
+    double v, g;
+    sep_eval(kind, c0, c1, q, v, g, h1);
+    const double kq1 = p * im, kp1 = -g;
+    te[0] = 0.5 * p * p * im - v;
+    const double q2 = q + hh * kq1, p2 = p + hh * kp1;
+    sep_eval(kind, c0, c1, q2, v, g, h2);
+    const double kq2 = p2 * im, kp2 = -g;
+    te[1] = 0.5 * p2 * p2 * im - v;
+    const double q3 = q + hh * kq2, p3 = p + hh * kp2;
+    sep_eval(kind, c0, c1, q3, v, g, h3);
+    const double kq3 = p3 * im, kp3 = -g;
+    te[2] = 0.5 * p3 * p3 * im - v;
+    const double q4 = q + dt * kq3, p4 = p + dt * kp3;
+    sep_eval(kind, c0, c1, q4, v, g, h4);
+    const double kq4 = p4 * im, kp4 = -g;
+    te[3] = 0.5 * p4 * p4 * im - v;
+    te[4] = 0.5 * p4 * p4 * im + v;
+    q = q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4);
+    p = p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4);
+}
+
+// 2 x 2 RK4 propagator P_a = [[p11, p12], [p21, p22]] of row a of the monodromy blocks: the unit vectors through rk4_pair
+__device__ __forceinline__ void sep_row_propagator(double im, double h1, double h2, double h3, double h4, double dt,
+                                                   double &p11, double &p12, double &p21, double &p22) {
+    p11 = 1.0; p21 = 0.0; p12 = 0.0; p22 = 1.0;
+    rk4_pair(p11, p21, im, h1, h2, h3, h4, dt);       // (u, v) = (1, 0) -> first column of P_a
+    rk4_pair(p12, p22, im, h1, h2, h3, h4, dt);       // (0, 1) -> second column
+}
+
+// (Mqq, Mpq)' = P_a (Mqq, Mpq), (Mqp, Mpp)' = P_a (Mqp, Mpp) for one element of row a
+__device__ __forceinline__ void sep_propagate_row(double p11, double p12, double p21, double p22,
+                                                  double &mqq, double &mqp, double &mpq, double &mpp) {
+    const double nqq = fma(p12, mpq, p11 * mqq), npq = fma(p22, mpq, p21 * mqq);
+    const double nqp = fma(p12, mpp, p11 * mqp), npp = fma(p22, mpp, p21 * mqp);
+    mqq = nqq; mpq = npq; mqp = nqp; mpp = npp;
+}
+
+// element (a, b) of the HK prefactor matrix for diagonal width matrices (propagators.py:969-986):
+//   1/2 (st_a/si_b Mqq + si_b/st_a Mpp) + i/2 (-hbar st_a si_b Mqp + Mpq / (hbar st_a si_b)),  ista = 1/st_a, isib = 1/si_b
+__device__ __forceinline__ cplx prefactor_element_diag(double sta, double ista, double sib, double isib,
+                                                       double mqq, double mqp, double mpq, double mpp) {
+    return c_make(0.5 * (sta * isib * mqq + ista * sib * mpp),
+                  0.5 * (-SC_HBAR * sta * sib * mqp + (1.0 / SC_HBAR) * ista * isib * mpq));
+}
+
+// branch rule of the sqrt tracker (propagators.py:1045-1047): c2 went from `prev` to `det` across the negative real axis
+__device__ __forceinline__ bool crossed_branch_cut(cplx prev, cplx det) {
+    return prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0;
 }
 
 #define SC_SEP16_MAX_D 12    // D <= 12: hk_step_sep16_kernel (four trajectories per wavefront); 13 .. 16: hk_step_w16_kernel

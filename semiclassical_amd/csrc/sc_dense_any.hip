@@ -91,6 +91,7 @@ __global__ __launch_bounds__(256) void prefactor_any_kernel(AnyArgs A) {
             for (int e = tid; e < DD; e += 256) {
                 const int a = e / D, b = e - a * D;
                 const double sta = A.hk.st[a], sib = A.hk.si[b];
+                // divisions, not prefactor_element_diag's reciprocals: the two round differently and results are pinned to this form
                 mat[e] = c_make(0.5 * (sta / sib * M[e] + sib / sta * M[3 * DD + e]),
                                 0.5 * (-SC_HBAR * sta * sib * M[DD + e] + M[2 * DD + e] / (SC_HBAR * sta * sib)));
             }
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(256) void prefactor_any_kernel(AnyArgs A) {
             cplx *c2 = (cplx *)A.st.c2;
             if (A.mode == 0) {
                 const cplx prev = c2[tr];
-                if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
             } else {
                 A.st.sgn[tr] = 1.0;
             }

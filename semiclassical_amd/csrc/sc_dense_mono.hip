@@ -608,6 +608,7 @@ __global__ __launch_bounds__(256) void dense_prefactor_kernel(MonoArgs A) {
             for (int e = tid; e < DD; e += nth) {
                 const int a = e / D, b = e - a * D;
                 const double sta = A.hk.st[a], sib = A.hk.si[b];
+                // divisions, not prefactor_element_diag's reciprocals: the two round differently and results are pinned to this form
                 mat[e] = c_make(0.5 * (sta / sib * M[e] + sib / sta * M[3 * DD + e]),
                                 0.5 * (-SC_HBAR * sta * sib * M[DD + e] + M[2 * DD + e] / (SC_HBAR * sta * sib)));
             }
@@ -620,7 +621,7 @@ __global__ __launch_bounds__(256) void dense_prefactor_kernel(MonoArgs A) {
             cplx *c2 = (cplx *)A.st.c2;
             if (A.mode == 0) {
                 const cplx prev = c2[tr];
-                if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
             } else {
                 A.st.sgn[tr] = 1.0;
             }
@@ -686,8 +687,7 @@ __global__ __launch_bounds__(256, NR > 4 ? 2 : 4) void dense_prefactor_reg_kerne
             for (int rb = 0; rb < NR; ++rb) {
                 const int b = 16 * rb + tjl;
                 const double sb = scl[2 * RW + b], isb = scl[3 * RW + b];
-                m[ra][rb] = c_make(0.5 * (sa * isb * v[0][rb] + isa * sb * v[3][rb]),
-                                   0.5 * (-SC_HBAR * sa * sb * v[1][rb] + (1.0 / SC_HBAR) * isa * isb * v[2][rb]));
+                m[ra][rb] = prefactor_element_diag(sa, isa, sb, isb, v[0][rb], v[1][rb], v[2][rb], v[3][rb]);
                 // the element must exist before the next slot's loads are issued: otherwise every raw value of the
                 // trajectory (4 NR^2 doubles) is loaded first and spilled
                 __asm__ volatile("" : "+v"(m[ra][rb].x), "+v"(m[ra][rb].y) : : "memory");
@@ -705,7 +705,7 @@ __global__ __launch_bounds__(256, NR > 4 ? 2 : 4) void dense_prefactor_reg_kerne
                 cplx *c2 = (cplx *)A.st.c2;
                 if (A.mode == 0) {
                     const cplx prev = c2[tr];
-                    if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                    if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
                 } else {
                     A.st.sgn[tr] = 1.0;
                 }

@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
                 gauss_jordan_rows<N, 1>(mat, dummy, r >= N, r, rowbase, myk, src, det2);
                 if (weak) det = det2;
             }
-            if (c2.x < 0.0 && det.x < 0.0 && c2.y * det.y < 0.0) sgn = -sgn;       // branch tracker (propagators.py:1045-1047)
+            if (crossed_branch_cut(c2, det)) sgn = -sgn;       // branch tracker (propagators.py:1045-1047)
             c2 = det;
             // ---- this wavefront's share of step k: one writer per slot ----
             if constexpr (MOM) run_moments_share<MOM>(R, v5, head, k, slot, lane);

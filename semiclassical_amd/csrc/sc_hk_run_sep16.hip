@@ -12,9 +12,10 @@
 // Per step and trajectory, in this order (= the order of the caller loop):
 //   terms of C_auto and k_ic from the CURRENT state       hk_correlate_kernel's arithmetic, sums over the modes by the same
 //                                                         rotate-and-add tree (propagators.py:784-843, 845-911)
-//   RK4 of (q_a, p_a), action, <T+V> at the k4 stage,     hk_step_sep16_kernel's arithmetic (propagators.py:86-119, 313-383)
-//   row propagators P_a applied to the monodromy rows
-//   prefactor row, determinant, branch tracker            fixed pivot order; a weak pivot (never for the diagonal blocks a
+//   RK4 of (q_a, p_a), action, <T+V> at the k4 stage,     sep_mode_rk4, sep_row_propagator, sep_propagate_row (sc_common.h: the
+//   row propagators P_a applied to the monodromy rows     functions hk_step_sep16_kernel calls; propagators.py:86-119, 313-383)
+//   prefactor row, determinant, branch tracker            prefactor_element_diag, crossed_branch_cut (sc_common.h);
+//                                                         fixed pivot order; a weak pivot (never for the diagonal blocks a
 //                                                         separable potential produces from M(0) = 1) repeats the
 //                                                         elimination with the pivot searched among the lanes
 //                                                         (propagators.py:969-1052)
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
     const StepArgs &A = R.step;
     const int D = A.st.dim, DD = D * D, tid = threadIdx.x, lane = tid & 63, r = tid & 15, grp = tid >> 4, wave = tid >> 6;
     const int rowbase = tid & 48;
-    const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
+    const double dt = A.dt, h6 = dt / 6.0;
     const bool mine = r < D;
     const double sta = mine ? A.hk.st[r] : 1.0, ista = 1.0 / sta;
     const double im = mine ? A.pot.inv_mass[r] : 0.0, c0 = mine ? A.pot.par0[r] : 0.0;
@@ -94,27 +95,9 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
             // ---- RK4 of (q_a, p_a) with the reference's stage formula, action, <T+V> and the row propagator P_a ----
             double red5[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, p11 = 1.0, p12 = 0.0, p21 = 0.0, p22 = 1.0;
             if (mine) {
-                double v, g, h1, h2, h3, h4;
-                sep_eval(KIND, c0, c1, q, v, g, h1);
-                const double kq1 = p * im, kp1 = -g;
-                red5[0] = 0.5 * p * p * im - v;
-                const double q2 = q + hh * kq1, p2 = p + hh * kp1;
-                sep_eval(KIND, c0, c1, q2, v, g, h2);
-                const double kq2 = p2 * im, kp2 = -g;
-                red5[1] = 0.5 * p2 * p2 * im - v;
-                const double q3 = q + hh * kq2, p3 = p + hh * kp2;
-                sep_eval(KIND, c0, c1, q3, v, g, h3);
-                const double kq3 = p3 * im, kp3 = -g;
-                red5[2] = 0.5 * p3 * p3 * im - v;
-                const double q4 = q + dt * kq3, p4 = p + dt * kp3;
-                sep_eval(KIND, c0, c1, q4, v, g, h4);
-                const double kq4 = p4 * im, kp4 = -g;
-                red5[3] = 0.5 * p4 * p4 * im - v;
-                red5[4] = 0.5 * p4 * p4 * im + v;
-                q = q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4);
-                p = p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4);
-                rk4_pair(p11, p21, im, h1, h2, h3, h4, dt);       // (u, v) = (1, 0) -> first column of P_a
-                rk4_pair(p12, p22, im, h1, h2, h3, h4, dt);       // (0, 1) -> second column
+                double h1, h2, h3, h4;
+                sep_mode_rk4(KIND, c0, c1, im, dt, q, p, red5, h1, h2, h3, h4);
+                sep_row_propagator(im, h1, h2, h3, h4, dt, p11, p12, p21, p22);
             }
             {
                 double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -130,12 +113,12 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
             cplx mat[DP], keep[DP];
 #pragma unroll
             for (int b = 0; b < DP; ++b) {
+                // sep_propagate_row written out: with the call hipcc spills 250 bytes per lane more at DP = 12
                 const double nqq = fma(p12, mpq[b], p11 * mqq[b]), npq = fma(p22, mpq[b], p21 * mqq[b]);
                 const double nqp = fma(p12, mpp[b], p11 * mqp[b]), npp = fma(p22, mpp[b], p21 * mqp[b]);
                 mqq[b] = nqq; mpq[b] = npq; mqp[b] = nqp; mpp[b] = npp;
                 const double sib = b < D ? ksi[b] : 1.0, isib = 1.0 / sib;
-                mat[b] = (mine && b < D) ? c_make(0.5 * (sta * isib * nqq + ista * sib * npp),
-                                                  0.5 * (-SC_HBAR * sta * sib * nqp + (1.0 / SC_HBAR) * ista * isib * npq))
+                mat[b] = (mine && b < D) ? prefactor_element_diag(sta, ista, sib, isib, mqq[b], mqp[b], mpq[b], mpp[b])
                                          : c_make(r == b ? 1.0 : 0.0, 0.0);
                 keep[b] = mat[b];
             }
@@ -149,7 +132,7 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
                 gauss_jordan_rows<DP, 1>(keep, dummy, r >= DP, r, rowbase, myk, src, det2);
                 if (weak) det = det2;
             }
-            if (c2.x < 0.0 && det.x < 0.0 && c2.y * det.y < 0.0) sgn = -sgn;       // branch tracker (propagators.py:1045-1047)
+            if (crossed_branch_cut(c2, det)) sgn = -sgn;       // branch tracker (propagators.py:1045-1047)
             c2 = det;
             // ---- this wavefront's share of step k: one writer per slot ----
             if constexpr (MOM) run_moments_share<MOM>(R, v5, head, k, slot, lane);
@@ -267,7 +250,7 @@ static bool run_lin_shape(const sc_potential *pot, const sc_hk_consts *hk, bool 
 
 extern "C" int sc_hk_run_supported(const sc_potential *pot, const sc_hk_consts *hk, const sc_overlap_consts *ovl) {
     if (!pot || !hk || !ovl) return 0;
-    const bool sep = pot->kind == SC_POT_MORSE || pot->kind == SC_POT_HARMONIC_SEP || pot->kind == SC_POT_EPS_MORSE;
+    const bool sep = sc_pot_is_separable(pot->kind);
     if (sep && hk->diag && ovl->diag && pot->dim <= SC_SEP16_MAX_D) return 1;
     return run_lin_shape(pot, hk) ? 1 : 0;
 }

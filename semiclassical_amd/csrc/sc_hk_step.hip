@@ -75,25 +75,10 @@ __global__ __launch_bounds__(256) void hk_step_kernel(StepArgs A) {
             if (!DENSE) {
                 if (own) {
                     const double c0 = A.pot.par0[tid], c1 = A.pot.par1 ? A.pot.par1[tid] : 0.0;
-                    double v, g, h;
-                    sep_eval(A.pot.kind, c0, c1, q, v, g, h);
-                    const double kq1 = p * im, kp1 = -g; hst[tid] = h;
-                    red5[0] = 0.5 * p * p * im - v;
-                    const double q2 = q + hh * kq1, p2 = p + hh * kp1;
-                    sep_eval(A.pot.kind, c0, c1, q2, v, g, h);
-                    const double kq2 = p2 * im, kp2 = -g; hst[D + tid] = h;
-                    red5[1] = 0.5 * p2 * p2 * im - v;
-                    const double q3 = q + hh * kq2, p3 = p + hh * kp2;
-                    sep_eval(A.pot.kind, c0, c1, q3, v, g, h);
-                    const double kq3 = p3 * im, kp3 = -g; hst[2 * D + tid] = h;
-                    red5[2] = 0.5 * p3 * p3 * im - v;
-                    const double q4 = q + dt * kq3, p4 = p + dt * kp3;
-                    sep_eval(A.pot.kind, c0, c1, q4, v, g, h);
-                    const double kq4 = p4 * im, kp4 = -g; hst[3 * D + tid] = h;
-                    red5[3] = 0.5 * p4 * p4 * im - v;
-                    red5[4] = 0.5 * p4 * p4 * im + v;
-                    qn = q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4);
-                    pn = p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4);
+                    double h1, h2, h3, h4;
+                    qn = q; pn = p;
+                    sep_mode_rk4(A.pot.kind, c0, c1, im, dt, qn, pn, red5, h1, h2, h3, h4);
+                    hst[tid] = h1; hst[D + tid] = h2; hst[2 * D + tid] = h3; hst[3 * D + tid] = h4;
                 }
             } else {
                 // V = E0 + g.dr + 1/2 dr.H.dr - origin ; grad = g + H.dr      potentials.py:583-590
@@ -154,8 +139,7 @@ __global__ __launch_bounds__(256) void hk_step_kernel(StepArgs A) {
                 }
                 if (diag) {
                     const double sta = vec[a], ista = vec[D + a], sib = vec[2 * D + b], isib = vec[3 * D + b];
-                    mat[e] = c_make(0.5 * (sta * isib * mqq + ista * sib * mpp),
-                                    0.5 * (-SC_HBAR * sta * sib * mqp + (1.0 / SC_HBAR) * ista * isib * mpq));
+                    mat[e] = prefactor_element_diag(sta, ista, sib, isib, mqq, mqp, mpq, mpp);
                 }
             }
             __syncthreads();
@@ -203,9 +187,7 @@ __global__ __launch_bounds__(256) void hk_step_kernel(StepArgs A) {
                 for (int e = tid; e < DD; e += nth) {
                     const int a = e / D, b = e - a * D;
                     const double sta = vec[a], ista = vec[D + a], sib = vec[2 * D + b], isib = vec[3 * D + b];
-                    mat[e] = c_make(0.5 * (sta * isib * Mq[a * W + b] + ista * sib * Mp[a * W + D + b]),
-                                    0.5 * (-SC_HBAR * sta * sib * Mq[a * W + D + b]
-                                           + (1.0 / SC_HBAR) * ista * isib * Mp[a * W + b]));
+                    mat[e] = prefactor_element_diag(sta, ista, sib, isib, Mq[a * W + b], Mq[a * W + D + b], Mp[a * W + b], Mp[a * W + D + b]);
                 }
                 __syncthreads();
             } else {
@@ -219,7 +201,7 @@ __global__ __launch_bounds__(256) void hk_step_kernel(StepArgs A) {
             cplx *c2 = (cplx *)A.st.c2;
             if (!init_track) {
                 const cplx prev = c2[tr];
-                if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
             } else {
                 A.st.sgn[tr] = 1.0;
             }
@@ -255,7 +237,7 @@ extern "C" int sc_hk_step(const sc_potential *pot, const sc_state *st, const sc_
     if (hk->diag && hk->dprime != D) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_step: diag prefactor needs d' == D");
     if (st->n <= 0) return SC_OK;
     const bool dense = pot->kind == SC_POT_HARMONIC_DENSE;
-    if (!dense && pot->kind != SC_POT_MORSE && pot->kind != SC_POT_HARMONIC_SEP && pot->kind != SC_POT_EPS_MORSE)
+    if (!dense && !sc_pot_is_separable(pot->kind))
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_step: unknown potential kind %d", pot->kind);
     bool fast = !dense && hk->diag && st->work;
     // The register kernels for D <= 12 and 16 < D <= 64 eliminate in a fixed (block-)pivot order and hand weak pivots to
@@ -337,8 +319,7 @@ extern "C" int sc_hk_step(const sc_potential *pot, const sc_state *st, const sc_
 // ---- two time steps per visit (include/semiclassical_hip.h: sc_hk_step_multi) ----
 extern "C" int sc_hk_step_multi_supported(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk) {
     if (!pot || !st || !hk) return 0;
-    const bool sep = pot->kind == SC_POT_MORSE || pot->kind == SC_POT_HARMONIC_SEP || pot->kind == SC_POT_EPS_MORSE;
-    return sep && hk->diag && hk->dprime == st->dim && pot->dim == st->dim && hk->dim == st->dim && st->dim > 16 && st->dim <= 64 &&
+    return sc_pot_is_separable(pot->kind) && hk->diag && hk->dprime == st->dim && pot->dim == st->dim && hk->dim == st->dim && st->dim > 16 && st->dim <= 64 &&
            st->mono_layout == SC_MONO_TILED16 && st->work && st->flags ? 1 : 0;
 }
 

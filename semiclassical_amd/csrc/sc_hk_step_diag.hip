@@ -26,7 +26,7 @@ __device__ __forceinline__ cplx wave_prod(cplx z) {
 template <bool STEP>
 __global__ __launch_bounds__(256) void hk_diag_step_kernel(StepArgs A, double *mdiag) {
     const int D = A.st.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
+    const double dt = A.dt, h6 = dt / 6.0;
     __shared__ double wsum[4];
     double esum = 0.0;
     for (int64_t tr = (int64_t)blockIdx.x * 4 + wave; tr < A.st.n; tr += (int64_t)gridDim.x * 4) {
@@ -39,38 +39,20 @@ __global__ __launch_bounds__(256) void hk_diag_step_kernel(StepArgs A, double *m
             if (a < D) {
                 double mqq = md[a], mqp = md[D + a], mpq = md[2 * D + a], mpp = md[3 * D + a];
                 if (STEP) {
-                    const double q = qp[a], p = qp[D + a], im = A.pot.inv_mass[a];
+                    const double im = A.pot.inv_mass[a];
                     const double c0 = A.pot.par0[a], c1 = A.pot.par1 ? A.pot.par1[a] : 0.0;
-                    double v, g, h1, h2, h3, h4;
-                    sep_eval(A.pot.kind, c0, c1, q, v, g, h1);
-                    const double kq1 = p * im, kp1 = -g;
-                    red5[0] += 0.5 * p * p * im - v;
-                    const double q2 = q + hh * kq1, p2 = p + hh * kp1;
-                    sep_eval(A.pot.kind, c0, c1, q2, v, g, h2);
-                    const double kq2 = p2 * im, kp2 = -g;
-                    red5[1] += 0.5 * p2 * p2 * im - v;
-                    const double q3 = q + hh * kq2, p3 = p + hh * kp2;
-                    sep_eval(A.pot.kind, c0, c1, q3, v, g, h3);
-                    const double kq3 = p3 * im, kp3 = -g;
-                    red5[2] += 0.5 * p3 * p3 * im - v;
-                    const double q4 = q + dt * kq3, p4 = p + dt * kp3;
-                    sep_eval(A.pot.kind, c0, c1, q4, v, g, h4);
-                    const double kq4 = p4 * im, kp4 = -g;
-                    red5[3] += 0.5 * p4 * p4 * im - v;
-                    red5[4] += 0.5 * p4 * p4 * im + v;
-                    qp[a] = q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4);
-                    qp[D + a] = p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4);
-                    double u1 = 1.0, v1 = 0.0, u2 = 0.0, v2 = 1.0;       // P_a = [[u1, u2], [v1, v2]]
-                    rk4_pair(u1, v1, im, h1, h2, h3, h4, dt);
-                    rk4_pair(u2, v2, im, h1, h2, h3, h4, dt);
-                    const double nqq = fma(u2, mpq, u1 * mqq), npq = fma(v2, mpq, v1 * mqq);
-                    const double nqp = fma(u2, mpp, u1 * mqp), npp = fma(v2, mpp, v1 * mqp);
-                    mqq = nqq; mpq = npq; mqp = nqp; mpp = npp;
+                    double q = qp[a], p = qp[D + a], te[5], h1, h2, h3, h4, p11, p12, p21, p22;
+                    sep_mode_rk4(A.pot.kind, c0, c1, im, dt, q, p, te, h1, h2, h3, h4);
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) red5[i] += te[i];
+                    qp[a] = q;
+                    qp[D + a] = p;
+                    sep_row_propagator(im, h1, h2, h3, h4, dt, p11, p12, p21, p22);
+                    sep_propagate_row(p11, p12, p21, p22, mqq, mqp, mpq, mpp);
                     md[a] = mqq; md[D + a] = mqp; md[2 * D + a] = mpq; md[3 * D + a] = mpp;
                 }
                 const double st = A.hk.st[a], si = A.hk.si[a], ist = 1.0 / st, isi = 1.0 / si;
-                mat = c_make(0.5 * (st * isi * mqq + ist * si * mpp),
-                             0.5 * (-SC_HBAR * st * si * mqp + (1.0 / SC_HBAR) * ist * isi * mpq));
+                mat = prefactor_element_diag(st, ist, si, isi, mqq, mqp, mpq, mpp);
             }
             det = c_mul(det, mat);
         }
@@ -85,7 +67,7 @@ __global__ __launch_bounds__(256) void hk_diag_step_kernel(StepArgs A, double *m
                 A.st.act[tr] += h6 * (red5[0] + 2.0 * red5[1] + 2.0 * red5[2] + red5[3]);
                 esum += red5[4];
                 const cplx prev = c2[tr];
-                if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
             } else {
                 A.st.sgn[tr] = 1.0;
             }
@@ -107,7 +89,7 @@ extern "C" int sc_hk_step_diag(const sc_potential *pot, const sc_state *st, cons
     if (D < 1) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_diag: D=%d", D);
     if (!hk->diag || hk->dprime != D)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_step_diag: needs diagonal width matrices without zero modes");
-    if (pot->kind != SC_POT_MORSE && pot->kind != SC_POT_HARMONIC_SEP && pot->kind != SC_POT_EPS_MORSE)
+    if (!sc_pot_is_separable(pot->kind))
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_step_diag: potential kind %d is not separable", pot->kind);
     if (st->n <= 0) return SC_OK;
     StepArgs a{*pot, *st, *hk, dt, mode, energy_partials, sc_step_grid(st->n, st->dim)};

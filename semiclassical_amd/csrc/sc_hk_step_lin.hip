@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
         int weak = SC_LIN_FORCE_FIXUP;
         const cplx det = det_rows_fixed_order<N>(mat, r, weak);
         double newsgn = 0.0;
-        if (do_step) { if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) newsgn = -sgn_old; }
+        if (do_step) { if (crossed_branch_cut(prev, det)) newsgn = -sgn_old; }
         else newsgn = 1.0;
         if (active) { pend_tr = tr; pend_det = det; pend_weak = weak; pend_sgn = newsgn; }
         if constexpr (!FETCHED) commit();

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void hk_step_modal_kernel(ModalArgs MA) {
             cplx *c2 = (cplx *)A.st.c2;
             if (!init_track) {
                 const cplx prev = c2[tr];
-                if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
             } else {
                 A.st.sgn[tr] = 1.0;
             }

@@ -281,9 +281,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
                 const int vofs = voffset(ra, rb), base = tile_base(ra, rb), plane = plane_bytes(ra, rb);
                 double mqq = raw[ra & 1][0][rb], mqp = raw[ra & 1][1][rb], mpq = raw[ra & 1][2][rb], mpp = raw[ra & 1][3][rb];
                 if (do_step) {
-                    const double nqq = fma(p12, mpq, p11 * mqq), npq = fma(p22, mpq, p21 * mqq);
-                    const double nqp = fma(p12, mpp, p11 * mqp), npp = fma(p22, mpp, p21 * mqp);
-                    mqq = nqq; mpq = npq; mqp = nqp; mpp = npp;
+                    sep_propagate_row(p11, p12, p21, p22, mqq, mqp, mpq, mpp);
                     const double out[4] = {mqq, mqp, mpq, mpp};
                     if constexpr (TILED) {
 #pragma unroll
@@ -314,8 +312,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
                 const int bl = (16 * rb + tjl) & 63;
                 const double sib = scl[128 + bl], isib = scl[192 + bl];
                 // elements outside the matrix were loaded as zeros: their mat entries are zeros
-                m[ra][rb] = c_make(0.5 * (sta * isib * mqq + ista * sib * mpp),
-                                   0.5 * (-SC_HBAR * sta * sib * mqp + (1.0 / SC_HBAR) * ista * isib * mpq));
+                m[ra][rb] = prefactor_element_diag(sta, ista, sib, isib, mqq, mqp, mpq, mpp);
                 // the element must exist HERE: hipcc otherwise sinks its computation to the first use in the elimination
                 // and carries (spills) the four raw values and the scalings instead
                 __asm__ volatile("" : "+v"(m[ra][rb].x), "+v"(m[ra][rb].y));
@@ -419,7 +416,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
             if (do_step) {
                 const cplx prev = *c2_in;
                 const double sg = *sg_in;
-                const bool flip = prev.x < 0.0 && c2new.x < 0.0 && prev.y * c2new.y < 0.0;
+                const bool flip = crossed_branch_cut(prev, c2new);
                 if (KS > 1) *sg_out = flip ? -sg : sg;
                 else if (flip) *sg_out = -sg;
             } else {
@@ -449,7 +446,7 @@ namespace {
 // monodromy rows (unit vectors pushed through the same stage formula) -> st.work[tr][4][D].
 __global__ __launch_bounds__(256) void hk_modes_kernel(StepArgs A) {
     const int D = A.st.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
+    const double dt = A.dt, h6 = dt / 6.0;
     __shared__ double wsum[4];
     double esum = 0.0;
     for (int64_t tr = (int64_t)blockIdx.x * 4 + wave; tr < A.st.n; tr += (int64_t)gridDim.x * 4) {
@@ -457,31 +454,14 @@ __global__ __launch_bounds__(256) void hk_modes_kernel(StepArgs A) {
         double *pr = A.st.work + tr * 4 * (int64_t)D;
         double red5[5] = {0, 0, 0, 0, 0};
         if (lane < D) {
-            const double q = qp[lane], p = qp[D + lane], im = A.pot.inv_mass[lane];
+            const double im = A.pot.inv_mass[lane];
             const double c0 = A.pot.par0[lane], c1 = A.pot.par1 ? A.pot.par1[lane] : 0.0;
-            double v, g, h1, h2, h3, h4;
-            sep_eval(A.pot.kind, c0, c1, q, v, g, h1);
-            const double kq1 = p * im, kp1 = -g;
-            red5[0] = 0.5 * p * p * im - v;
-            const double q2 = q + hh * kq1, p2 = p + hh * kp1;
-            sep_eval(A.pot.kind, c0, c1, q2, v, g, h2);
-            const double kq2 = p2 * im, kp2 = -g;
-            red5[1] = 0.5 * p2 * p2 * im - v;
-            const double q3 = q + hh * kq2, p3 = p + hh * kp2;
-            sep_eval(A.pot.kind, c0, c1, q3, v, g, h3);
-            const double kq3 = p3 * im, kp3 = -g;
-            red5[2] = 0.5 * p3 * p3 * im - v;
-            const double q4 = q + dt * kq3, p4 = p + dt * kp3;
-            sep_eval(A.pot.kind, c0, c1, q4, v, g, h4);
-            const double kq4 = p4 * im, kp4 = -g;
-            red5[3] = 0.5 * p4 * p4 * im - v;
-            red5[4] = 0.5 * p4 * p4 * im + v;
-            qp[lane] = q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4);
-            qp[D + lane] = p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4);
-            double u1 = 1.0, v1 = 0.0, u2 = 0.0, v2 = 1.0;
-            rk4_pair(u1, v1, im, h1, h2, h3, h4, dt);
-            rk4_pair(u2, v2, im, h1, h2, h3, h4, dt);
-            pr[lane] = u1; pr[D + lane] = u2; pr[2 * D + lane] = v1; pr[3 * D + lane] = v2;
+            double q = qp[lane], p = qp[D + lane], h1, h2, h3, h4, p11, p12, p21, p22;
+            sep_mode_rk4(A.pot.kind, c0, c1, im, dt, q, p, red5, h1, h2, h3, h4);
+            qp[lane] = q;
+            qp[D + lane] = p;
+            sep_row_propagator(im, h1, h2, h3, h4, dt, p11, p12, p21, p22);
+            pr[lane] = p11; pr[D + lane] = p12; pr[2 * D + lane] = p21; pr[3 * D + lane] = p22;
         }
 #pragma unroll
         for (int i = 0; i < 5; ++i) red5[i] = wave_sum(red5[i]);
@@ -506,7 +486,7 @@ struct ModesMultiArgs {
 template <int KS>
 __global__ __launch_bounds__(256) void hk_modes_multi_kernel(StepArgs A, ModesMultiArgs MM) {
     const int D = A.st.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
+    const double dt = A.dt, h6 = dt / 6.0;
     __shared__ double wsum[KS][4];
     double esum[KS];
 #pragma unroll
@@ -522,29 +502,10 @@ __global__ __launch_bounds__(256) void hk_modes_multi_kernel(StepArgs A, ModesMu
             double *pr = MM.work + ((int64_t)ks * A.st.n + tr) * 4 * (int64_t)D;
             double red5[5] = {0, 0, 0, 0, 0};
             if (in) {
-                double v, g, h1, h2, h3, h4;
-                sep_eval(A.pot.kind, c0, c1, q, v, g, h1);
-                const double kq1 = p * im, kp1 = -g;
-                red5[0] = 0.5 * p * p * im - v;
-                const double q2 = q + hh * kq1, p2 = p + hh * kp1;
-                sep_eval(A.pot.kind, c0, c1, q2, v, g, h2);
-                const double kq2 = p2 * im, kp2 = -g;
-                red5[1] = 0.5 * p2 * p2 * im - v;
-                const double q3 = q + hh * kq2, p3 = p + hh * kp2;
-                sep_eval(A.pot.kind, c0, c1, q3, v, g, h3);
-                const double kq3 = p3 * im, kp3 = -g;
-                red5[2] = 0.5 * p3 * p3 * im - v;
-                const double q4 = q + dt * kq3, p4 = p + dt * kp3;
-                sep_eval(A.pot.kind, c0, c1, q4, v, g, h4);
-                const double kq4 = p4 * im, kp4 = -g;
-                red5[3] = 0.5 * p4 * p4 * im - v;
-                red5[4] = 0.5 * p4 * p4 * im + v;
-                q = q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4);
-                p = p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4);
-                double u1 = 1.0, v1 = 0.0, u2 = 0.0, v2 = 1.0;
-                rk4_pair(u1, v1, im, h1, h2, h3, h4, dt);
-                rk4_pair(u2, v2, im, h1, h2, h3, h4, dt);
-                pr[lane] = u1; pr[D + lane] = u2; pr[2 * D + lane] = v1; pr[3 * D + lane] = v2;
+                double h1, h2, h3, h4, p11, p12, p21, p22;
+                sep_mode_rk4(A.pot.kind, c0, c1, im, dt, q, p, red5, h1, h2, h3, h4);
+                sep_row_propagator(im, h1, h2, h3, h4, dt, p11, p12, p21, p22);
+                pr[lane] = p11; pr[D + lane] = p12; pr[2 * D + lane] = p21; pr[3 * D + lane] = p22;
                 double *qo = ks == KS - 1 ? qp : MM.qp_mid + ((int64_t)ks * A.st.n + tr) * 2 * D;
                 qo[lane] = q; qo[D + lane] = p;
             }
@@ -580,7 +541,7 @@ __global__ __launch_bounds__(256) void hk_step_w16_kernel(StepArgs A) {
     __shared__ double wsum[4];
     const int D = A.st.dim, DD = D * D, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rg = lane >> 4, tj = lane & 15;
-    const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
+    const double dt = A.dt, h6 = dt / 6.0;
     const bool colok = tj < D;
     const double sib = colok ? A.hk.si[tj] : 1.0, isib = 1.0 / sib;
     double sta[4], ista[4];
@@ -598,30 +559,13 @@ __global__ __launch_bounds__(256) void hk_step_w16_kernel(StepArgs A) {
         if (STEP) {
             double red5[5] = {0, 0, 0, 0, 0};
             if (lane < D) {
-                const double q = qp[lane], p = qp[D + lane], im = A.pot.inv_mass[lane];
+                const double im = A.pot.inv_mass[lane];
                 const double c0 = A.pot.par0[lane], c1 = A.pot.par1 ? A.pot.par1[lane] : 0.0;
-                double v, g, h1, h2, h3, h4;
-                sep_eval(A.pot.kind, c0, c1, q, v, g, h1);
-                const double kq1 = p * im, kp1 = -g;
-                red5[0] = 0.5 * p * p * im - v;
-                const double q2 = q + hh * kq1, p2 = p + hh * kp1;
-                sep_eval(A.pot.kind, c0, c1, q2, v, g, h2);
-                const double kq2 = p2 * im, kp2 = -g;
-                red5[1] = 0.5 * p2 * p2 * im - v;
-                const double q3 = q + hh * kq2, p3 = p + hh * kp2;
-                sep_eval(A.pot.kind, c0, c1, q3, v, g, h3);
-                const double kq3 = p3 * im, kp3 = -g;
-                red5[2] = 0.5 * p3 * p3 * im - v;
-                const double q4 = q + dt * kq3, p4 = p + dt * kp3;
-                sep_eval(A.pot.kind, c0, c1, q4, v, g, h4);
-                const double kq4 = p4 * im, kp4 = -g;
-                red5[3] = 0.5 * p4 * p4 * im - v;
-                red5[4] = 0.5 * p4 * p4 * im + v;
-                qp[lane] = q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4);
-                qp[D + lane] = p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4);
-                double u1 = 1.0, v1 = 0.0, u2 = 0.0, v2 = 1.0;
-                rk4_pair(u1, v1, im, h1, h2, h3, h4, dt);
-                rk4_pair(u2, v2, im, h1, h2, h3, h4, dt);
+                double q = qp[lane], p = qp[D + lane], h1, h2, h3, h4, u1, u2, v1, v2;       // P_a = [[u1, u2], [v1, v2]]
+                sep_mode_rk4(A.pot.kind, c0, c1, im, dt, q, p, red5, h1, h2, h3, h4);
+                qp[lane] = q;
+                qp[D + lane] = p;
+                sep_row_propagator(im, h1, h2, h3, h4, dt, u1, u2, v1, v2);
                 prop[wave][0][lane] = u1; prop[wave][1][lane] = u2; prop[wave][2][lane] = v1; prop[wave][3][lane] = v2;
             }
 #pragma unroll
@@ -648,14 +592,10 @@ __global__ __launch_bounds__(256) void hk_step_w16_kernel(StepArgs A) {
             const int e = r * D + tj;
             double mqq = ok ? M[e] : 0.0, mqp = ok ? M[DD + e] : 0.0, mpq = ok ? M[2 * DD + e] : 0.0, mpp = ok ? M[3 * DD + e] : 0.0;
             if (STEP) {
-                const double nqq = fma(p12[s], mpq, p11[s] * mqq), npq = fma(p22[s], mpq, p21[s] * mqq);
-                const double nqp = fma(p12[s], mpp, p11[s] * mqp), npp = fma(p22[s], mpp, p21[s] * mqp);
-                mqq = nqq; mpq = npq; mqp = nqp; mpp = npp;
+                sep_propagate_row(p11[s], p12[s], p21[s], p22[s], mqq, mqp, mpq, mpp);
                 if (ok) { M[e] = mqq; M[DD + e] = mqp; M[2 * DD + e] = mpq; M[3 * DD + e] = mpp; }
             }
-            m[s] = ok ? c_make(0.5 * (sta[s] * isib * mqq + ista[s] * sib * mpp),
-                               0.5 * (-SC_HBAR * sta[s] * sib * mqp + (1.0 / SC_HBAR) * ista[s] * isib * mpq))
-                      : c_make(r == tj ? 1.0 : 0.0, 0.0);
+            m[s] = ok ? prefactor_element_diag(sta[s], ista[s], sib, isib, mqq, mqp, mpq, mpp) : c_make(r == tj ? 1.0 : 0.0, 0.0);
         }
         // ---- phase C
         cplx det = c_make(1.0, 0.0);
@@ -701,7 +641,7 @@ __global__ __launch_bounds__(256) void hk_step_w16_kernel(StepArgs A) {
             cplx *c2 = (cplx *)A.st.c2;
             if (STEP) {
                 const cplx prev = c2[tr];
-                if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
             } else {
                 A.st.sgn[tr] = 1.0;
             }

@@ -30,7 +30,7 @@ template <int DP, bool STEP, int KIND>
 __global__ __launch_bounds__(256, 2) void hk_step_sep16_kernel(StepArgs A) {
     __shared__ double red[16];
     const int D = A.st.dim, DD = D * D, tid = threadIdx.x, r = tid & 15, grp = tid >> 4;
-    const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
+    const double dt = A.dt, h6 = dt / 6.0;
     const bool mine = r < D;
     const double sta = mine ? A.hk.st[r] : 1.0, ista = 1.0 / sta;
     const double im = mine ? A.pot.inv_mass[r] : 0.0, c0 = mine ? A.pot.par0[r] : 0.0;
@@ -71,29 +71,11 @@ __global__ __launch_bounds__(256, 2) void hk_step_sep16_kernel(StepArgs A) {
             // ---- RK4 of (q_a, p_a) with the reference's stage formula, action, <T+V> and the row propagator P_a
             double red5[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, p11 = 1.0, p12 = 0.0, p21 = 0.0, p22 = 1.0;
             if (mine) {
-                const double q = ldg(rq, vo_q, 0), p = ldg(rq, vo_q, 8 * D);
-                double v, g, h1, h2, h3, h4;
-                sep_eval(KIND, c0, c1, q, v, g, h1);
-                const double kq1 = p * im, kp1 = -g;
-                red5[0] = 0.5 * p * p * im - v;
-                const double q2 = q + hh * kq1, p2 = p + hh * kp1;
-                sep_eval(KIND, c0, c1, q2, v, g, h2);
-                const double kq2 = p2 * im, kp2 = -g;
-                red5[1] = 0.5 * p2 * p2 * im - v;
-                const double q3 = q + hh * kq2, p3 = p + hh * kp2;
-                sep_eval(KIND, c0, c1, q3, v, g, h3);
-                const double kq3 = p3 * im, kp3 = -g;
-                red5[2] = 0.5 * p3 * p3 * im - v;
-                const double q4 = q + dt * kq3, p4 = p + dt * kp3;
-                sep_eval(KIND, c0, c1, q4, v, g, h4);
-                const double kq4 = p4 * im, kp4 = -g;
-                red5[3] = 0.5 * p4 * p4 * im - v;
-                red5[4] = 0.5 * p4 * p4 * im + v;
-                stg(q + h6 * (kq1 + 2.0 * kq2 + 2.0 * kq3 + kq4), rq, vo_q, 0);
-                stg(p + h6 * (kp1 + 2.0 * kp2 + 2.0 * kp3 + kp4), rq, vo_q, 8 * D);
-                p11 = 1.0; p21 = 0.0; p12 = 0.0; p22 = 1.0;
-                rk4_pair(p11, p21, im, h1, h2, h3, h4, dt);       // (u, v) = (1, 0) -> first column of P_a
-                rk4_pair(p12, p22, im, h1, h2, h3, h4, dt);       // (0, 1) -> second column
+                double q = ldg(rq, vo_q, 0), p = ldg(rq, vo_q, 8 * D), h1, h2, h3, h4;
+                sep_mode_rk4(KIND, c0, c1, im, dt, q, p, red5, h1, h2, h3, h4);
+                stg(q, rq, vo_q, 0);
+                stg(p, rq, vo_q, 8 * D);
+                sep_row_propagator(im, h1, h2, h3, h4, dt, p11, p12, p21, p22);
             }
             {
                 double one = 1.0, s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -113,11 +95,9 @@ __global__ __launch_bounds__(256, 2) void hk_step_sep16_kernel(StepArgs A) {
             // ---- (Mqq, Mpq)' = P_a (Mqq, Mpq), (Mqp, Mpp)' = P_a (Mqp, Mpp)
 #pragma unroll
             for (int b = 0; b < DP; ++b) {
-                const double nqq = fma(p12, mpq[b], p11 * mqq[b]), npq = fma(p22, mpq[b], p21 * mqq[b]);
-                const double nqp = fma(p12, mpp[b], p11 * mqp[b]), npp = fma(p22, mpp[b], p21 * mqp[b]);
-                mqq[b] = nqq; mpq[b] = npq; mqp[b] = nqp; mpp[b] = npp;
+                sep_propagate_row(p11, p12, p21, p22, mqq[b], mqp[b], mpq[b], mpp[b]);
                 const unsigned vo = b < D ? vo_m + 8u * b : OOB;
-                stg(nqq, rm, vo, 0); stg(nqp, rm, vo, 8 * DD); stg(npq, rm, vo, 16 * DD); stg(npp, rm, vo, 24 * DD);
+                stg(mqq[b], rm, vo, 0); stg(mqp[b], rm, vo, 8 * DD); stg(mpq[b], rm, vo, 16 * DD); stg(mpp[b], rm, vo, 24 * DD);
             }
         }
         // ---- prefactor row a (rows and columns beyond D: identity, lanes beyond DP: no row)
@@ -125,8 +105,7 @@ __global__ __launch_bounds__(256, 2) void hk_step_sep16_kernel(StepArgs A) {
 #pragma unroll
         for (int b = 0; b < DP; ++b) {
             const double sib = b < D ? ksi[b] : 1.0, isib = 1.0 / sib;
-            mat[b] = (mine && b < D) ? c_make(0.5 * (sta * isib * mqq[b] + ista * sib * mpp[b]),
-                                              0.5 * (-SC_HBAR * sta * sib * mqp[b] + (1.0 / SC_HBAR) * ista * isib * mpq[b]))
+            mat[b] = (mine && b < D) ? prefactor_element_diag(sta, ista, sib, isib, mqq[b], mqp[b], mpq[b], mpp[b])
                                      : c_make(r == b ? 1.0 : 0.0, 0.0);
         }
         int weak = SC_SEP16_FORCE_FIXUP;
@@ -138,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void hk_step_sep16_kernel(StepArgs A) {
             cplx *c2 = (cplx *)A.st.c2;
             if (STEP) {
                 const cplx prev = c2[tr];
-                if (prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0) A.st.sgn[tr] = -A.st.sgn[tr];
+                if (crossed_branch_cut(prev, det)) A.st.sgn[tr] = -A.st.sgn[tr];
             } else {
                 A.st.sgn[tr] = 1.0;
             }

@@ -325,7 +325,7 @@ class HermanKlukPropagator(object):
         else:
             if desc is None:
                 desc = self._potential_descriptor(potential, dt)
-            if desc.kind not in (_lib.SC_POT_MORSE, _lib.SC_POT_HARMONIC_SEP, _lib.SC_POT_EPS_MORSE):
+            if desc.kind not in _lib.SEPARABLE_KINDS:
                 self._blocks_structurally_diagonal = False          # a dense Hessian couples the rows
             modal = self._modal_step_constants(potential, desc, dt)
             if modal is not None:
@@ -357,7 +357,7 @@ class HermanKlukPropagator(object):
 
     def _shortcut_applies(self, desc):
         return (self.exploit_separability and self._mono_is_diag and bool(self._pre.diag)
-                and desc.kind in (_lib.SC_POT_MORSE, _lib.SC_POT_HARMONIC_SEP, _lib.SC_POT_EPS_MORSE))
+                and desc.kind in _lib.SEPARABLE_KINDS)
 
     # The separable fast path streams the monodromy blocks in 16 x 16 tiles (SC_MONO_TILED16, include/semiclassical_hip.h);
     # everything else reads them row-major.  The state switches order in place when it enters / leaves that path.
@@ -365,7 +365,7 @@ class HermanKlukPropagator(object):
 
     def _fast_path_layout(self, desc):
         fast = (self._tiled_fast_path and bool(self._pre.diag) and 16 < self.dim <= 64
-                and desc.kind in (_lib.SC_POT_MORSE, _lib.SC_POT_HARMONIC_SEP, _lib.SC_POT_EPS_MORSE))
+                and desc.kind in _lib.SEPARABLE_KINDS)
         return _lib.SC_MONO_TILED16 if fast else _lib.SC_MONO_ROWMAJOR
 
     def _set_mono_layout(self, layout):
@@ -813,7 +813,7 @@ class HermanKlukPropagator(object):
 
     def _run_whole_loop(self, desc, dt, nt, slots, potential=None, moments=None):
         self._leave_modal()
-        if desc.kind not in (_lib.SC_POT_MORSE, _lib.SC_POT_HARMONIC_SEP, _lib.SC_POT_EPS_MORSE):
+        if desc.kind not in _lib.SEPARABLE_KINDS:
             self._blocks_structurally_diagonal = False
         self._sync_dense_mono(leave_diagonal=True)
         self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)

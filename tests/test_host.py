@@ -209,6 +209,18 @@ def test_cursor_handover_is_fenced_in_the_source():
     assert re.search(r"nextbuf\[tid\] = 0; weakbuf\[tid\] = 0;", src)
 
 
+def test_step_physics_is_defined_once_in_the_source():
+    """the per-mode RK4 (the only caller of sep_eval) and the branch rule of the sqrt tracker are written out in
+    csrc/sc_common.h alone: every kernel calls sep_mode_rk4 / crossed_branch_cut"""
+    import glob
+    csrc = os.path.join(ROOT, "semiclassical_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) > 20
+    for needle in ("sep_eval(", ".y * det.y"):
+        holders = [os.path.basename(f) for f in files if needle in open(f).read()]
+        assert holders == ["sc_common.h"], (needle, holders)
+
+
 def test_normal_mode_step_matrices_reproduce_the_full_step_matrix():
     """MolecularHarmonicPotential._normal_modes (sc_hk_run_modal): T blockdiag-by-mode(phi) T^-1 with T = diag(A, B) is the RK4 step
     matrix Phi(dt) of _step_matrix, including zero-frequency modes (free motion) and a wide mass ratio"""
