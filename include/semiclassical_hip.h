@@ -337,6 +337,30 @@ int sc_hk_run_m(const sc_potential *pot, const sc_state *st, const sc_hk_consts 
                 const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
                 double dt, int32_t nsteps, double *partials, double *slots_out, double *elog, double *moments_out, void *stream);
 
+/* ---- Block sums (Monte-Carlo error bars of anything linear in C_auto(t), k_ic(t): the rate k_ic(E)) ------------------------
+ * A batch is split into B fixed blocks, B a power of two in 2 ... 64 (anything else: SC_ERR_BAD_ARGUMENT): the trajectory with
+ * rank-local index i belongs to block (i >> 2) & (B - 1).  Per time step the entry points below ADD NOTHING to the state or to the
+ * slot sums; they form, from terms the existing kernels already produce,
+ *     out[b][0..3] = Re sum cq_i, Im sum cq_i, Re sum kq_i, Im sum kq_i   over the trajectories i of block b
+ * with cq_i, kq_i as defined at sc_hk_correlate (propagators.py:784-911: 806 and 837 for cq_i, 900-909 for kq_i; weight included,
+ * dynamical phase not), so that sum_b out[b] is the slot row of the step.  One writer per output, fixed summation order: the same
+ * bits in every run.  The host evaluates a linear functional on every block's own estimate out[b] N / n_b and takes the standard
+ * error from the spread of the B values (hostmath.block_standard_error, rates.rate_standard_error).
+ *   sc_term_blocks      adds the block sums of the EXPORTED per-trajectory terms cq[n], kq[n] (complex; what sc_hk_correlate(_m)
+ *                       writes to cq_out / kq_out, sc_wm_correlate to its term arrays, or the caller forms itself for
+ *                       position-dependent couplings) into out[B][4].  kq may be NULL: the k columns are 0.
+ *   sc_term_blocks_at   the same into ROW *cursor of out_base[.][B][4] (cursor as for sc_reduce_slot_at).  It reads the cursor and
+ *                       never advances it: launch it BEFORE the reduction that does.
+ *   sc_hk_run_blocks    adds, for the whole-loop entry points (sc_hk_run, sc_hk_run_m, sc_hk_run_modal, sc_hk_run_modal_m), the
+ *                       block sums of their per-wavefront `partials` [nsteps][sc_hk_run_slots(n, dim)][5] of the launch that just
+ *                       ran into out[nsteps][B][4]: wavefront slot s holds the trajectories with (i >> 2) mod slots == s, and the
+ *                       slot count either does not wrap (slot = i >> 2) or is a multiple of B, so block = s mod B; anything else
+ *                       is refused (SC_ERR_UNSUPPORTED).  Same stream, before `partials` is reused. */
+int sc_term_blocks(const double *cq, const double *kq, int64_t n, int32_t B, double *out, void *stream);
+int sc_term_blocks_at(const double *cq, const double *kq, int64_t n, int32_t B, double *out_base, const int64_t *cursor,
+                      void *stream);
+int sc_hk_run_blocks(const double *partials, int64_t n, int32_t dim, int32_t nsteps, int32_t B, double *out, void *stream);
+
 /* sc_hk_run for a CONSTANT dense Hessian with the monodromy blocks of the state in NORMAL-MODE coordinates (round 4).  RK4 of a
  * linear system commutes with a change of basis: with W = m^-1/2 H m^-1/2 = U diag(lambda) U^T, A = m^-1/2 U, B = m^1/2 U and
  *     Mqq~ = A^-1 Mqq A,  Mqp~ = A^-1 Mqp B,  Mpq~ = B^-1 Mpq A,  Mpp~ = B^-1 Mpp B

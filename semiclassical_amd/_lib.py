@@ -112,6 +112,9 @@ SIGNATURES = {
     "sc_reduce_moments": (C.c_int, [c_double_p, C.c_int32, c_double_p, C.c_void_p]),
     "sc_reduce_slot_moments_at": (C.c_int, [c_double_p, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p,
                                             C.c_void_p]),
+    "sc_term_blocks": (C.c_int, [c_double_p, c_double_p, C.c_int64, C.c_int32, c_double_p, C.c_void_p]),
+    "sc_term_blocks_at": (C.c_int, [c_double_p, c_double_p, C.c_int64, C.c_int32, c_double_p, C.c_void_p, C.c_void_p]),
+    "sc_hk_run_blocks": (C.c_int, [c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_void_p]),
     "sc_hk_run_slots": (C.c_int, [C.c_int64, C.c_int32]),
     "sc_hk_run_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "sc_hk_run_m": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), P(sc_overlap_consts), P(sc_nac_consts), c_double_p,

@@ -242,7 +242,14 @@ __device__ __forceinline__ bool crossed_branch_cut(cplx prev, cplx det) {
     return prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0;
 }
 
-#define SC_SEP16_MAX_D 12    // D <= 12: hk_step_sep16_kernel (four trajectories per wavefront); 13 .. 16: hk_step_w16_kernel
+// The partition of a batch into B blocks for the Monte-Carlo error bars (batch means), defined ONCE: the
+// block of the trajectory with rank-local index i.  Groups of four consecutive trajectories go round robin to the blocks; B is a
+// power of two in 2 ... 64.  The trajectories are independent draws, so any fixed partition is valid; this one is what the
+// whole-loop kernels already keep apart (block = wavefront slot mod B, sc_blocks.hip).  hostmath.error_block is the host's copy.
+__host__ __device__ __forceinline__ int sc_error_block(int64_t i, int B) { return (int)((i >> 2) & (B - 1)); }
+__host__ __device__ __forceinline__ bool sc_error_blocks_valid(int B) { return B >= 2 && B <= 64 && (B & (B - 1)) == 0; }
+
+#define SC_SEP16_MAX_D 12   // D <= 12: hk_step_sep16_kernel (four trajectories per wavefront); 13 .. 16: hk_step_w16_kernel
 int sc_launch_step_sep16(const StepArgs &a, int grid_entries, hipStream_t s);   // sc_hk_step_sep16.hip: 1 launched, 0 not taken
 int sc_launch_step_sd_multi(const StepArgs &a, const sc_multi_scratch &ms, hipStream_t s);    // sc_hk_step_sd.hip: two steps per visit
 int sc_launch_step_lin(const StepArgs &a, int grid, hipStream_t s);   // sc_hk_step_lin.hip: 1 launched, 0 shape not built

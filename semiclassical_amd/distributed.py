@@ -177,7 +177,7 @@ class RcclCommunicator(object):
             self.handle = None
 
 
-def flush_correlations(slots, moments=None, group=None, comm=None):
+def flush_correlations(slots, moments=None, blocks=None, block_counts=None, group=None, comm=None):
     """sum the raw per-step correlation sums over all ranks, in place (columns 0..3 of ``slots``).
 
     Column 4 (reserved) is left rank-local.  A single collective per call.  With the ``gloo`` backend a
@@ -186,18 +186,36 @@ def flush_correlations(slots, moments=None, group=None, comm=None):
     all-reduce through the C-ABI's ``sc_flush_allreduce`` instead of torch.distributed.
     ``moments``: the (nt, 6) second-moment sums of ``run(..., moments=...)``, summed in place as well -- packed into the
     same buffer, so that the flush stays one collective.
+    ``blocks``: the (nt, B, 4) block sums of ``run(..., blocks=...)`` with ``block_counts``, a float64 tensor (B,) of this rank's
+    trajectories per block (``hostmath.block_counts`` of the rank-local count: every rank partitions by its local index).  Sums
+    and counts add over the ranks, in place, in the same single collective: further columns and one more row of the buffer.
     """
     nt = slots.shape[0]
+    if (blocks is None) != (block_counts is None):
+        raise ValueError("flush_correlations: blocks and block_counts travel together")
+    nb = 0 if blocks is None else blocks.shape[1]
 
     def packed():
-        if moments is None:
-            return slots[:, :4].contiguous()
-        return torch.cat((slots[:, :4], moments[:nt, :6]), dim=1).contiguous()
+        parts = [slots[:, :4]]
+        if moments is not None:
+            parts.append(moments[:nt, :6])
+        if blocks is None:
+            return parts[0].contiguous() if len(parts) == 1 else torch.cat(parts, dim=1).contiguous()
+        parts.append(blocks[:nt].reshape(nt, 4 * nb))
+        body = torch.cat(parts, dim=1)
+        last = torch.zeros((1, body.shape[1]), dtype=body.dtype, device=body.device)
+        last[0, :nb] = block_counts.to(device=body.device, dtype=body.dtype)
+        return torch.cat((body, last), dim=0).contiguous()
 
     def unpack(buf):
-        slots[:, :4] = buf[:, :4]
+        slots[:, :4] = buf[:nt, :4]
+        at = 4
         if moments is not None:
-            moments[:nt, :6] = buf[:, 4:10]
+            moments[:nt, :6] = buf[:nt, 4:10]
+            at = 10
+        if blocks is not None:
+            blocks[:nt] = buf[:nt, at:at + 4 * nb].reshape(nt, nb, 4)
+            block_counts.copy_(buf[nt, :nb])
 
     if comm is not None:
         buf = packed()

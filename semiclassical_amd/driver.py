@@ -134,11 +134,17 @@ class CorrelationStore(object):
 
     ERROR_KEYS = ('autocorrelation_error', 'ic_correlation_error', 'autocorrelation_second_moment', 'ic_correlation_second_moment')
 
-    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None):
+    BLOCK_KEYS = ('autocorrelation_blocks', 'ic_correlation_blocks', 'block_trajectories')
+
+    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None):
         """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
         per-sample second moments (rows (S_rr, S_ii, S_ri) times the batch size, phase applied) of the batch, folded the same
         way; the standard errors of the pooled means follow from them.  Files and batches that do not both carry them lose
-        the error keys (with a warning): errors over only part of the stored trajectories would be wrong."""
+        the error keys (with a warning): errors over only part of the stored trajectories would be wrong.
+        ``blocks``: (C_blocks, k_blocks, counts) -- the block sums (nt, B) of the batch (phase applied; their sum over the blocks is
+        the batch mean) and the trajectories per block (B,).  The sums are folded with the same weights as the means, so that the
+        stored blocks keep adding up to the stored means, and the counts add: block b of the file is block b of every batch,
+        pooled.  The same rule as for the second moments drops the block keys."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
@@ -158,7 +164,22 @@ class CorrelationStore(object):
                            "this task does not compute them (\"standard_errors\": true)")
             for key in self.ERROR_KEYS:
                 stored.pop(key, None)
+        have_blocks = 'autocorrelation_blocks' in stored
+        fits = blocks is not None and (done == 0 or (have_blocks and stored['autocorrelation_blocks'].shape == np.shape(blocks[0])))
+        if fits:
+            pool = have_blocks and done > 0
+            for key, new in zip(self.BLOCK_KEYS[:2], blocks[:2]):
+                stored[key] = (ntraj * np.asarray(new) + done * stored[key]) / total if pool else np.asarray(new, dtype=complex)
+            counts = np.asarray(blocks[2], dtype=np.int64)
+            stored['block_trajectories'] = stored['block_trajectories'] + counts if pool else counts
+        elif have_blocks or blocks is not None:
+            logger.warning("error blocks dropped from %s: %s", self.path,
+                           "this task does not compute them (\"error_blocks\": B)" if blocks is None else
+                           "the stored trajectories have no blocks, or another number of them")
+            for key in self.BLOCK_KEYS:
+                stored.pop(key, None)
         stored.pop('ic_rate', None)          # a rate computed from the old correlation function is stale now
+        stored.pop('ic_rate_error', None)
         logger.info(f"<phi(0)|phi(0)>= {stored['autocorrelation'][0]}")
         assert abs(stored['autocorrelation'][0] - 1.0) < 1.0e-3
         np.savez(self.path, **stored)
@@ -176,15 +197,23 @@ def make_propagator(task, Gamma_0, device):
     return propagators.HermanKlukPropagator(Gamma_0, Gamma_0, device=device)
 
 
-def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False):
+def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False,
+                    error_blocks=0):
     """C_auto(t), k_ic(t) of one batch of trajectories: the device loop leaves the raw per-step sums in a device buffer,
     ``flush`` (None on a single rank) adds the buffers of all ranks -- ONE all-reduce per batch, SURVEY 8e -- and the host
     applies the dynamical phase.  ``norm_every`` > 0 logs the wavefunction norm (the O(n^2) convergence diagnostic of
     cli.py:424-429) at every norm_every-th step by cutting the device loop there; with ``across_ranks`` it is the norm of
     the whole sharded batch (a collective: every rank calls it, ``log`` says who prints).  ``errors``: also the per-sample
-    second moments (M_C, M_k) of the batch, (nt, 3) each (see CorrelationStore.add_batch), flushed in the same collective."""
+    second moments (M_C, M_k) of the batch, (nt, 3) each (see CorrelationStore.add_batch), flushed in the same collective.
+    ``error_blocks`` = B > 0: the last element of the result is (C_blocks, k_blocks, counts), the block sums (nt, B) of the batch
+    with the phase applied and the trajectories per block (every rank partitions ITS trajectories by their local index; sums and
+    counts are added over the ranks in the same collective)."""
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
     moments = torch.zeros((nt, 6), dtype=torch.float64, device=propagator.device) if errors else None
+    blocks = counts = None
+    if error_blocks:
+        blocks = torch.zeros((nt, error_blocks, 4), dtype=torch.float64, device=propagator.device)
+        counts = torch.from_numpy(propagator.block_counts(propagator.ntraj, error_blocks)).to(torch.float64)
     length = norm_every if norm_every > 0 else nt
     pieces = []
     for first in range(0, nt, length):
@@ -195,22 +224,29 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         count = min(length, nt - first)
         pieces.append((first, count, propagator.t))
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
-                       moments=None if moments is None else moments[first:first + count])
+                       moments=None if moments is None else moments[first:first + count],
+                       blocks=None if blocks is None else blocks[first:first + count])
     if flush is not None:
-        if moments is None:
+        if blocks is not None:
+            flush(slots, moments, blocks, counts)
+        elif moments is None:
             flush(slots)
         else:
             flush(slots, moments)
     propagator.synchronize()                      # raises the energy-conservation error of this rank's trajectories
+    tail = ()
+    if blocks is not None:
+        parts = [propagator.finalize_blocks(blocks[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
+        tail = (tuple(np.concatenate(part) for part in zip(*parts)) + (np.rint(counts.numpy()).astype(np.int64),),)
     if moments is None:
         parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
                  for first, count, t0 in pieces]
-        return tuple(np.concatenate(part) for part in zip(*parts))
+        return tuple(np.concatenate(part) for part in zip(*parts)) + tail
     parts = [propagator.phased_moments(slots[first:first + count], moments[first:first + count], t0, dt, setup.zero_point_energy)
              for first, count, t0 in pieces]
     C, k, mC, mk = (np.concatenate(part) for part in zip(*parts))
     n = propagator._ntraj_norm
-    return C, k, n * mC, n * mk
+    return (C, k, n * mC, n * mk) + tail
 
 
 def run_semiclassical_dynamics(task, device='cuda', comm=None):
@@ -264,7 +300,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     device_seed = int(seed_all) if seed_all is not None else int.from_bytes(os.urandom(8), 'little')
 
     if comm is not None:
-        flush = lambda slots, moments=None: Dm.flush_correlations(slots, moments, comm=comm)
+        flush = lambda slots, moments=None, blocks=None, counts=None: Dm.flush_correlations(slots, moments, blocks, counts, comm=comm)
     elif world > 1:
         flush = Dm.flush_correlations
     else:
@@ -284,13 +320,18 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
             propagator.set_initial_conditions(setup.q0, setup.p0, setup.Gamma_0, zi[:, mine], probi[mine],
                                               ntraj_total=per_batch)
         errors = bool(task.get('standard_errors', False))
+        # error bars of the rate by batch means (a key the reference does not have): B blocks per batch, 0 = off
+        error_blocks = int(task.get('error_blocks', 0) or 0)
+        if error_blocks and not hostmath.valid_error_blocks(error_blocks):
+            raise ConfigurationError(f"'error_blocks' should be a power of two in 2 ... 64 (or 0), got {error_blocks}")
         out = propagate_batch(propagator, setup, dt, nt, times, norm_every=task.get('calc_norm_every', 0), flush=flush,
-                              across_ranks=world > 1 and comm is None, log=writer, errors=errors)
+                              across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks)
         autocorrelation, ic_correlation = out[:2]
         assert not np.isnan(autocorrelation).any(), f"encountered NaN's in autocorrelation : {autocorrelation}"
         assert not np.isnan(ic_correlation).any(), f"encountered NaN's in IC correlation : {ic_correlation}"
         if writer:
-            store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:] if errors else None)
+            store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:4] if errors else None,
+                            blocks=out[-1] if error_blocks else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -320,6 +361,11 @@ def calculate_rates(task):
     keep = energies >= 0.0
     stored['energies'] = energies[keep]
     stored['ic_rate'] = (2.0 * np.pi * spectrum)[keep].real
+    stored.pop('ic_rate_error', None)
+    if all(key in stored for key in CorrelationStore.BLOCK_KEYS):
+        # Monte-Carlo standard error of the rate at every energy from the spread of the blocks' own rates (batch means)
+        _, sigma = rates.rate_standard_error(stored['times'], stored['ic_correlation_blocks'], stored['block_trajectories'], lineshape)
+        stored['ic_rate_error'] = (2.0 * np.pi * sigma)[keep]
     np.savez(task.get('rates', 'correlations.npz'), **stored)
 
 

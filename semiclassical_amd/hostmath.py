@@ -205,3 +205,56 @@ def standard_errors(mean, m3, ntraj):
         sr = np.sqrt(np.maximum(n * m3[..., 0] - mean.real ** 2, 0.0) / den)
         si = np.sqrt(np.maximum(n * m3[..., 1] - mean.imag ** 2, 0.0) / den)
     return sr + 1j * si
+
+
+# ---- batch means: error bars of anything linear in C_auto(t) or k_ic(t) ----
+
+def valid_error_blocks(B):
+    """B blocks: a power of two in 2 ... 64 (sc_error_blocks_valid, csrc/sc_common.h)"""
+    return isinstance(B, (int, np.integer)) and 2 <= B <= 64 and (B & (B - 1)) == 0
+
+
+def error_block(i, B):
+    """The partition of a batch into B blocks, the host's copy of sc_error_block (csrc/sc_common.h): block of the trajectory with
+    rank-local index ``i`` (an integer or an integer array).  Groups of four consecutive trajectories are dealt round robin to
+    the blocks.  The trajectories are independent draws, so any fixed partition is valid; this one is what the whole-loop kernels
+    already keep apart: their wavefront slot holds the trajectories with (i >> 2) mod slots == slot, and the slot count either
+    does not wrap or is a multiple of B, so block = slot mod B."""
+    return (np.asarray(i, dtype=np.int64) >> 2) & (B - 1)
+
+
+def block_counts(n, B):
+    """n_b: how many of the trajectories 0 ... n - 1 fall into each of the B blocks of ``error_block``; follows from n alone"""
+    if not valid_error_blocks(B):
+        raise ValueError(f"the number of blocks has to be a power of two in 2 ... 64, got {B}")
+    groups, rest = divmod(int(n), 4)
+    counts = np.full(B, 4 * (groups // B), dtype=np.int64)
+    counts[:groups % B] += 4
+    counts[groups % B] += rest
+    return counts
+
+
+def block_standard_error(values, counts):
+    """Standard error of a pooled estimate from its values on B blocks (batch means).
+
+    ``values`` (B, ...): a functional LINEAR in the correlation functions evaluated on each block's own estimate (the block's
+    sum times N / n_b); ``counts`` (B,): the trajectories n_b of the blocks.  With N = sum n_b and the pooled value
+    F = sum_b n_b F_b / N the result is sqrt(sum_b n_b (F_b - F)^2 / ((B' - 1) N)) over the B' non-empty blocks -- the ANOVA form,
+    exact for unequal n_b; with one sample per block it is the per-sample standard error.  Blocks with n_b = 0 are dropped; fewer
+    than two non-empty blocks give NaN.  Complex values: sigma_Re + i sigma_Im, as ``standard_errors``."""
+    values = np.asarray(values)
+    counts = np.asarray(counts, dtype=np.float64)
+    assert values.shape[0] == counts.shape[0], "one value per block"
+    keep = counts > 0
+    values, counts = values[keep], counts[keep]
+    nb = counts.shape[0]
+    if nb < 2:
+        return np.full(values.shape[1:], np.nan + (1j * np.nan if np.iscomplexobj(values) else 0.0))
+    total = counts.sum()
+    w = counts.reshape((nb,) + (1,) * (values.ndim - 1))
+    pooled = (w * values).sum(axis=0) / total
+    dev = values - pooled
+    if np.iscomplexobj(values):
+        return (np.sqrt((w * dev.real ** 2).sum(axis=0) / ((nb - 1) * total))
+                + 1j * np.sqrt((w * dev.imag ** 2).sum(axis=0) / ((nb - 1) * total)))
+    return np.sqrt((w * dev ** 2).sum(axis=0) / ((nb - 1) * total))

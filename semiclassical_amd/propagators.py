@@ -576,15 +576,26 @@ class HermanKlukPropagator(object):
         check(lib.sc_term_moments(ptr(self._cq), ptr(self._kq) if has_k else None, self.ntraj, ptr(self._mpart), self._stream()))
         return self._gterm
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None, mom_ptr=None):
+    def _term_blocks(self, has_k, blk, cursor=None):
+        """block sums of the exported per-trajectory terms _cq (and _kq) into the (B, 4) doubles at blk = (address, B), or into
+        row *cursor of the (., B, 4) buffer there (the cursor is read, not advanced: launch before the reduction that advances it)"""
+        out, nblocks = blk
+        kq = ptr(self._kq) if has_k else None
+        if cursor is None:
+            check(lib.sc_term_blocks(ptr(self._cq), kq, self.ntraj, nblocks, C_void(out), self._stream()))
+        else:
+            check(lib.sc_term_blocks_at(ptr(self._cq), kq, self.ntraj, nblocks, C_void(out), ptr(cursor), self._stream()))
+
+    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None, mom_ptr=None, blk=None):
         """per-trajectory terms + their sums for the current state into the 5-double slot at `slot_ptr` (`slot_row`: the same
         five doubles as a tensor, needed when the k_ic sum is formed by torch: position-dependent couplings; `state`: another
         view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi; `mom_ptr`: the six second-moment
-        sums go to the 6 doubles there, formed inside the correlate kernel)"""
+        sums go to the 6 doubles there, formed inside the correlate kernel; `blk` = (address, B): the block sums of the step go
+        there -- the terms are exported and sc_term_blocks follows the correlate kernel)"""
         s = self._stream()
         nac = self._nac
         generic = getattr(self, "_nac_generic", None) is not None
-        per_trajectory = per_trajectory or generic
+        per_trajectory = per_trajectory or generic or blk is not None
         in_kernel = mom_ptr is not None and not generic
         with self._timed("hk_correlate"):
             check(lib.sc_hk_correlate_m(self._state if state is None else state, self._ovl_t0, nac, ptr(self._vi), ptr(self.probi),
@@ -592,10 +603,14 @@ class HermanKlukPropagator(object):
                                         ptr(self._cq) if per_trajectory else None,
                                         ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
                                         ptr(self._mpart) if in_kernel else None, s))
+        if blk is not None and not generic:
+            self._term_blocks(nac is not None, blk, cursor)
         self._reduce_into(self._cpart, self._gcorr, slot_ptr, cursor, mom_ptr if in_kernel else None, self._gcorr)
         if generic:
             assert slot_row is not None and cursor is None
             self._generic_kic(slot_row)
+            if blk is not None:
+                self._term_blocks(True, blk)
             if mom_ptr is not None:
                 # k_ic terms formed by torch (position-dependent couplings): the moments of the exported terms
                 rows = self._term_moments(True)
@@ -627,7 +642,7 @@ class HermanKlukPropagator(object):
         k = complex(self._slot_host[2], self._slot_host[3])
         return k * np.exp(1j / hbar * self.t * energy0_es)
 
-    def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False):
+    def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None):
         """The caller loop of cli.py:401-436 on the device: ``nt`` times (C_auto, k_ic, step), no host sync.
 
         Returns ``(autocorrelation[nt], ic_correlation[nt])`` as complex NumPy arrays.  With ``slots`` (a
@@ -650,6 +665,13 @@ class HermanKlukPropagator(object):
         without the dynamical phase (``finalize_moments`` applies it and forms the errors).  With ``slots=None`` and
         ``standard_errors=True`` the return value is ``(C, k, sigma_C, sigma_k)``, sigma = sigma_Re + i sigma_Im of each step.
         C and k are the same bit for bit with or without moments.
+
+        Error bars of the rate: ``blocks`` (a contiguous float64 device tensor (>= nt, B, 4), B a power of two in 2 ... 64) receives
+        per step the sums Re C, Im C, Re k, Im k over each of the B blocks of trajectories (``hostmath.error_block``; row k = the
+        state before step k, without the dynamical phase: ``finalize_blocks`` applies it), on every route.  Their sum over the
+        blocks is the slot row; any linear functional of C(t) or k(t) evaluated per block gives its standard error
+        (``hostmath.block_standard_error``, ``rates.rate_standard_error``).  Independent of ``moments``; slots and moments are the
+        same bit for bit with or without blocks.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
         dt = float(dt)
@@ -665,6 +687,9 @@ class HermanKlukPropagator(object):
             self._check_slots(slots, nt)
         if moments is not None:
             self._check_slots(moments, nt, width=6, name="moments")
+        nblocks = None if blocks is None else self._check_blocks(blocks, nt)
+        bbase = None if blocks is None else blocks.data_ptr()
+        brow = (lambda k: None) if bbase is None else (lambda k: (bbase + 32 * nblocks * k, nblocks))
         t0 = self.t
         base = slots.data_ptr()
         mbase = None if moments is None else moments.data_ptr()
@@ -674,22 +699,22 @@ class HermanKlukPropagator(object):
         desc = self._potential_descriptor(potential, dt) if fused else None
         if fused and self._whole_loop_applies(desc):
             # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run)
-            self._run_whole_loop(desc, dt, nt, slots, potential, moments)
+            self._run_whole_loop(desc, dt, nt, slots, potential, moments, blocks)
         elif (use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing
               and self._modal_step_constants(potential, desc, dt) is None):
             # (the normal-mode step runs the plain loop: its first step may change the basis of the blocks)
-            self._run_graph(potential, dt, nt, desc, slots, mbase)
+            self._run_graph(potential, dt, nt, desc, slots, mbase, brow(0))
         else:
             pairs = fused and nt >= 2 and self._multi_applies(desc)
             k = 0
             while k < nt:
-                self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k], mom_ptr=mrow(k))
+                self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k], mom_ptr=mrow(k), blk=brow(k))
                 if pairs and k + 1 < nt:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
                     self._launch_correlate(base + 40 * (k + 1), per_trajectory=False, state=self._multi["state_mid"],
-                                           mom_ptr=mrow(k + 1))
+                                           mom_ptr=mrow(k + 1), blk=brow(k + 1))
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -811,7 +836,7 @@ class HermanKlukPropagator(object):
             self._to_normal_modes(self._modal_basis, forward=False)
             self._modal_basis = None
 
-    def _run_whole_loop(self, desc, dt, nt, slots, potential=None, moments=None):
+    def _run_whole_loop(self, desc, dt, nt, slots, potential=None, moments=None, blocks=None):
         self._leave_modal()
         if desc.kind not in _lib.SEPARABLE_KINDS:
             self._blocks_structurally_diagonal = False
@@ -839,6 +864,11 @@ class HermanKlukPropagator(object):
             else:
                 run = lib.sc_hk_run_m if mom else lib.sc_hk_run
                 check(run(desc, self._state, self._hk, *head, *tail))
+            if blocks is not None:
+                # block sums of this launch's per-wavefront partials, before the next launch reuses the scratch
+                nblocks = blocks.shape[1]
+                check(lib.sc_hk_run_blocks(ptr(partials), self.ntraj, self.dim, k, nblocks,
+                                           C_void(blocks.data_ptr() + 32 * nblocks * k0), self._stream()))
         if modal is not None:
             self._to_normal_modes(modal, forward=False)
         self._run_scratch = partials          # alive until the stream has consumed it
@@ -892,13 +922,13 @@ class HermanKlukPropagator(object):
             check(lib.sc_energy_guard(C_void(m["epart"].data_ptr() + 8 * sub * self._gstep), self._gstep, float(n), ptr(self._elog), s))
         self._nsteps += 2
 
-    def _run_graph(self, potential, dt, nt, desc, slots, mbase=None):
+    def _run_graph(self, potential, dt, nt, desc, slots, mbase=None, blk=None):
         """first iteration eagerly (lazy set-up, layout conversion), then one captured iteration replayed nt - 1 times"""
         base = slots.data_ptr()
         cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
 
         def iteration():
-            self._launch_correlate(base, per_trajectory=False, cursor=cursor, mom_ptr=mbase)
+            self._launch_correlate(base, per_trajectory=False, cursor=cursor, mom_ptr=mbase, blk=blk)
             self._launch_step(potential, dt, desc=desc, remembered=True)
         iteration()
         graph = torch.cuda.CUDAGraph()
@@ -923,6 +953,32 @@ class HermanKlukPropagator(object):
             raise ValueError(f"{name} has to be a contiguous float64 tensor of shape (>= {nt}, {width}) on {self.device}, got "
                              f"{getattr(slots, 'dtype', type(slots))} {tuple(getattr(slots, 'shape', ()))} on "
                              f"{getattr(slots, 'device', '?')}")
+
+    def _check_blocks(self, blocks, nt):
+        """the kernels write B x 4 doubles at blocks + 32 B k for k < nt: refuse anything that is not exactly that buffer; returns B"""
+        if not (isinstance(blocks, torch.Tensor) and blocks.dtype == F64 and blocks.dim() == 3 and blocks.shape[2] == 4
+                and blocks.shape[0] >= nt and blocks.is_contiguous() and blocks.device == self.device):
+            raise ValueError(f"blocks has to be a contiguous float64 tensor of shape (>= {nt}, B, 4) on {self.device}, got "
+                             f"{getattr(blocks, 'dtype', type(blocks))} {tuple(getattr(blocks, 'shape', ()))} on "
+                             f"{getattr(blocks, 'device', '?')}")
+        nblocks = int(blocks.shape[1])
+        if not hostmath.valid_error_blocks(nblocks):
+            raise ValueError(f"the number of blocks has to be a power of two in 2 ... 64, got {nblocks}")
+        return nblocks
+
+    @staticmethod
+    def block_counts(n, B):
+        """trajectories per block of a rank that holds ``n`` trajectories (hostmath.block_counts; sharded: add over the ranks)"""
+        return hostmath.block_counts(n, B)
+
+    @staticmethod
+    def finalize_blocks(blocks, t0, dt, energy0_es):
+        """(C_blocks, k_blocks), complex (nt, B): the block sums of run(..., blocks=...) with the dynamical phase of finalize_slots
+        applied; their sums over the blocks are the C and k of finalize_slots"""
+        raw = blocks.detach().cpu().numpy() if isinstance(blocks, torch.Tensor) else np.asarray(blocks)
+        times = t0 + hostmath.time_grid(raw.shape[0], dt)
+        phase = np.exp(1j / hbar * times * energy0_es)[:, None]
+        return (raw[:, :, 0] + 1j * raw[:, :, 1]) * phase, (raw[:, :, 2] + 1j * raw[:, :, 3]) * phase
 
     @staticmethod
     def finalize_slots(slots, t0, dt, energy0_es):
@@ -1320,7 +1376,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         Dm.all_reduce_sum(slot, group)
         return float(torch.sqrt(slot[0]).item())
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, mom_ptr=None):
+    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, mom_ptr=None, blk=None):
         # the per-trajectory terms were produced together with the prefactor; recompute (with the stored branch
         # signs, no tracking) only if the coupling vector was not known at that time
         knows_nac = self._wm_nac_bufs is not None or self._wm_nac_traj is not None
@@ -1331,6 +1387,8 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
             # sc_wm_correlate exports every trajectory's terms exactly once (register kernel or its pivoted re-run): their moments,
             # in a pass of its own (not fused into the WM kernels)
             rows = self._term_moments(self._wm_has_nac)
+        if blk is not None:
+            self._term_blocks(self._wm_has_nac, blk, cursor)         # the same exported terms; before the cursor advances
         self._reduce_into(self._wpart, self._gwm, slot_ptr, cursor, mom_ptr, rows)
 
     def _correlate_current(self, need_nac):

@@ -6,9 +6,9 @@ reference semiclassical/rates.py:20-82 including the cos^2 switching function an
 import numpy as np
 from numpy import fft
 
-from . import units
+from . import hostmath, units
 
-__all__ = ['rate_from_correlation']
+__all__ = ['rate_from_correlation', 'rate_standard_error']
 
 
 def rate_from_correlation(times, correlation, lineshape):
@@ -31,3 +31,26 @@ def rate_from_correlation(times, correlation, lineshape):
     rate = 2 * t_max * fft.ifft(fft.ifftshift(damp * lineshape(full_times) * full))
     rate *= 1.0e15 / units.autime_to_fs
     return fft.fftshift(energies), fft.fftshift(rate)
+
+
+def rate_standard_error(times, correlation_blocks, counts, lineshape):
+    """Monte-Carlo standard error of the rate of ``rate_from_correlation`` by batch means.
+
+    correlation_blocks: complex (nt, B), the block sums of k(t) (phase applied; their sum over the blocks is the k(t) the rate is
+    computed from); counts: (B,) trajectories per block.  The transform is linear in k(t): it is applied to every block's own
+    estimate ``blocks[:, b] N / n_b`` and the error follows from the spread of the B rates (hostmath.block_standard_error), which
+    carries the correlation between the time steps that per-step errors cannot.  Returns (energies, sigma) on the grid and in the
+    unit of ``rate_from_correlation``; sigma is the error of the real part of the rate.  Empty blocks are left out."""
+    blocks = np.asarray(correlation_blocks)
+    counts = np.asarray(counts, dtype=np.float64)
+    assert blocks.ndim == 2 and blocks.shape == (times.shape[0], counts.shape[0]), "`correlation_blocks` should have the shape (nt, B)"
+    total = counts.sum()
+    filled = np.flatnonzero(counts > 0)
+    energies, values = None, []
+    for b in filled:
+        energies, rate = rate_from_correlation(times, blocks[:, b] * (total / counts[b]), lineshape)
+        values.append(rate.real)
+    if energies is None:
+        energies, _ = rate_from_correlation(times, np.zeros(times.shape[0], dtype=complex), lineshape)
+        return energies, np.full(energies.shape, np.nan)
+    return energies, hostmath.block_standard_error(np.array(values), counts[filled])
