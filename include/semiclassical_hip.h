@@ -521,6 +521,19 @@ int sc_wm_pair_sum(const double *qp, const double *coef, const double *cqq, cons
  * elog[2] > 1e-2 Hartree the next time it synchronises. */
 int sc_energy_guard(const double *energy_partials, int32_t n_blocks, double n_traj, double *elog, void *stream);
 
+/* Per-trajectory symplecticity of the monodromy matrix M = [[Mqq, Mqp], [Mpq, Mpp]]: an exact flow has M^T J M = J, the fixed RK4
+ * step only nearly (the reference has no such check).  With A = Mqq, B = Mqp, C = Mpq, D = Mpp (Cartesian
+ * blocks) the three independent blocks of M^T J M - J are
+ *     E1 = A^T C - C^T A,    E2 = A^T D - C^T B - 1,    E3 = B^T D - D^T B,
+ * taken in the scaled canonical coordinates q~_a = scale_a q_a, p~_a = p_a / scale_a (scale: [D] positive, NULL = ones):
+ *     E1~_ab = E1_ab / (scale_a scale_b),   E2~_ab = E2_ab scale_b / scale_a,   E3~_ab = E3_ab scale_a scale_b.
+ *   dev [n][3] = max_ab |E1~|, max_ab |E2~|, max_ab |E3~| per trajectory; the trajectory's deviation is the largest of the three.
+ *                A trajectory with a non-finite element in any of its four blocks reports +inf in all three.
+ * Reads st->mono in the storage order st->mono_layout says (SC_MONO_ROWMAJOR: 1 <= D <= 510; SC_MONO_TILED16: D <= 64) and
+ * never converts or writes it.  No atomics, fixed order of operations: the same bits in every run.  D <= 16 runs on the vector
+ * ALUs (one trajectory per 16 lanes), larger D on the FP64 matrix cores (one workgroup per trajectory at a time). */
+int sc_symplectic_deviation(const sc_state *st, const double *scale, double *dev, void *stream);
+
 /* ---- multi-GPU flush -------------------------------------------------------------------------
  * Trajectories shard over the GPUs of a node, one process per GPU; every term of C_auto / k_ic already carries the weight
  * 1/(N_total P(q_i, p_i)) (propagators.py:837, 909), so the functions of the whole ensemble are the plain SUM of the

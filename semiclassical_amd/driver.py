@@ -136,7 +136,10 @@ class CorrelationStore(object):
 
     BLOCK_KEYS = ('autocorrelation_blocks', 'ic_correlation_blocks', 'block_trajectories')
 
-    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None):
+    SYMPLECTICITY_KEYS = ('symplecticity_steps', 'symplecticity_max', 'symplecticity_mean', 'symplecticity_exceeding',
+                          'symplecticity_tolerance')
+
+    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None):
         """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
         per-sample second moments (rows (S_rr, S_ii, S_ri) times the batch size, phase applied) of the batch, folded the same
         way; the standard errors of the pooled means follow from them.  Files and batches that do not both carry them lose
@@ -144,7 +147,11 @@ class CorrelationStore(object):
         ``blocks``: (C_blocks, k_blocks, counts) -- the block sums (nt, B) of the batch (phase applied; their sum over the blocks is
         the batch mean) and the trajectories per block (B,).  The sums are folded with the same weights as the means, so that the
         stored blocks keep adding up to the stored means, and the counts add: block b of the file is block b of every batch,
-        pooled.  The same rule as for the second moments drops the block keys."""
+        pooled.  The same rule as for the second moments drops the block keys.
+        ``symplecticity``: the record of propagate_batch's symplecticity checks ('steps', 'max', 'mean' per check and, with a
+        tolerance, 'exceeding' and 'tolerance').  Over batches the maxima pool as maxima, the means with the weights of the
+        correlation functions, the counts add.  Files and batches that do not both carry the keys, or that differ in the steps
+        checked or in the tolerance, lose them (same rule again)."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
@@ -178,11 +185,40 @@ class CorrelationStore(object):
                            "the stored trajectories have no blocks, or another number of them")
             for key in self.BLOCK_KEYS:
                 stored.pop(key, None)
+        have_checks = 'symplecticity_steps' in stored
+        if symplecticity is not None and (done == 0 or (have_checks and self._same_checks(stored, symplecticity))):
+            pool = have_checks and done > 0
+            if not pool:
+                for key in self.SYMPLECTICITY_KEYS:
+                    stored.pop(key, None)
+            new_max, new_mean = (np.asarray(symplecticity[key], dtype=np.float64) for key in ('max', 'mean'))
+            stored['symplecticity_steps'] = np.asarray(symplecticity['steps'], dtype=np.int64)
+            stored['symplecticity_max'] = np.maximum(stored['symplecticity_max'], new_max) if pool else new_max
+            stored['symplecticity_mean'] = (ntraj * new_mean + done * stored['symplecticity_mean']) / total if pool else new_mean
+            if 'tolerance' in symplecticity:
+                counts = np.asarray(symplecticity['exceeding'], dtype=np.int64)
+                stored['symplecticity_exceeding'] = stored['symplecticity_exceeding'] + counts if pool else counts
+                stored['symplecticity_tolerance'] = float(symplecticity['tolerance'])
+        elif have_checks or symplecticity is not None:
+            logger.warning("symplecticity checks dropped from %s: %s", self.path,
+                           "this task does not make them (\"check_symplecticity_every\": k)" if symplecticity is None else
+                           "the stored trajectories have none, or were checked at other steps or against another tolerance")
+            for key in self.SYMPLECTICITY_KEYS:
+                stored.pop(key, None)
         stored.pop('ic_rate', None)          # a rate computed from the old correlation function is stale now
         stored.pop('ic_rate_error', None)
         logger.info(f"<phi(0)|phi(0)>= {stored['autocorrelation'][0]}")
         assert abs(stored['autocorrelation'][0] - 1.0) < 1.0e-3
         np.savez(self.path, **stored)
+
+    @staticmethod
+    def _same_checks(stored, symplecticity):
+        """the stored symplecticity checks were made at the same steps and against the same tolerance (or none) as the new ones"""
+        if not np.array_equal(stored['symplecticity_steps'], np.asarray(symplecticity['steps'])):
+            return False
+        if ('symplecticity_tolerance' in stored) != ('tolerance' in symplecticity):
+            return False
+        return 'tolerance' not in symplecticity or float(stored['symplecticity_tolerance']) == float(symplecticity['tolerance'])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -197,8 +233,20 @@ def make_propagator(task, Gamma_0, device):
     return propagators.HermanKlukPropagator(Gamma_0, Gamma_0, device=device)
 
 
+def _check_symplecticity(propagator, step, time, tolerance, log):
+    """one symplecticity check of the batch: (step, max, mean, trajectories above the tolerance) -- one host transfer"""
+    eps = propagator.symplectic_deviation()
+    stats = [eps.max(), eps.mean()] + ([(eps > tolerance).sum().to(eps.dtype)] if tolerance is not None else [])
+    largest, mean, *above = torch.stack(stats).tolist()
+    exceeding = int(above[0]) if above else None
+    if log:
+        tail = "" if exceeding is None else f"  above {tolerance:g}: {exceeding} of {propagator.ntraj}"
+        logger.info(f" time/fs= {time * units.autime_to_fs}  symplecticity max= {largest:9.3e}  mean= {mean:9.3e}{tail}")
+    return step, largest, mean, exceeding
+
+
 def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False,
-                    error_blocks=0):
+                    error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None):
     """C_auto(t), k_ic(t) of one batch of trajectories: the device loop leaves the raw per-step sums in a device buffer,
     ``flush`` (None on a single rank) adds the buffers of all ranks -- ONE all-reduce per batch, SURVEY 8e -- and the host
     applies the dynamical phase.  ``norm_every`` > 0 logs the wavefunction norm (the O(n^2) convergence diagnostic of
@@ -207,25 +255,37 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     second moments (M_C, M_k) of the batch, (nt, 3) each (see CorrelationStore.add_batch), flushed in the same collective.
     ``error_blocks`` = B > 0: the last element of the result is (C_blocks, k_blocks, counts), the block sums (nt, B) of the batch
     with the phase applied and the trajectories per block (every rank partitions ITS trajectories by their local index; sums and
-    counts are added over the ranks in the same collective)."""
+    counts are added over the ranks in the same collective).
+    ``symplecticity_every`` = k > 0 cuts the device loop at every k-th step as well and checks the symplecticity of every
+    trajectory's monodromy matrix there (propagator.symplectic_deviation, this rank's trajectories only); the result then ends
+    with one more element, a dict with 'steps', 'max' and 'mean' of the deviation per check and, with a
+    ``symplecticity_tolerance``, 'exceeding' (trajectories above it) and 'tolerance'.  Nothing else of the result changes."""
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
     moments = torch.zeros((nt, 6), dtype=torch.float64, device=propagator.device) if errors else None
     blocks = counts = None
     if error_blocks:
         blocks = torch.zeros((nt, error_blocks, 4), dtype=torch.float64, device=propagator.device)
         counts = torch.from_numpy(propagator.block_counts(propagator.ntraj, error_blocks)).to(torch.float64)
-    length = norm_every if norm_every > 0 else nt
-    pieces = []
-    for first in range(0, nt, length):
-        if norm_every > 0:
+    # the device loop is cut at the multiples of either diagnostic's period
+    cuts = sorted({0} | {s for every in (norm_every, symplecticity_every) if every > 0 for s in range(0, nt, every)}) if nt > 0 else []
+    pieces, checks = [], []
+    for first, stop in zip(cuts, cuts[1:] + [nt]):
+        if norm_every > 0 and first % norm_every == 0:
             norm = propagator.norm(across_ranks=across_ranks)
             if log:
                 logger.info(f" time/fs= {times[first] * units.autime_to_fs}  norm= {norm:9.6f}")
-        count = min(length, nt - first)
+        if symplecticity_every > 0 and first % symplecticity_every == 0:
+            checks.append(_check_symplecticity(propagator, first, times[first], symplecticity_tolerance, log))
+        count = stop - first
         pieces.append((first, count, propagator.t))
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
                        moments=None if moments is None else moments[first:first + count],
                        blocks=None if blocks is None else blocks[first:first + count])
+    if symplecticity_every > 0 and pieces:
+        # The clock of a piece is t0 + (dt + dt + ...), which differs from the uncut loop's 0 + dt + dt + ... in the last bits, and
+        # with it the dynamical phase.  The check must leave every bit of the correlation functions as it is: the phase is taken
+        # on the grid of the uncut loop (calc_norm_every alone keeps the grid it always had).
+        pieces = [(0, nt, pieces[0][2])]
     if flush is not None:
         if blocks is not None:
             flush(slots, moments, blocks, counts)
@@ -238,6 +298,12 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     if blocks is not None:
         parts = [propagator.finalize_blocks(blocks[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
         tail = (tuple(np.concatenate(part) for part in zip(*parts)) + (np.rint(counts.numpy()).astype(np.int64),),)
+    if symplecticity_every > 0:
+        steps, largest, mean, exceeding = zip(*checks)
+        record = {'steps': np.asarray(steps, dtype=np.int64), 'max': np.asarray(largest), 'mean': np.asarray(mean)}
+        if symplecticity_tolerance is not None:
+            record.update(exceeding=np.asarray(exceeding, dtype=np.int64), tolerance=float(symplecticity_tolerance))
+        tail = tail + (record,)
     if moments is None:
         parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
                  for first, count, t0 in pieces]
@@ -262,6 +328,16 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     if comm is not None:
         rank, world = comm.rank, comm.world
     writer = rank == 0
+    # per-trajectory symplecticity of the monodromy matrices at every k-th step (keys the reference does not have), 0 = off
+    check_every = task.get('check_symplecticity_every', 0) or 0
+    tolerance = task.get('symplecticity_tolerance', None)
+    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 0:
+        raise ConfigurationError(f"'check_symplecticity_every' should be a non-negative integer, got {check_every!r}")
+    if tolerance is not None and (isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not tolerance > 0):
+        raise ConfigurationError(f"'symplecticity_tolerance' should be a positive number, got {tolerance!r}")
+    if check_every and world > 1:
+        raise ConfigurationError("'check_symplecticity_every' is not available with more than one rank: the maximum over the "
+                                 "trajectories does not fit the one sum all-reduce per batch")
     setup = build_problem(task)
 
     dt = task['time_step_fs'] / units.autime_to_fs
@@ -325,13 +401,17 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         if error_blocks and not hostmath.valid_error_blocks(error_blocks):
             raise ConfigurationError(f"'error_blocks' should be a power of two in 2 ... 64 (or 0), got {error_blocks}")
         out = propagate_batch(propagator, setup, dt, nt, times, norm_every=task.get('calc_norm_every', 0), flush=flush,
-                              across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks)
+                              across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks,
+                              symplecticity_every=check_every, symplecticity_tolerance=tolerance)
+        checks = None
+        if check_every:
+            out, checks = out[:-1], out[-1]
         autocorrelation, ic_correlation = out[:2]
         assert not np.isnan(autocorrelation).any(), f"encountered NaN's in autocorrelation : {autocorrelation}"
         assert not np.isnan(ic_correlation).any(), f"encountered NaN's in IC correlation : {ic_correlation}"
         if writer:
             store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:4] if errors else None,
-                            blocks=out[-1] if error_blocks else None)
+                            blocks=out[-1] if error_blocks else None, symplecticity=checks)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -776,14 +776,15 @@ class HermanKlukPropagator(object):
         cache[key] = hit
         return hit
 
-    def _to_normal_modes(self, modal, forward):
-        """monodromy blocks <-> normal-mode coordinates, in place: Mqq~ = A^-1 Mqq A, Mqp~ = A^-1 Mqp B, Mpq~ = B^-1 Mpq A, Mpp~ = B^-1 Mpp B"""
+    def _to_normal_modes(self, modal, forward, state=None):
+        """monodromy blocks <-> normal-mode coordinates, in place: Mqq~ = A^-1 Mqq A, Mqp~ = A^-1 Mqp B, Mpq~ = B^-1 Mpq A, Mpp~ = B^-1 Mpp B
+        (``state``: a copy of the engine state whose ``mono`` points elsewhere; default the state itself)"""
         if "stacks" not in modal:
             A, B, Ai, Bi = modal["A"], modal["B"], modal["Ainv"], modal["Binv"]
             modal["stacks"] = {True: (torch.stack((Ai, Ai, Bi, Bi)).contiguous(), torch.stack((A, B, A, B)).contiguous()),
                                False: (torch.stack((A, A, B, B)).contiguous(), torch.stack((Ai, Bi, Ai, Bi)).contiguous())}
         left, right = modal["stacks"][forward]
-        check(lib.sc_mono_similarity(self._state, ptr(left), ptr(right), self._stream()))
+        check(lib.sc_mono_similarity(self._state if state is None else state, ptr(left), ptr(right), self._stream()))
 
     # step() / run() with a constant dense Hessian and these D take the normal-mode step kernel (sc_hk_step_modal)
     modal_step_dims = (17, 64)
@@ -1057,6 +1058,42 @@ class HermanKlukPropagator(object):
         self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
         self._leave_modal()
         return tuple(self._mono[:, k].permute(1, 2, 0) for k in range(4))
+
+    def symplectic_deviation(self, scale=None, per_block=False):
+        """Distance of every trajectory's monodromy matrix from the symplectic condition M^T J M = J (not in the reference;
+        DESIGN.md section 4.10): the integration error of the fixed RK4 step, trajectory by trajectory.
+
+        Returns a device tensor (n,), the largest element of the three blocks E1 = Mqq^T Mpq - Mpq^T Mqq,
+        E2 = Mqq^T Mpp - Mpq^T Mqp - 1, E3 = Mqp^T Mpp - Mpp^T Mqp in the scaled coordinates q_a sigma_a, p_a / sigma_a -- or, with
+        ``per_block``, the three maxima (n, 3).  ``scale`` = sigma, a positive vector of length D; the default sqrt(diag Gamma_t),
+        the width of the propagated Gaussians, makes all three blocks of a harmonic mode O(1).  A trajectory with a non-finite
+        monodromy element reports +inf.  No host synchronisation; the state (storage order and basis of the blocks included) is not
+        changed: the steps that follow give the bits they would have given without the check."""
+        default = scale is None
+        scale = self.__dict__.get("_width_scale") if default else torch.as_tensor(scale, dtype=F64)
+        if scale is None:
+            scale = torch.sqrt(torch.diagonal(self._Gt))
+        if scale.shape != (self.dim,):
+            raise ValueError(f"scale should have shape ({self.dim},), got {tuple(scale.shape)}")
+        if scale.device.type == "cpu" and not bool(((scale > 0) & torch.isfinite(scale)).all()):
+            raise ValueError("scale has to be positive and finite (a mode of zero width needs an explicit scale)")
+        scale = scale.to(self.device).contiguous()
+        if default:
+            self._width_scale = scale     # Gamma_t is fixed at construction: uploaded once
+        self._sync_dense_mono()           # fold in the diagonals the separable shortcut advanced
+        state = self._state               # the storage order stays what it is: the kernels read either
+        if self._modal_basis is not None:
+            # Blocks in normal-mode coordinates (constant dense Hessian): the check needs the Cartesian ones, but transforming the
+            # state back and forth would change the last bits of every later step.  It looks at a Cartesian COPY (4 D^2 doubles
+            # per trajectory for the duration of the call) and leaves the state in its basis.
+            cartesian = self._mono.clone()
+            state = sc_state.from_buffer_copy(self._state)
+            state.mono = cartesian.data_ptr()
+            self._to_normal_modes(self._modal_basis, forward=False, state=state)
+        dev = torch.empty((self.ntraj, 3), dtype=F64, device=self.device)
+        with self._timed("symplectic_deviation"):
+            check(lib.sc_symplectic_deviation(state, ptr(scale), ptr(dev), self._stream()))
+        return dev if per_block else dev.max(dim=1).values
 
     def semiclassical_prefactor(self):
         return self._sgn * torch.sqrt(self._c2)
