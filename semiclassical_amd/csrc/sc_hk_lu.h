@@ -53,6 +53,9 @@ struct PivotRecord {        // published by the owner of row k together with the
 // row: DPP row_newbcast (no LDS traffic; 64-bit DPP moves exist on gfx90a+ exactly for this control).  The lane is
 // an immediate of the instruction, so there are 16 leaves of 2N moves each and a computed jump (s_setpc_b64) to
 // the leaf of pl; a leaf is 2N*8 + 4 bytes (s_branch to the end).
+// (Measured and rejected: the broadcast fused into the multiply-adds, v_fmac_f64_dpp acc, m[ra][KB], -+r row_newbcast:pl, with the
+// leaves holding the rank-1 update itself -- 320 instructions less per wave and matrix, but 13 KB more code per sub-step in leaves that
+// are all touched once per block, and no faster at any D: docs/NOTEBOOK.md section 9.1.)
 #define SC_DPP_MOV(o, i, P) "v_mov_b64_dpp %[" #o "], %[" #i "] row_newbcast:" #P " row_mask:0xf bank_mask:0xf\n\t"
 #define SC_LEAF1(P) SC_DPP_MOV(ox0, ix0, P) SC_DPP_MOV(oy0, iy0, P) "s_branch .Lend_%=\n\t"
 #define SC_LEAF2(P) SC_DPP_MOV(ox0, ix0, P) SC_DPP_MOV(oy0, iy0, P) SC_DPP_MOV(ox1, ix1, P) SC_DPP_MOV(oy1, iy1, P) \
@@ -206,6 +209,26 @@ __device__ __forceinline__ void publish_pivot_row(const cplx (&m)[NR][NR], cplx 
 // whose row lies beyond D are skipped.  The order in which rows are eliminated does not change the determinant.
 __device__ __forceinline__ bool pivot_step_valid(int kt, int nk) { return 4 * (kt & 3) + (kt >> 2) < nk; }
 
+// SC_LU_PEEL_LAST: the LAST pivot step of a full block KB < NR - 1 updates the trailing (N-1) x (N-1) row / column slots only -- row
+// slot KB and column slot KB are never read again, and nobody publishes behind it.  The step is peeled off the loop statically (its
+// leaf set of N - 1 column entries sits behind the loop, the loop itself is unchanged).
+#ifndef SC_LU_PEEL_LAST
+#define SC_LU_PEEL_LAST 1
+#endif
+// pivot-column entries of the row slots BELOW slot KB only
+template <int NR, int KB>
+__device__ __forceinline__ void column_fetch_below(const cplx (&m)[NR][NR], cplx (&c)[NR], int pl) {
+    pl = __builtin_amdgcn_readfirstlane(pl);
+    if constexpr (NR - KB == 2) column_fetch_n(pl, m[KB + 1][KB], c[KB + 1]);
+    if constexpr (NR - KB == 3) column_fetch_n(pl, m[KB + 1][KB], m[KB + 2][KB], c[KB + 1], c[KB + 2]);
+    if constexpr (NR - KB == 4) column_fetch_n(pl, m[KB + 1][KB], m[KB + 2][KB], m[KB + 3][KB], c[KB + 1], c[KB + 2], c[KB + 3]);
+    if constexpr (NR - KB == 5)
+        column_fetch_n(pl, m[KB + 1][KB], m[KB + 2][KB], m[KB + 3][KB], m[KB + 4][KB], c[KB + 1], c[KB + 2], c[KB + 3], c[KB + 4]);
+    if constexpr (NR - KB == 6)
+        column_fetch_n(pl, m[KB + 1][KB], m[KB + 2][KB], m[KB + 3][KB], m[KB + 4][KB], m[KB + 5][KB], c[KB + 1], c[KB + 2], c[KB + 3],
+                       c[KB + 4], c[KB + 5]);
+}
+
 // `tid` = index of the thread inside its 256-thread elimination group (= threadIdx.x when the group is the workgroup),
 // `barrier()` synchronises the four wavefronts of the group.
 // `detbuf`: the 16 NR signed pivots in LDS (see publish_pivot_row), all 1 before block 0.
@@ -221,7 +244,8 @@ __device__ __forceinline__ void eliminate_block(cplx (&m)[NR][NR], cplx *detbuf,
     bool live = FULL ? true : 16 * KB + tj < D;
     barrier();
     if (ti == 0) publish_pivot_row<NR, KB, RW>(m, detbuf, live, 0, seq, rowbuf, pivrec, weak, tid);
-    for (int kt = 0; kt < 16; ++kt) {
+    constexpr bool PEEL = SC_LU_PEEL_LAST != 0 && FULL;
+    for (int kt = 0; kt < (PEEL ? 15 : 16); ++kt) {
         if (!FULL && !pivot_step_valid(kt, nk)) continue;
         int next = kt + 1;
         if (!FULL) while (next < 16 && !pivot_step_valid(next, nk)) ++next;
@@ -255,6 +279,28 @@ __device__ __forceinline__ void eliminate_block(cplx (&m)[NR][NR], cplx *detbuf,
         for (int ra = KB + 1; ra < NR; ++ra) {
 #pragma unroll
             for (int rb = KB; rb < NR; ++rb) m[ra][rb] = c_fnma(c[ra], r[rb], m[ra][rb]);
+        }
+    }
+    if constexpr (PEEL) {
+        // Step 15 of a full block: only the trailing slots are read again.  The poll is the loop's (same tag word, same compiler
+        // fences around the speculative row reads) and has to stay in step with it; there is no `next` owner and no LU_PIVOT_CLOCK
+        // stamp here because nobody publishes behind this step.  c, r and c_fnma are the loop's on the slots that are updated.
+        int tag;
+        cplx r[NR];
+        for (;;) {
+            tag = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&pivrec[15].pad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            __asm__ volatile("" ::: "memory");
+#pragma unroll
+            for (int rb = KB + 1; rb < NR; ++rb) r[rb] = rowbuf[15][16 * rb + tj];
+            __asm__ volatile("" ::: "memory");
+            if ((tag >> 4) == seq) break;
+        }
+        cplx c[NR];
+        column_fetch_below<NR, KB>(m, c, tag & 15);
+#pragma unroll
+        for (int ra = KB + 1; ra < NR; ++ra) {
+#pragma unroll
+            for (int rb = KB + 1; rb < NR; ++rb) m[ra][rb] = c_fnma(c[ra], r[rb], m[ra][rb]);
         }
     }
 }

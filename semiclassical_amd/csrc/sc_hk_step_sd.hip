@@ -26,7 +26,8 @@
 //            by 1/pivot and publishes it through LDS; the pivot-column entries a thread needs sit in its own
 //            16-lane group and are fetched with DPP row_newbcast.  The four waves are NOT barrier-coupled:
 //            consumers poll a tag in the pivot record (see eliminate_block); one barrier in front of the first
-//            block and one behind the last.  Pivot products (with the signs of the column choices) accumulate in
+//            block and one behind the last.  The last pivot step of a full block updates only the trailing slots
+//            (SC_LU_PEEL_LAST, sc_hk_lu.h).  Pivot products (with the signs of the column choices) accumulate in
 //            LDS per row group; thread 0 multiplies them while the others stream the next trajectory.
 //            If the best in-block pivot is more than 16x smaller than the largest live entry of the row, the
 //            trajectory is flagged (sc_state.flags) and its determinant is recomputed by the fully pivoted
@@ -191,7 +192,12 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         const int tj = tl & 15, tjl = tj;
         const int til = (tl >> 6) * 4 + ((tl >> 4) & 3);    // wave w holds rows 4w .. 4w+3 of every 16-row slot
         if (tl == 0) *weak = SC_SD_FORCE_FIXUP;             // 1: variant library that hands every trajectory to the fallback
-        if (tl < 16 * NR) detbuf[par][tl] = c_make(1.0, 0.0);
+        if (tl < 16 * NR) {
+            // formed HERE: hipcc otherwise keeps the constant's four registers live across the whole trajectory loop and spills them
+            double one = 1.0, zero = 0.0;
+            __asm__ volatile("" : "+v"(one), "+v"(zero));
+            detbuf[par][tl] = c_make(one, zero);
+        }
         int drawn = 0;
         if (ks == 0 && cursor && tl == 0) drawn = atomicAdd(cursor, 1);
         const int pk = tl >> 6, pa = tl & 63;               // thread -> (row of P, mode) of st.work
