@@ -240,16 +240,20 @@ int sc_hk_step(const sc_potential *pot, const sc_state *st, const sc_hk_consts *
 
 /* TWO consecutive time steps per visit of a trajectory (round 4): the same arithmetic as two calls of sc_hk_step, for the
  * separable / diagonal-width fast path with 16 < D <= 64 on the tiled storage order (sc_hk_step_multi_supported).  A workgroup
- * streams a trajectory's monodromy blocks, applies step k, stores them, eliminates -- and streams the SAME trajectory again for
- * step k + 1: these loads hit the L2 / memory-side cache instead of HBM (profiles/r4_revisit.txt), one of the four HBM transfers
- * of two time steps is gone.  Results are bit-identical to two sc_hk_step calls (tests/test_hk_multi_gpu.py).  Measured at
- * D = 60, n = 1e5: 4.38 instead of 4.55 ms per step -- the streaming phase alone drops from 4.39 to 2.94 ms per step, but the
- * elimination (FP64 VALU issue) then bounds the kernel at 3.8-4.4 ms (profiles/r4_sd_phases.txt).
+ * streams a trajectory's monodromy blocks M(k), applies step k in registers and eliminates -- for D > 32 WITHOUT storing -- and streams the
+ * SAME blocks again: these loads hit the L2 / memory-side cache instead of HBM (profiles/pair_nostore_revisit.txt); it applies
+ * step k and then step k + 1 (the same fma sequence: the bits of M(k+1) are those sc_hk_step would have stored), stores M(k+2)
+ * and eliminates.  Two of the four HBM transfers of two time steps are gone.  Between the two sub-steps, and until the stores of
+ * the second one, the blocks in memory are those of the visit's START, M(k): M(k+1) never exists in memory (D <= 32: the first
+ * sub-step stores M(k+1) and the second reloads it, as in round 4; callers must not rely on either).  Results are
+ * bit-identical to two sc_hk_step calls (tests/test_hk_multi_gpu.py, tests/test_pair_no_mid_store_gpu.py).  Measured at
+ * D = 60, n = 1e5 in round 4, with the intermediate store: 4.38 instead of 4.55 ms per step -- the elimination (FP64 VALU issue)
+ * bounds the kernel, not the streaming phase (profiles/r4_sd_phases.txt); without the store: docs/NOTEBOOK.md section 9.2.
  *   ms->work    [2][n][4][D]   row propagators of both sub-steps (scratch)
  *   ms->qp_mid  [n][2D], act_mid [n], c2_mid [n] complex, sgn_mid [n]: the state BETWEEN the two steps -- what sc_hk_correlate of
  *               the second time step reads (pass an sc_state whose qp / act / c2 / sgn point to them)
  *   ms->unrepaired   one int32 on the device, zeroed by the caller.  The fix-up of a weak in-block pivot (sc_state.flags) needs
- *               the blocks the determinant belongs to; for the FIRST sub-step they have moved on.  The kernel counts such
+ *               the blocks the determinant belongs to; those of the FIRST sub-step are not in memory (any more).  The kernel counts such
  *               determinants here: non-zero after the call = the intermediate determinants (and everything derived from them)
  *               are not reliable, redo the two steps from a saved state with sc_hk_step.  Monodromy blocks that are
  *               diagonal (separable potential from M(0) = 1) cannot have weak pivots; HermanKlukPropagator.run() takes this

@@ -59,11 +59,17 @@
 #ifndef SC_SD_LOAD_AUX
 #define SC_SD_LOAD_AUX 2
 #endif
-#ifndef SC_SD_MULTI_LOAD_AUX            // first sub-step of a multi-step visit
+#ifndef SC_SD_MULTI_LOAD_AUX            // first sub-step of a multi-step visit whose intermediate sub-steps store their blocks
 #define SC_SD_MULTI_LOAD_AUX 2
 #endif
-#ifndef SC_SD_MULTI_MID_AUX             // stores of an intermediate sub-step, loads of the following one
+#ifndef SC_SD_NOSTORE_LOAD_AUX          // ... whose intermediate sub-steps do not: the later sub-steps read the SAME lines again, so the first
+#define SC_SD_NOSTORE_LOAD_AUX 0        // load has to allocate in the L2 / memory-side cache (non-temporal: the re-read comes from HBM)
+#endif
+#ifndef SC_SD_MULTI_MID_AUX             // stores of an intermediate sub-step (where there are any), loads of every later sub-step
 #define SC_SD_MULTI_MID_AUX 0
+#endif
+#ifndef SC_SD_NOSTORE_MIN_NR            // multi-step visits: smallest NR whose intermediate sub-steps store no blocks (see KS > 1 below)
+#define SC_SD_NOSTORE_MIN_NR 3
 #endif
 #ifndef SC_SD_STORE_AUX
 #define SC_SD_STORE_AUX 2
@@ -93,17 +99,22 @@ typedef unsigned int sc_v4u __attribute__((ext_vector_type(4)));
 // the workgroup walks the 4 D^2 doubles of the trajectory linearly -- measured 14 % more streaming bandwidth than the
 // 128-byte row segments of the row-major layout (tools/micro/stream_patterns.hip).
 //
-// KS > 1 (round 4, sc_hk_step_multi): KS consecutive time steps per VISIT of a trajectory.  The blocks are stored after every
-// sub-step as before, but the next sub-step of the same trajectory follows at once, by the same threads at the same addresses:
-// its loads hit the L2 / the 256 MB memory-side cache (1024 workgroups hold 118 MB between two sub-steps) instead of HBM
-// (tools/micro/revisit.hip, profiles/r4_revisit.txt: a second read-modify-write visit costs 1.1 ms instead of 4.6).  The
-// intermediate stores and loads are plain (cacheable), the first load and the last store of a visit non-temporal (the first
-// load plain, the last store plain: same time).  Measured (profiles/r4_sd_phases.txt): WITHOUT the elimination the pair kernel
-// streams at 2.94 ms per step (one step per visit: 4.39); WITH it 4.40 against 4.63 -- in this mode the kernel is bound by the
-// elimination (26-36 us of a workgroup's 39-50 us per item; FP64 VALU issue, 64-71 % busy in the SQ counters), no longer by HBM.
-// Load depth 2 / 1.5, earlier prefetch, wave priority for the owner of the next pivot, an early request of thread 0's previous
-// determinant: each measured, none faster (spills at 128 VGPRs, or no effect).  Row
-// propagators of sub-step ks: M.work[ks][n][4][D] (hk_modes_multi_kernel); determinant and branch sign after sub-step
+// KS > 1 (round 4, sc_hk_step_multi): KS consecutive time steps per VISIT of a trajectory; every sub-step is the one-step kernel's
+// stream-eliminate sequence, the next one follows at once by the same threads at the same addresses.  Two schemes, chosen per NR at
+// compile time (mid_store below; measurements and what else was tried: docs/NOTEBOOK.md sections 9 and 9.2):
+//   NR >= SC_SD_NOSTORE_MIN_NR (D > 32), store-free: only the LAST sub-step of a visit stores the blocks.  An earlier sub-step ks
+//     loads the blocks of the visit's start, applies P(0) .. P(ks) (prop[0..ks], kept in LDS for the whole visit), forms its
+//     prefactor matrix and determinant and stores nothing: nobody outside the kernel reads the blocks between the sub-steps, and
+//     the intermediate store was a full HBM write pass.  The last sub-step loads the SAME blocks again, redoes the earlier
+//     rotations (sep_propagate_row is explicit fma: the bits the earlier sub-step formed), applies its own and stores.  The
+//     re-read follows the first read within one elimination (~30 us; 1024 workgroups hold 118 MB in between), so the first load
+//     of a visit is plain (it has to allocate in the L2 / the 256 MB memory-side cache: profiles/pair_nostore_revisit.txt) and
+//     only the last store is non-temporal.  Until the last sub-step's stores the blocks in memory are those of the visit's start.
+//   NR < SC_SD_NOSTORE_MIN_NR (D <= 32), the scheme of round 4: every sub-step stores; intermediate stores and the loads that
+//     follow them are plain (they meet in the cache), the first load and the last store of a visit non-temporal.  There the kernel
+//     waits for round trips, not for HBM, and the redone rotation is latency it cannot hide (store-free measured 0.6 - 2.6 % slower).
+// Either way the kernel is bound by the elimination (FP64 VALU issue), no longer by HBM.
+// Row propagators of sub-step ks: M.work[ks][n][4][D] (hk_modes_multi_kernel); determinant and branch sign after sub-step
 // ks < KS - 1: M.c2_mid / M.sgn_mid [ks][n], after the last one: the state's own arrays.
 struct MultiArgs {
     const double *work;        // [KS][n][4][D]; KS = 1: unused (st.work)
@@ -131,7 +142,11 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     const int pc_blk = g_sd_clock == nullptr ? -1 : (blockIdx.x == 0 ? 0 : (blockIdx.x == 512 ? 1 : -1));
     int pc_item = 0;
 #endif
-    __shared__ double prop[4 * 64];          // P_a = (p11, p12, p21, p22) of row a
+    // KS > 1: do the intermediate sub-steps of a visit store their blocks (NR < SC_SD_NOSTORE_MIN_NR), or does the last one redo them?
+    constexpr bool mid_store = KS > 1 && NR < SC_SD_NOSTORE_MIN_NR;
+    constexpr int NP = mid_store ? 1 : KS;
+    constexpr int aux_first = KS == 1 ? SC_SD_LOAD_AUX : (mid_store ? SC_SD_MULTI_LOAD_AUX : SC_SD_NOSTORE_LOAD_AUX);   // first load of a visit
+    __shared__ double prop[NP][4 * 64];      // P_a = (p11, p12, p21, p22) of row a; without intermediate stores one set per sub-step of a visit
     __shared__ double scl[4 * 64];           // st, 1/st, si, 1/si
     __shared__ cplx rowbuf[16][64];
     __shared__ PivotRecord pivrec[16];
@@ -141,6 +156,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     __shared__ int weakbuf[2];               // bit 0: weak in-block pivot (-> pivoted fallback), bit 1: zero pivot
     __shared__ int nextbuf[2];               // what thread 0 drew from the trajectory cursor
 
+    static_assert(KS == 1 || !SC_SD_DIRECT_P || NR < SC_SD_NOSTORE_MIN_NR, "a later sub-step of a visit needs the row propagators of the earlier ones (prop[])");
     const int D = A.st.dim, DD = D * D, tid = threadIdx.x;
     constexpr bool do_step = STEP;                   // false: prefactor and tracker initialisation only (t = 0)
     constexpr int NCL_BASE = 16 * (NR - 1);          // first column of the last column tile
@@ -150,7 +166,8 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         if (tid < 16) pivrec[tid].pad = 0;
         if (tid < 2) { nextbuf[tid] = 0; weakbuf[tid] = 0; }      // never read before they are written (RESET BARRIER below); defined anyway
         scl[tid] = st; scl[64 + tid] = 1.0 / st; scl[128 + tid] = si; scl[192 + tid] = 1.0 / si;
-        prop[tid] = 1.0; prop[64 + tid] = 0.0; prop[128 + tid] = 0.0; prop[192 + tid] = 1.0;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) { prop[k][tid] = 1.0; prop[k][64 + tid] = 0.0; prop[k][128 + tid] = 0.0; prop[k][192 + tid] = 1.0; }
     }
     __syncthreads();
 
@@ -179,8 +196,9 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     for (int64_t tr = blockIdx.x; tr < A.st.n; tr = trn) {
       sfor<0, KS>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::value;                 // sub-step of this visit
-        constexpr int aux_load = ks == 0 ? (KS > 1 ? SC_SD_MULTI_LOAD_AUX : SC_SD_LOAD_AUX) : SC_SD_MULTI_MID_AUX;
+        constexpr int aux_load = ks == 0 ? aux_first : SC_SD_MULTI_MID_AUX;
         constexpr int aux_store = ks == KS - 1 ? SC_SD_STORE_AUX : SC_SD_MULTI_MID_AUX;
+        constexpr bool store_blocks = ks == KS - 1 || mid_store; // otherwise an intermediate sub-step leaves the blocks in memory alone
         // what is streamed next: the next sub-step of this trajectory, or the first one of the next trajectory
         constexpr int ksn = ks + 1 < KS ? ks + 1 : 0;
         int *weak = &weakbuf[par];
@@ -268,7 +286,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         };
         auto first_requests = [&](int64_t t, auto ksnc) {    // P_a and row slot 0 of sub-step ksnc of trajectory t
             constexpr int k2 = decltype(ksnc)::value;
-            constexpr int aux2 = k2 == 0 ? (KS > 1 ? SC_SD_MULTI_LOAD_AUX : SC_SD_LOAD_AUX) : SC_SD_MULTI_MID_AUX;
+            constexpr int aux2 = k2 == 0 ? aux_first : SC_SD_MULTI_MID_AUX;
             const double *wk = KS > 1 ? MA.work + (int64_t)k2 * A.st.n * 4 * Dl : A.st.work;
             if (!SC_SD_DIRECT_P && do_step && pa < Dl) prv = wk[(t * 4 + pk) * (int64_t)Dl + pa];
             load_slot(std::integral_constant<int, 0>(), t, std::integral_constant<int, aux2>());
@@ -279,8 +297,23 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
             constexpr int ra = decltype(rac)::value;
             const __amdgpu_buffer_rsrc_t rs = resource(tr);
             const int al = (16 * ra + til) & 63;
-            const double p11 = SC_SD_DIRECT_P ? pv[ra & 1][0] : prop[al], p12 = SC_SD_DIRECT_P ? pv[ra & 1][1] : prop[64 + al];
-            const double p21 = SC_SD_DIRECT_P ? pv[ra & 1][2] : prop[128 + al], p22 = SC_SD_DIRECT_P ? pv[ra & 1][3] : prop[192 + al];
+            if constexpr (ks > 0 && !mid_store) {
+                // the blocks in memory are those of the visit's start: redo the earlier sub-steps' rotations first (explicit fma:
+                // the bits those sub-steps formed), all rb of the slot per propagator, so that the four P values share registers
+                sfor<0, ks>([&](auto kpc) {
+                    constexpr int kp = decltype(kpc)::value;
+                    WM_BLOCK {          // a basic block of its own: scheduled together with the rest of the slot it costs 9 spilled registers at NR = 4
+                        const double q11 = prop[kp][al], q12 = prop[kp][64 + al], q21 = prop[kp][128 + al], q22 = prop[kp][192 + al];
+#pragma unroll
+                        for (int rb = 0; rb < NR; ++rb)
+                            sep_propagate_row(q11, q12, q21, q22, raw[ra & 1][0][rb], raw[ra & 1][1][rb], raw[ra & 1][2][rb], raw[ra & 1][3][rb]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+            }
+            constexpr int kq = mid_store ? 0 : ks;
+            const double p11 = SC_SD_DIRECT_P ? pv[ra & 1][0] : prop[kq][al], p12 = SC_SD_DIRECT_P ? pv[ra & 1][1] : prop[kq][64 + al];
+            const double p21 = SC_SD_DIRECT_P ? pv[ra & 1][2] : prop[kq][128 + al], p22 = SC_SD_DIRECT_P ? pv[ra & 1][3] : prop[kq][192 + al];
             const double sta = scl[al], ista = scl[64 + al];
 #pragma unroll
             for (int rb = 0; rb < NR; ++rb) {
@@ -289,7 +322,12 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
                 if (do_step) {
                     sep_propagate_row(p11, p12, p21, p22, mqq, mqp, mpq, mpp);
                     const double out[4] = {mqq, mqp, mpq, mpp};
-                    if constexpr (TILED) {
+                    if constexpr (!store_blocks) {
+                        (void)out; (void)rs; (void)vofs; (void)base; (void)plane;
+                        // no store, no store-data hazard to guard; the elements are still scheduled one by one (hipcc otherwise
+                        // interleaves the four rb of the slot and spills 8 registers at NR = 4)
+                        __builtin_amdgcn_sched_barrier(0);
+                    } else if constexpr (TILED) {
 #pragma unroll
                         for (int pp = 0; pp < 2; ++pp) {
                             sc_v4u v;
@@ -333,9 +371,9 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         if (NR > 1 && SC_SD_DEPTH > 1) load_slot(std::integral_constant<int, (NR > 1 ? 1 : 0)>(), tr, std::integral_constant<int, aux_load>());
         __builtin_amdgcn_sched_barrier(0);
         if (do_step && !SC_SD_DIRECT_P) {
-            // every wave is past the previous trajectory's phase B (the elimination barriers lie in between), so prop
-            // may be overwritten without another barrier
-            if (pa < D) prop[64 * pk + pa] = prv;
+            // every wave is past the previous visit's phase B of this sub-step (the elimination barriers lie in between), so
+            // prop[ks] may be overwritten without another barrier; the sets of the earlier sub-steps of this visit stay
+            if (pa < D) prop[mid_store ? 0 : ks][64 * pk + pa] = prv;
             __syncthreads();
         }
         sfor<0, NR>([&](auto rac) {

@@ -7,6 +7,10 @@
 // Here: the same bytes, the same launch shape (1024 persistent workgroups x 256 threads, grid-stride over the trajectories, 16 B per
 // lane, linear order), K read-modify-write passes over a trajectory back to back before the workgroup moves on -- time per pass for
 // K = 1, 2, 4, with plain and with non-temporal accesses, and with a delay between the passes (the elimination takes ~20 us).
+// Second question (the pair kernel without its intermediate store): the first pass of a visit only READS, the second pass reads the
+// same lines again, modifies and writes them (non-temporal stores, as the kernel's last sub-step).  Is a line that a READ brought in
+// still in the L2 / memory-side cache 30 us and 118 MB later, and does it have to be a plain load?  read_then_rmw below: launch time
+// against one read-modify-write pass (1 read + 1 write from HBM); a missed re-read shows as a second read pass (+ ~1.8 ms).
 // build: hipcc --offload-arch=gfx950 -O3 -o revisit revisit.hip ; run: ./revisit [n] [D]
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -42,6 +46,63 @@ __global__ __launch_bounds__(256, 4) void revisit(double *mono, long n, long uni
             }
         }
     }
+}
+
+// pass 1: loads only (NT1: non-temporal), folded into a value that is stored only if it is NaN (never: keeps the loads alive);
+// DELAY ticks; pass 2: plain loads, the update of revisit<>, non-temporal stores
+template <bool NT1, int DELAY>
+__global__ __launch_bounds__(256, 4) void read_then_rmw(double *mono, long n, long units, double *sink) {
+    for (long tr = blockIdx.x; tr < n; tr += gridDim.x) {
+        d2 *M = (d2 *)mono + tr * units;
+        double acc = 0.0;
+        for (long c0 = 0; c0 < units; c0 += 256 * 8) {
+            d2 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long c = c0 + u * 256 + threadIdx.x;
+                v[u] = c < units ? (NT1 ? __builtin_nontemporal_load(M + c) : M[c]) : (d2){0.0, 0.0};
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += v[u].x + v[u].y;
+        }
+        if (acc != acc) sink[0] = acc;
+        if (DELAY > 0) {
+            const long long t0 = wall_clock64();
+            while (wall_clock64() - t0 < DELAY) __builtin_amdgcn_s_sleep(8);
+        }
+        for (long c0 = 0; c0 < units; c0 += 256 * 8) {
+            d2 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long c = c0 + u * 256 + threadIdx.x;
+                v[u] = c < units ? M[c] : (d2){0.0, 0.0};
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long c = c0 + u * 256 + threadIdx.x;
+                const d2 o = {v[u].x * 1.0000001 + v[u].y * 1e-9, v[u].y * 1.0000001 - v[u].x * 1e-9};
+                if (c < units) __builtin_nontemporal_store(o, M + c);
+            }
+        }
+    }
+}
+
+template <bool NT1, int DELAY>
+static void run_read_then_rmw(double *mono, long n, long units, double *sink, const char *what) {
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    float best = 1e30f;
+    for (int rep = 0; rep < 3; ++rep) {
+        CHECK(hipEventRecord(e0));
+        hipLaunchKernelGGL((read_then_rmw<NT1, DELAY>), dim3(1024), dim3(256), 0, 0, mono, n, units, sink);
+        CHECK(hipEventRecord(e1));
+        CHECK(hipEventSynchronize(e1));
+        float ms;
+        CHECK(hipEventElapsedTime(&ms, e0, e1));
+        if (ms < best) best = ms;
+    }
+    printf("%-64s %8.3f ms per launch  (one pass = %.2f GB; re-read from the cache: 1 read + 1 write from HBM, missed: 2 reads + 1 write)\n",
+           what, best, 16.0 * units * n / 1e9);
 }
 
 template <int K, bool NT, int DELAY>
@@ -100,5 +161,12 @@ int main(int argc, char **argv) {
     run<2, true, 0>(mono, n, units, "non-temporal, passes back to back");
     run<2, true, 2000>(mono, n, units, "non-temporal, 20 us between the passes");
     (void)t1;
+    // read only, then read-modify-write (plain re-read, non-temporal stores); reference: the K = 1 lines above (1 read + 1 write)
+    double *sink;
+    CHECK(hipMalloc(&sink, sizeof(double)));
+    run_read_then_rmw<false, 0>(mono, n, units, sink, "read (plain), then read-modify-write, back to back");
+    run_read_then_rmw<true, 0>(mono, n, units, sink, "read (non-temporal), then read-modify-write, back to back");
+    run_read_then_rmw<false, 3000>(mono, n, units, sink, "read (plain), 30 us, then read-modify-write");
+    run_read_then_rmw<true, 3000>(mono, n, units, sink, "read (non-temporal), 30 us, then read-modify-write");
     return 0;
 }
