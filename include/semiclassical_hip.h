@@ -267,6 +267,24 @@ int sc_hk_step_multi_supported(const sc_potential *pot, const sc_state *st, cons
 int sc_hk_step_multi(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_multi_scratch *ms,
                      double dt, double *energy_partials, void *stream);
 
+/* KS = `ksteps` consecutive time steps per visit of a trajectory, 2 <= ksteps <= 4 (an addition: the ABI number stays): sc_hk_step_multi for a general
+ * number of sub-steps, the same arithmetic as ksteps calls of sc_hk_step.  ksteps = 2 IS sc_hk_step_multi (same kernels).
+ * ksteps = 3, 4 exist for 32 < D <= 64 only (sc_hk_step_visit_supported), in the store-free scheme: sub-step ks loads the blocks
+ * of the visit's start M(k) (the first load allocates in the cache, every later one re-reads the same lines), applies the row
+ * propagators P(0) .. P(ks) one after the other with the explicit fma sequence of sc_hk_step, forms its prefactor matrix and
+ * determinant, and only the LAST sub-step stores: M(k + ksteps).  Per time step 1 / ksteps of a read pass from HBM and
+ * 1 / ksteps of a write pass; until the last sub-step's stores the blocks in memory are M(k).  Bit-identical to ksteps calls
+ * of sc_hk_step (tests/test_visit_steps_gpu.py); measurements: docs/NOTEBOOK.md section 9.3.
+ *   ms->work    [ksteps][n][4][D]
+ *   ms->qp_mid  [ksteps - 1][n][2D], act_mid [ksteps - 1][n], c2_mid [ksteps - 1][n] complex, sgn_mid [ksteps - 1][n]: the
+ *               states after sub-step 0 .. ksteps - 2 (one sc_state view per intermediate state for sc_hk_correlate)
+ *   ms->unrepaired   as for sc_hk_step_multi: counts weak in-block pivots of ALL intermediate sub-steps; the fix-up launch
+ *               repairs the last sub-step's determinant from M(k + ksteps) in memory
+ *   energy_partials [ksteps][sc_step_grid()] (ksteps sc_energy_guard calls). */
+int sc_hk_step_visit_supported(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, int32_t ksteps);
+int sc_hk_step_visit(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_multi_scratch *ms,
+                     double dt, double *energy_partials, int32_t ksteps, void *stream);
+
 /* out[i] = <qp[i] , G_bra | qk,pk,G_ket> for i < n  (complex).  propagators.py:181-240 with a single ket. */
 int sc_overlap(const sc_overlap_consts *oc, const double *qp, int64_t n, double *out, void *stream);
 

@@ -101,6 +101,9 @@ SIGNATURES = {
     "sc_hk_step_multi_supported": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts)]),
     "sc_hk_step_multi": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), P(sc_multi_scratch), C.c_double, c_double_p,
                                    C.c_void_p]),
+    "sc_hk_step_visit_supported": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), C.c_int32]),
+    "sc_hk_step_visit": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), P(sc_multi_scratch), C.c_double, c_double_p,
+                                   C.c_int32, C.c_void_p]),
     "sc_overlap": (C.c_int, [P(sc_overlap_consts), c_double_p, C.c_int64, c_double_p, C.c_void_p]),
     "sc_nac_initial": (C.c_int, [P(sc_nac_consts), c_double_p, C.c_int64, c_double_p, C.c_void_p]),
     "sc_hk_correlate": (C.c_int, [P(sc_state), P(sc_overlap_consts), P(sc_nac_consts), c_double_p, c_double_p,

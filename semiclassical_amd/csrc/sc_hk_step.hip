@@ -323,22 +323,39 @@ extern "C" int sc_hk_step_multi_supported(const sc_potential *pot, const sc_stat
            st->mono_layout == SC_MONO_TILED16 && st->work && st->flags ? 1 : 0;
 }
 
-extern "C" int sc_hk_step_multi(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_multi_scratch *ms,
-                                double dt, double *energy_partials, void *stream) {
-    if (!pot || !st || !hk || !ms) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_step_multi: null argument");
+// KS = `ksteps` time steps per visit: sc_hk_step_multi (`who`, ksteps = 2) and sc_hk_step_visit
+static int hk_step_visit(const char *who, const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_multi_scratch *ms,
+                         double dt, double *energy_partials, int ksteps, void *stream) {
+    if (!pot || !st || !hk || !ms) return sc_fail(SC_ERR_BAD_ARGUMENT, "%s: null argument", who);
     if (!ms->work || !ms->qp_mid || !ms->act_mid || !ms->c2_mid || !ms->sgn_mid || !ms->unrepaired)
-        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_step_multi: null scratch field");
-    if (!sc_hk_step_multi_supported(pot, st, hk))
-        return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_multi: needs a separable potential, diagonal width matrices, 16 < D <= 64, the tiled "
-                       "storage order (sc_mono_convert) and sc_state.work / flags (use sc_hk_step)");
+        return sc_fail(SC_ERR_BAD_ARGUMENT, "%s: null scratch field", who);
+    if (!sc_hk_step_visit_supported(pot, st, hk, ksteps))
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: needs a separable potential, diagonal width matrices, 16 < D <= 64 (more than two steps per "
+                       "visit: 32 < D, at most four), the tiled storage order (sc_mono_convert) and sc_state.work / flags (use sc_hk_step)", who);
     if (st->n <= 0) return SC_OK;
     hipStream_t s = (hipStream_t)stream;
     // flags[n]: trajectories flagged in the LAST sub-step, flags[n + 1]: trajectory cursor of the block kernel
     if (hipMemsetAsync(st->flags + st->n, 0, 2 * sizeof(int32_t), s) != hipSuccess) return sc_check_launch("sc_hk_step_multi (flag counter)");
     const int grid = sc_step_grid(st->n, st->dim);
-    StepArgs a{*pot, *st, *hk, dt, 0, energy_partials, 2 * grid};
-    int rc = sc_launch_step_sd_multi(a, *ms, s);
+    StepArgs a{*pot, *st, *hk, dt, 0, energy_partials, ksteps * grid};
+    int rc = sc_launch_step_sd_multi(a, *ms, ksteps, s);
     if (rc != SC_OK) return rc;
     // weak in-block pivots of the LAST sub-step (normally none): fully pivoted fix-up from the final blocks, as in sc_hk_step
     return sc_hk_step(pot, st, hk, dt, 0x400, nullptr, stream);
+}
+
+extern "C" int sc_hk_step_multi(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_multi_scratch *ms,
+                                double dt, double *energy_partials, void *stream) {
+    return hk_step_visit("sc_hk_step_multi", pot, st, hk, ms, dt, energy_partials, 2, stream);
+}
+
+// ---- two to four time steps per visit (include/semiclassical_hip.h: sc_hk_step_visit) ----
+extern "C" int sc_hk_step_visit_supported(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, int32_t ksteps) {
+    if (ksteps < 2 || ksteps > 4 || !sc_hk_step_multi_supported(pot, st, hk)) return 0;
+    return ksteps == 2 || st->dim > 32 ? 1 : 0;       // more than two: the store-free scheme of 32 < D only
+}
+
+extern "C" int sc_hk_step_visit(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_multi_scratch *ms,
+                                double dt, double *energy_partials, int32_t ksteps, void *stream) {
+    return hk_step_visit("sc_hk_step_visit", pot, st, hk, ms, dt, energy_partials, ksteps, stream);
 }

@@ -99,17 +99,20 @@ typedef unsigned int sc_v4u __attribute__((ext_vector_type(4)));
 // the workgroup walks the 4 D^2 doubles of the trajectory linearly -- measured 14 % more streaming bandwidth than the
 // 128-byte row segments of the row-major layout (tools/micro/stream_patterns.hip).
 //
-// KS > 1 (round 4, sc_hk_step_multi): KS consecutive time steps per VISIT of a trajectory; every sub-step is the one-step kernel's
+// KS > 1 (sc_hk_step_multi: KS = 2; sc_hk_step_visit: KS = 2 .. 4): KS consecutive time steps per VISIT of a trajectory; every sub-step is the one-step kernel's
 // stream-eliminate sequence, the next one follows at once by the same threads at the same addresses.  Two schemes, chosen per NR at
 // compile time (mid_store below; measurements and what else was tried: docs/NOTEBOOK.md sections 9 and 9.2):
 //   NR >= SC_SD_NOSTORE_MIN_NR (D > 32), store-free: only the LAST sub-step of a visit stores the blocks.  An earlier sub-step ks
 //     loads the blocks of the visit's start, applies P(0) .. P(ks) (prop[0..ks], kept in LDS for the whole visit), forms its
 //     prefactor matrix and determinant and stores nothing: nobody outside the kernel reads the blocks between the sub-steps, and
-//     the intermediate store was a full HBM write pass.  The last sub-step loads the SAME blocks again, redoes the earlier
-//     rotations (sep_propagate_row is explicit fma: the bits the earlier sub-step formed), applies its own and stores.  The
-//     re-read follows the first read within one elimination (~30 us; 1024 workgroups hold 118 MB in between), so the first load
-//     of a visit is plain (it has to allocate in the L2 / the 256 MB memory-side cache: profiles/pair_nostore_revisit.txt) and
-//     only the last store is non-temporal.  Until the last sub-step's stores the blocks in memory are those of the visit's start.
+//     the intermediate store was a full HBM write pass.  Every later sub-step loads the SAME blocks again and redoes the earlier
+//     rotations one by one (sep_propagate_row is explicit fma: the bits the earlier sub-steps formed; no composed 2 x 2 products),
+//     the last one applies its own and stores.  The re-reads follow the first read within KS - 1 eliminations (~30 us each; 1024
+//     workgroups hold 118 MB in between), so the first load of a visit is plain (it has to allocate in the L2 / the 256 MB
+//     memory-side cache: profiles/pair_nostore_revisit.txt, profiles/visit_steps_revisit.txt) and only the last store is
+//     non-temporal.  Until the last sub-step's stores the blocks in memory are those of the visit's start.  Per time step the
+//     blocks cross HBM 2 / KS times, and sub-step ks redoes ks rotations: (KS - 1) / 2 per time step on top of its own, in a
+//     kernel bound by FP64 issue -- measured at n = 1e5: KS = 3 is the fastest for every NR >= 3 (docs/NOTEBOOK.md section 9.3).
 //   NR < SC_SD_NOSTORE_MIN_NR (D <= 32), the scheme of round 4: every sub-step stores; intermediate stores and the loads that
 //     follow them are plain (they meet in the cache), the first load and the last store of a visit non-temporal.  There the kernel
 //     waits for round trips, not for HBM, and the redone rotation is latency it cannot hide (store-free measured 0.6 - 2.6 % slower).
@@ -145,6 +148,9 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     // KS > 1: do the intermediate sub-steps of a visit store their blocks (NR < SC_SD_NOSTORE_MIN_NR), or does the last one redo them?
     constexpr bool mid_store = KS > 1 && NR < SC_SD_NOSTORE_MIN_NR;
     constexpr int NP = mid_store ? 1 : KS;
+    // NR = 4 with four sub-steps: P_a requested during the previous elimination is one value too many for 128 registers (hipcc spills it
+    // behind s_waitcnt vmcnt(0) in the middle of the last diagonal block); there it is requested at the top of the sub-step instead
+    constexpr bool late_p = KS >= 4 && NR >= 4;
     constexpr int aux_first = KS == 1 ? SC_SD_LOAD_AUX : (mid_store ? SC_SD_MULTI_LOAD_AUX : SC_SD_NOSTORE_LOAD_AUX);   // first load of a visit
     __shared__ double prop[NP][4 * 64];      // P_a = (p11, p12, p21, p22) of row a; without intermediate stores one set per sub-step of a visit
     __shared__ double scl[4 * 64];           // st, 1/st, si, 1/si
@@ -365,6 +371,9 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         // sched_barrier: the stages are scheduled one by one (hipcc otherwise interleaves the stages of this branch-free
         // block until the raw values of three slots are live at once, and spills)
         SD_TICK(0);
+        if constexpr (late_p) {                          // not requested during the previous elimination (see late_p)
+            if (!first && do_step && pa < Dl) prv = MA.work[(((int64_t)ks * A.st.n + tr) * 4 + pk) * (int64_t)Dl + pa];
+        }
         if (first || !SC_SD_XPREFETCH || NR == 1) first_requests(tr, ksc);
         first = false;
         __builtin_amdgcn_sched_barrier(0);
@@ -414,7 +423,13 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
             if (SC_SD_XPREFETCH && NR > 1 && KB == (NR - SC_SD_XPREFETCH_AHEAD > 1 ? NR - SC_SD_XPREFETCH_AHEAD : 1)) {
                 const int64_t tnext = ks + 1 < KS ? tr : trn;
                 if (tnext < A.st.n) {
-                    first_requests(tnext, std::integral_constant<int, ksn>());
+                    if constexpr (late_p) {         // the row slots only: P_a follows at the top of the sub-step
+                        constexpr int auxn = ksn == 0 ? aux_first : SC_SD_MULTI_MID_AUX;
+                        load_slot(std::integral_constant<int, 0>(), tnext, std::integral_constant<int, auxn>());
+                        if (SC_SD_XPREFETCH2) load_slot(std::integral_constant<int, 1>(), tnext, std::integral_constant<int, auxn>());
+                    } else {
+                        first_requests(tnext, std::integral_constant<int, ksn>());
+                    }
                 } else {                            // nothing follows: end the live ranges of the old values
                     prv = 0.0;
 #pragma unroll
@@ -447,7 +462,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         if (tl < 16) lu_partial_products<NR>(detbuf[par], tl);
         if (ks == KS - 1 && tl == 0 && (*weak & 1) && A.st.flags && !skip_lu) {
             // c2 / sgn are left to the fully pivoted fallback, which tracks against the state's c2 / sgn: after an
-            // intermediate sub-step those are two steps old, so hand it this sub-step's predecessor (c2_mid / sgn_mid)
+            // intermediate sub-step those are KS steps old, so hand it this sub-step's predecessor (c2_mid / sgn_mid)
             if (KS > 1) {
                 c2[tr] = *c2_in;
                 A.st.sgn[tr] = *sg_in;
@@ -767,9 +782,31 @@ int sc_launch_step_sd(const StepArgs &a, hipStream_t s) {
     return sc_check_launch("sc_hk_step (separable/diagonal fast path)");
 }
 
-// TWO time steps per visit (sc_hk_step_multi; the caller has validated: separable potential, diagonal widths, 16 < D <= 64, tiled
-// blocks, flags present): hk_modes_multi_kernel<2>, then the block kernel with two sub-steps per trajectory.
-int sc_launch_step_sd_multi(const StepArgs &a, const sc_multi_scratch &ms, hipStream_t s) {
+// KS = 3, 4 time steps per visit (sc_hk_step_visit; validated by the caller as for sc_launch_step_sd_multi, and 32 < D <= 64: the
+// store-free scheme): hk_modes_multi_kernel<KS>, then the block kernel with KS sub-steps per trajectory.
+template <int KS>
+static int launch_step_sd_visit(const StepArgs &a, const sc_multi_scratch &ms, hipStream_t s) {
+    const int D = a.st.dim, nr = (D + 15) / 16, grid = sc_step_grid(a.st.n, D);
+    ModesMultiArgs mm{ms.work, ms.qp_mid, ms.act_mid};
+    hipLaunchKernelGGL(hk_modes_multi_kernel<KS>, dim3(grid), dim3(256), 0, s, a, mm);
+    int rc = sc_check_launch("sc_hk_step_visit (modes)");
+    if (rc) return rc;
+    MultiArgs ma{ms.work, ms.c2_mid, ms.sgn_mid, ms.unrepaired};
+    switch (nr) {
+        case 3: hipLaunchKernelGGL((hk_step_sd_kernel<3, 4, true, true, KS>), dim3(grid), dim3(256), 0, s, a, ma); break;
+        case 4: hipLaunchKernelGGL((hk_step_sd_kernel<4, 4, true, true, KS>), dim3(grid), dim3(256), 0, s, a, ma); break;
+        default: return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_visit: %d steps per visit at D = %d", KS, D);
+    }
+    return sc_check_launch("sc_hk_step_visit (KS steps per visit)");
+}
+
+// KS time steps per visit (sc_hk_step_multi: two, sc_hk_step_visit: two to four; the caller has validated: separable potential,
+// diagonal widths, 16 < D <= 64, tiled blocks, flags present): hk_modes_multi_kernel<KS>, then the block kernel with KS sub-steps
+// per trajectory.
+int sc_launch_step_sd_multi(const StepArgs &a, const sc_multi_scratch &ms, int ksteps, hipStream_t s) {
+    if (ksteps == 3) return launch_step_sd_visit<3>(a, ms, s);
+    if (ksteps == 4) return launch_step_sd_visit<4>(a, ms, s);
+    if (ksteps != 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_visit: %d steps per visit", ksteps);
     const int D = a.st.dim, nr = (D + 15) / 16, grid = sc_step_grid(a.st.n, D);
     ModesMultiArgs mm{ms.work, ms.qp_mid, ms.act_mid};
     hipLaunchKernelGGL(hk_modes_multi_kernel<2>, dim3(grid), dim3(256), 0, s, a, mm);

@@ -490,7 +490,7 @@ class HermanKlukPropagator(object):
 
     def step_kernel_times_ms(self):
         """duration PER TIME STEP of the step-kernel launches recorded while ``profile_step_kernel`` was set (a launch of the
-        two-steps-per-visit path counts for two)"""
+        steps-per-visit paths counts for its number of time steps)"""
         torch.cuda.current_stream(self.device).synchronize()
         return [e0.elapsed_time(e1) / steps for e0, e1, steps in self.__dict__.get("_step_events", [])]
 
@@ -658,7 +658,10 @@ class HermanKlukPropagator(object):
 
         Separable potentials with diagonal width matrices and 16 < D <= 64 advance TWO time steps per launch while the monodromy
         blocks are known to be diagonal (``sc_hk_step_multi``: the second step's reads come from the memory-side cache; results
-        bit-identical to one launch per step; ``pair_steps = False`` switches it off).
+        bit-identical to one launch per step; ``pair_steps = False`` switches it off).  For 32 < D <= 64 and an ensemble whose
+        blocks exceed the memory-side cache (``visit_min_bytes``) a visit takes up to ``visit_steps`` (three; at most four) time steps
+        (``sc_hk_step_visit``: one read and one write of the blocks per visit), the last ``nt mod visit_steps`` steps a shorter
+        visit or a single step; ``visit_steps = 2`` is the launch sequence of pairs.  Same bits either way.
 
         Standard errors: ``moments`` (a contiguous float64 device tensor (>= nt, 6), parallel to ``slots``) receives per step the
         sums over the trajectories of (Re c_i)^2, (Im c_i)^2, Re c_i Im c_i of the C_auto terms, then the same of the k_ic terms,
@@ -706,10 +709,12 @@ class HermanKlukPropagator(object):
             self._run_graph(potential, dt, nt, desc, slots, mbase, brow(0))
         else:
             pairs = fused and nt >= 2 and self._multi_applies(desc)
+            kmax = self._visit_steps_for(desc) if pairs else 1
             k = 0
             while k < nt:
                 self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k], mom_ptr=mrow(k), blk=brow(k))
-                if pairs and k + 1 < nt:
+                ks = min(kmax, nt - k) if pairs else 1       # never a visit longer than the steps left
+                if ks == 2:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
@@ -718,6 +723,16 @@ class HermanKlukPropagator(object):
                     self.t += dt
                     self.t += dt
                     k += 2
+                elif ks > 2:
+                    # three or four (sc_hk_step_visit): the blocks leave and reach HBM once per visit; row k + j of the slots, moments
+                    # and blocks comes from the j-th intermediate state
+                    self._launch_step_visit(desc, dt, ks)
+                    for j in range(1, ks):
+                        self._launch_correlate(base + 40 * (k + j), per_trajectory=False, state=self._multi["states_mid"][j - 1],
+                                               mom_ptr=mrow(k + j), blk=brow(k + j))
+                    for _ in range(ks):
+                        self.t += dt
+                    k += ks
                 else:
                     self._launch_step(potential, dt, desc=desc, remembered=True)
                     self.t += dt
@@ -879,6 +894,13 @@ class HermanKlukPropagator(object):
 
     _multi_ok = True                # WM needs its own kernel after every single step
     pair_steps = True               # run(): two time steps per visit where sc_hk_step_multi applies (False: one launch per step)
+    # run(): the MAXIMUM number of time steps per visit (sc_hk_step_visit; 2 = pairs only, the behaviour before visits; at most 4).
+    # Three is what was measured to be fastest at n = 1e5 for every 32 < D <= 64 (four is slower than three: every further sub-step
+    # redoes one more rotation and the kernel is bound by FP64 issue; docs/NOTEBOOK.md section 9.3); D <= 32 has no kernel for more
+    # than two.  Longer visits are taken only where the monodromy blocks of the ensemble are larger than the 256 MB memory-side
+    # cache: the gain is HBM traffic, and a smaller state never leaves the cache between two steps
+    visit_steps = 3
+    visit_min_bytes = 256 << 20
 
     def _multi_applies(self, desc):
         """two time steps per visit (sc_hk_step_multi): separable potential, diagonal widths, 16 < D <= 64 (the tiled fast path),
@@ -890,38 +912,73 @@ class HermanKlukPropagator(object):
         probe.mono_layout = _lib.SC_MONO_TILED16
         return bool(lib.sc_hk_step_multi_supported(desc, probe, self._hk))
 
-    def _launch_step_pair(self, desc, dt):
+    def _visit_steps_for(self, desc):
+        """largest number of time steps per visit run() may take: ``visit_steps``, capped by the size of the state
+        (``visit_min_bytes``) and by what the library has for this D"""
+        ks = int(self.visit_steps) if 32 * self.dim * self.dim * self.ntraj >= self.visit_min_bytes else 2
+        probe = sc_state.from_buffer_copy(self._state)
+        probe.mono_layout = _lib.SC_MONO_TILED16
+        while ks > 2 and not lib.sc_hk_step_visit_supported(desc, probe, self._hk, ks):
+            ks -= 1
+        return max(ks, 2)
+
+    def _visit_scratch(self, ks):
+        """scratch of sc_hk_step_multi / sc_hk_step_visit for up to `ks` steps per visit: work [ks], epart [ks], and the ks - 1
+        intermediate states qp / act / c2 / sgn with one sc_state view each (``states_mid``; ``state_mid`` is the first)"""
         n, d, dev = self.ntraj, self.dim, self.device
-        if self._multi is None:
-            grid = self._gstep
-            bufs = {"work": torch.empty((2, n, 4, d), dtype=F64, device=dev), "qp": torch.empty((n, 2 * d), dtype=F64, device=dev),
-                    "act": torch.empty(n, dtype=F64, device=dev), "c2": torch.empty(n, dtype=C128, device=dev),
-                    "sgn": torch.empty(n, dtype=F64, device=dev), "bad": torch.zeros(1, dtype=torch.int32, device=dev),
-                    "epart": torch.zeros((2, grid), dtype=F64, device=dev)}
-            bufs["ms"] = sc_multi_scratch(work=ptr(bufs["work"]), qp_mid=ptr(bufs["qp"]), act_mid=ptr(bufs["act"]), c2_mid=ptr(bufs["c2"]),
-                                          sgn_mid=ptr(bufs["sgn"]), unrepaired=ptr(bufs["bad"]))
-            mid = sc_state.from_buffer_copy(self._state)
-            mid.qp, mid.act, mid.c2, mid.sgn = ptr(bufs["qp"]), ptr(bufs["act"]), ptr(bufs["c2"]), ptr(bufs["sgn"])
-            bufs["state_mid"] = mid
-            self._multi = bufs
         m = self._multi
+        if m is not None and m["ks"] >= ks:
+            return m
+        grid = self._gstep
+        bufs = {"ks": ks, "work": torch.empty((ks, n, 4, d), dtype=F64, device=dev),
+                "qp": torch.empty(((ks - 1) * n, 2 * d), dtype=F64, device=dev),
+                "act": torch.empty((ks - 1) * n, dtype=F64, device=dev), "c2": torch.empty((ks - 1) * n, dtype=C128, device=dev),
+                "sgn": torch.empty((ks - 1) * n, dtype=F64, device=dev),
+                "bad": m["bad"] if m is not None else torch.zeros(1, dtype=torch.int32, device=dev),
+                "epart": torch.zeros((ks, grid), dtype=F64, device=dev)}
+        bufs["ms"] = sc_multi_scratch(work=ptr(bufs["work"]), qp_mid=ptr(bufs["qp"]), act_mid=ptr(bufs["act"]), c2_mid=ptr(bufs["c2"]),
+                                      sgn_mid=ptr(bufs["sgn"]), unrepaired=ptr(bufs["bad"]))
+        mids = []
+        for j in range(ks - 1):
+            mid = sc_state.from_buffer_copy(self._state)
+            mid.qp, mid.act = ptr(bufs["qp"][j * n:]), ptr(bufs["act"][j * n:])
+            mid.c2, mid.sgn = ptr(bufs["c2"][j * n:]), ptr(bufs["sgn"][j * n:])
+            mids.append(mid)
+        bufs["states_mid"], bufs["state_mid"] = mids, mids[0]
+        if m is not None:
+            bufs["retired"] = m              # launches on the stream may still use the smaller scratch
+        self._multi = bufs
+        return bufs
+
+    def _launch_step_pair(self, desc, dt):
+        self._launch_step_visit(desc, dt, 2)
+
+    def _launch_step_visit(self, desc, dt, ks):
+        """`ks` time steps in one visit of every trajectory: 2 = sc_hk_step_multi, 3 and 4 = sc_hk_step_visit"""
+        n = self.ntraj
+        m = self._visit_scratch(ks)
         s = self._stream()
         self._leave_modal()
         self._sync_dense_mono(leave_diagonal=True)
         self._set_mono_layout(_lib.SC_MONO_TILED16)
-        m["state_mid"].mono_layout = _lib.SC_MONO_TILED16
+        for mid in m["states_mid"]:
+            mid.mono_layout = _lib.SC_MONO_TILED16
         timed = getattr(self, "profile_step_kernel", False)
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        with self._timed("hk_step_pair"):
-            check(lib.sc_hk_step_multi(desc, self._state, self._hk, m["ms"], dt, ptr(m["epart"]), s))
+        if ks == 2:
+            with self._timed("hk_step_pair"):
+                check(lib.sc_hk_step_multi(desc, self._state, self._hk, m["ms"], dt, ptr(m["epart"]), s))
+        else:
+            with self._timed("hk_step_visit"):
+                check(lib.sc_hk_step_visit(desc, self._state, self._hk, m["ms"], dt, ptr(m["epart"]), ks, s))
         if timed:
             e1.record()
-            self.__dict__.setdefault("_step_events", []).append((e0, e1, 2))
-        for sub in range(2):
+            self.__dict__.setdefault("_step_events", []).append((e0, e1, ks))
+        for sub in range(ks):
             check(lib.sc_energy_guard(C_void(m["epart"].data_ptr() + 8 * sub * self._gstep), self._gstep, float(n), ptr(self._elog), s))
-        self._nsteps += 2
+        self._nsteps += ks
 
     def _run_graph(self, potential, dt, nt, desc, slots, mbase=None, blk=None):
         """first iteration eagerly (lazy set-up, layout conversion), then one captured iteration replayed nt - 1 times"""

@@ -50,20 +50,20 @@ def main():
     fetch = per_kernel(fetch_dir, "FETCH_SIZE")
     write = per_kernel(write_dir, "WRITE_SIZE")
     # template arguments <NR, MINW, STEP, TILED, KS>: the step launches run on the tiled layout, the prefactor-only launch
-    # of initial_conditions() on the row-major one; KS = 2 is the two-steps-per-visit kernel of run() (sc_hk_step_multi), whose
-    # counters cover TWO time steps per launch -- everything below is per TIME STEP
-    try:
-        kstep, f_step = pick(fetch, "hk_step_sd_kernel", "true, true, 2>")
-        _, w_step = pick(write, "hk_step_sd_kernel", "true, true, 2>")
-        _, f_modes = pick(fetch, "hk_modes_multi_kernel")
-        _, w_modes = pick(write, "hk_modes_multi_kernel")
-        steps_per_launch = 2
-    except KeyError:
-        kstep, f_step = pick(fetch, "hk_step_sd_kernel", "true, true, 1>")
-        _, w_step = pick(write, "hk_step_sd_kernel", "true, true, 1>")
-        _, f_modes = pick(fetch, "hk_modes_kernel")
-        _, w_modes = pick(write, "hk_modes_kernel")
-        steps_per_launch = 1
+    # of initial_conditions() on the row-major one; KS > 1 are the steps-per-visit kernels of run() (sc_hk_step_multi, sc_hk_step_visit),
+    # whose counters cover KS time steps per launch -- everything below is per TIME STEP
+    for steps_per_launch in (4, 3, 2, 1):      # KS > 2: sc_hk_step_visit
+        try:
+            kstep, f_step = pick(fetch, "hk_step_sd_kernel", f"true, true, {steps_per_launch}>")
+        except KeyError:
+            continue
+        _, w_step = pick(write, "hk_step_sd_kernel", f"true, true, {steps_per_launch}>")
+        modes = f"hk_modes_multi_kernel<{steps_per_launch}>" if steps_per_launch > 1 else "hk_modes_kernel"
+        _, f_modes = pick(fetch, modes)
+        _, w_modes = pick(write, modes)
+        break
+    else:
+        raise KeyError("hk_step_sd_kernel")
     _, f_pref = pick(fetch, "hk_step_sd_kernel", "false, false, 1>")
     f_step, w_step, f_modes, w_modes = ([v / steps_per_launch for v in x] for x in (f_step, w_step, f_modes, w_modes))
     mean = lambda x: sum(x) / len(x)
@@ -76,7 +76,7 @@ def main():
     res = {
         "workload": {"ntraj": n, "dim": dim, "kernel": kstep.replace("void ", "").replace("(anonymous namespace)::", "").split("(StepArgs")[0],
                      "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (two separate passes) -- "
-                                "python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline"},
+                                "python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline [--no-configs]"},
         "steps_per_launch": steps_per_launch,
         "FETCH_SIZE_KiB_per_launch": mean(f_step), "WRITE_SIZE_KiB_per_launch": mean(w_step),
         "launches_averaged": len(f_step),
@@ -89,8 +89,8 @@ def main():
         "algorithmic_bytes_per_launch": alg,
         "traffic_over_algorithmic": (read_b + write_b + modes_b) / alg,
         "note": "step kernel + its modes pre-pass (row propagators: 4*D*8 B written and read back per trajectory).  All 'per_launch' "
-                "figures are per TIME STEP: with steps_per_launch = 2 (sc_hk_step_multi) the counters of a launch were halved.  "
-                "FETCH_SIZE counts what the L2 requests from the fabric; the second sub-step's reads are served by the memory-side "
+                "figures are per TIME STEP: with steps_per_launch = KS > 1 (sc_hk_step_multi, sc_hk_step_visit) the counters of a launch "
+                "were divided by KS.  FETCH_SIZE counts what the L2 requests from the fabric; the later sub-steps' reads are served by the memory-side "
                 "cache (tools/micro/revisit.hip), so DRAM reads are lower than this figure",
     }
     with open(out_path, "w") as fh:

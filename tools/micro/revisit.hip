@@ -11,6 +11,11 @@
 // same lines again, modifies and writes them (non-temporal stores, as the kernel's last sub-step).  Is a line that a READ brought in
 // still in the L2 / memory-side cache 30 us and 118 MB later, and does it have to be a plain load?  read_then_rmw below: launch time
 // against one read-modify-write pass (1 read + 1 write from HBM); a missed re-read shows as a second read pass (+ ~1.8 ms).
+// Third question (KS > 2 time steps per visit without intermediate stores): a plain first read, then R = 1, 2, 3 re-read passes of the
+// same lines by the same workgroup, DELAY ticks of idle in front of every re-read; the first R - 1 re-reads only read, the last one
+// modifies and stores non-temporally.  read_rereads below: ms per launch per (R, gap) next to the single read-modify-write pass and a
+// read-only pass from HBM; "sleeps only" skips the intermediate re-reads but keeps their idle time, so the difference to it is what
+// the re-reads themselves cost.  A re-read that costs as much as the HBM read pass did not survive in the cache.
 // build: hipcc --offload-arch=gfx950 -O3 -o revisit revisit.hip ; run: ./revisit [n] [D]
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -85,6 +90,81 @@ __global__ __launch_bounds__(256, 4) void read_then_rmw(double *mono, long n, lo
             }
         }
     }
+}
+
+// pass 0: plain loads only; then R re-read passes, each after DELAY ticks of idle: the first R - 1 load only (MID: or are skipped, their
+// idle time kept), the last one loads, updates and stores non-temporally.  R = 0: the read-only pass alone (NT0: non-temporal loads)
+template <int R, int DELAY, bool MID, bool NT0>
+__global__ __launch_bounds__(256, 4) void read_rereads(double *mono, long n, long units, double *sink) {
+    for (long tr = blockIdx.x; tr < n; tr += gridDim.x) {
+        d2 *M = (d2 *)mono + tr * units;
+        double acc = 0.0;
+#pragma unroll 1
+        for (int r = 0; r < (R > 0 ? R : 1); ++r) {
+            if (r == 0 || MID) {
+                for (long c0 = 0; c0 < units; c0 += 256 * 8) {
+                    d2 v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const long c = c0 + u * 256 + threadIdx.x;
+                        v[u] = c < units ? (NT0 ? __builtin_nontemporal_load(M + c) : M[c]) : (d2){0.0, 0.0};
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) acc += v[u].x + v[u].y;
+                }
+            }
+            if (DELAY > 0 && R > 0) {
+                const long long t0 = wall_clock64();
+                while (wall_clock64() - t0 < DELAY) __builtin_amdgcn_s_sleep(8);
+            }
+        }
+        if (acc != acc) sink[0] = acc;
+        if (R == 0) continue;
+        for (long c0 = 0; c0 < units; c0 += 256 * 8) {
+            d2 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long c = c0 + u * 256 + threadIdx.x;
+                v[u] = c < units ? M[c] : (d2){0.0, 0.0};
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long c = c0 + u * 256 + threadIdx.x;
+                const d2 o = {v[u].x * 1.0000001 + v[u].y * 1e-9, v[u].y * 1.0000001 - v[u].x * 1e-9};
+                if (c < units) __builtin_nontemporal_store(o, M + c);
+            }
+        }
+    }
+}
+
+template <int R, int DELAY, bool MID, bool NT0>
+static double run_read_rereads(double *mono, long n, long units, double *sink, const char *what) {
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    float best = 1e30f;
+    for (int rep = 0; rep < 3; ++rep) {
+        CHECK(hipEventRecord(e0));
+        hipLaunchKernelGGL((read_rereads<R, DELAY, MID, NT0>), dim3(1024), dim3(256), 0, 0, mono, n, units, sink);
+        CHECK(hipEventRecord(e1));
+        CHECK(hipEventSynchronize(e1));
+        float ms;
+        CHECK(hipEventElapsedTime(&ms, e0, e1));
+        if (ms < best) best = ms;
+    }
+    printf("%-72s R = %d gap = %2d us : %8.3f ms per launch\n", what, R, DELAY / 100, best);
+    return best;
+}
+
+template <int DELAY>
+static void visit_gate(double *mono, long n, long units, double *sink, double hbm_read) {
+    const double r1 = run_read_rereads<1, DELAY, true, false>(mono, n, units, sink, "read, 1 re-read (read-modify-write, non-temporal stores)");
+    const double r2 = run_read_rereads<2, DELAY, true, false>(mono, n, units, sink, "read, 2 re-reads (the last one read-modify-write)");
+    const double r3 = run_read_rereads<3, DELAY, true, false>(mono, n, units, sink, "read, 3 re-reads (the last one read-modify-write)");
+    const double s2 = run_read_rereads<2, DELAY, false, false>(mono, n, units, sink, "read, 2 gaps, 1 re-read (sleeps only)");
+    const double s3 = run_read_rereads<3, DELAY, false, false>(mono, n, units, sink, "read, 3 gaps, 1 re-read (sleeps only)");
+    printf("# gap = %2d us: second re-read %+.3f ms (its gap alone %+.3f), third re-read %+.3f ms (its gap alone %+.3f); HBM read pass %.3f ms\n",
+           DELAY / 100, r2 - r1, s2 - r1, r3 - r2, s3 - s2, hbm_read);
+    printf("# gap = %2d us: per time step, streaming alone: KS = 2: %.3f  KS = 3: %.3f  KS = 4: %.3f ms\n", DELAY / 100, r1 / 2, r2 / 3, r3 / 4);
 }
 
 template <bool NT1, int DELAY>
@@ -168,5 +248,14 @@ int main(int argc, char **argv) {
     run_read_then_rmw<true, 0>(mono, n, units, sink, "read (non-temporal), then read-modify-write, back to back");
     run_read_then_rmw<false, 3000>(mono, n, units, sink, "read (plain), 30 us, then read-modify-write");
     run_read_then_rmw<true, 3000>(mono, n, units, sink, "read (non-temporal), 30 us, then read-modify-write");
+    // KS time steps per visit: R = KS - 1 re-reads of what a plain first read brought in
+    printf("# visit of R + 1 sub-steps: plain first read, R re-reads by the same workgroup, gap in front of each, last pass non-temporal stores\n");
+    const double hbm_nt = run_read_rereads<0, 0, true, true>(mono, n, units, sink, "read-only pass from HBM (non-temporal loads)");
+    const double hbm_pl = run_read_rereads<0, 0, true, false>(mono, n, units, sink, "read-only pass from HBM (plain loads)");
+    run<1, true, 0>(mono, n, units, "single read-modify-write pass (non-temporal)");
+    const double hbm_read = hbm_nt < hbm_pl ? hbm_nt : hbm_pl;
+    visit_gate<0>(mono, n, units, sink, hbm_read);
+    visit_gate<3000>(mono, n, units, sink, hbm_read);
+    visit_gate<6000>(mono, n, units, sink, hbm_read);
     return 0;
 }

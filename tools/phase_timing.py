@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Ablation timing of the step kernel on the bench workload (debug tool, GPU box only).
 
-Usage: python tools/phase_timing.py [ntraj]
+Usage: [DIM=60] [LAYOUT=tiled] [VISIT_STEPS=3,4] python tools/phase_timing.py [ntraj]
 Times (HIP events on the launch stream): the full step and the prefactor-only launch (loads + matrix + elimination, no
 RK4 / stores).  The elimination is ablated at COMPILE time (a run-time switch costs the kernel its register allocation):
     tools/mkvar.sh nolu -DSC_SD_ABLATE_LU=1 ;  SC_LIB_PATH=var/libsc_nolu.so SC_DEBUG_SKIP_LU=1 python tools/phase_timing.py
@@ -59,3 +59,12 @@ if prop._state.mono_layout == 1 and lib.sc_hk_step_multi_supported(desc, prop._s
     pair = lambda: check(lib.sc_hk_step_multi(desc, prop._state, prop._hk, m["ms"], dt, ptr(m["epart"]), prop._stream()))
     t_pair = timed(pair)
     print(f"D={DIM} n={n} two steps per visit [{what}]: {t_pair / 2:.3f} ms per step ({t_pair:.3f} per launch)", flush=True)
+    # more time steps per visit (sc_hk_step_visit): VISIT_STEPS=3,4
+    for ks in (int(k) for k in os.environ.get("VISIT_STEPS", "3,4").split(",") if k):
+        if not lib.sc_hk_step_visit_supported(desc, prop._state, prop._hk, ks):
+            print(f"D={DIM} n={n} {ks} steps per visit: not supported", flush=True)
+            continue
+        m = prop._visit_scratch(ks)
+        visit = lambda: check(lib.sc_hk_step_visit(desc, prop._state, prop._hk, m["ms"], dt, ptr(m["epart"]), ks, prop._stream()))
+        t_visit = timed(visit)
+        print(f"D={DIM} n={n} {ks} steps per visit [{what}]: {t_visit / ks:.3f} ms per step ({t_visit:.3f} per launch)", flush=True)

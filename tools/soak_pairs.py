@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""One-off soak: the pair path against one launch per step over many steps at the benchmark size, bit for bit (the store-data hazard of
-DESIGN section 3 showed up in 1 % of the trajectories per step before it was guarded: any residue would break the identity here)."""
+"""One-off soak: the steps-per-visit path of run() (pairs, or visits of up to `visit_steps` time steps) against one launch per step over
+many steps at the benchmark size, bit for bit (the store-data hazard of DESIGN section 3 showed up in 1 % of the trajectories per step
+before it was guarded: any residue would break the identity here).      python tools/soak_pairs.py [ntraj] [steps] [visit_steps]"""
 import os
 import sys
 import numpy as np
@@ -18,9 +19,13 @@ out = []
 for pairs in (True, False):
     prop = PR.HermanKlukPropagator(G, G, device="cuda")
     prop.pair_steps = pairs
+    if len(sys.argv) > 3:
+        prop.visit_steps = int(sys.argv[3])
     prop.initial_conditions(q0, 0.0 * q0, G, ntraj=n, seed=7)
     c, k = prop.run(pot, dt, nt, E0)
     prop.synchronize()
+    if pairs:
+        print("steps per visit:", prop._multi["ks"], flush=True)
     out.append((c, k, prop._mono.clone(), prop._c2.clone(), prop._sgn.clone(), prop._qp.clone()))
     del prop
 a, b = out
