@@ -232,7 +232,15 @@ __device__ __forceinline__ void column_fetch_below(const cplx (&m)[NR][NR], cplx
 // `tid` = index of the thread inside its 256-thread elimination group (= threadIdx.x when the group is the workgroup),
 // `barrier()` synchronises the four wavefronts of the group.
 // `detbuf`: the 16 NR signed pivots in LDS (see publish_pivot_row), all 1 before block 0.
-template <int NR, int KB, int RW, class Barrier>
+// TRIM_LAST (hk_step_sd_kernel only; the other callers keep the loop they were measured with): the LAST diagonal block (KB = NR - 1,
+// no trailing slots) without the work nobody reads.  All a wave contributes there are the pivot rows it publishes, so it leaves the
+// step loop once it has published its last own valid row -- the updates of its rows behind that would be read by no one -- and a
+// wave that owns no valid step of the block (D = 60: rows 60..63 of wave 3 are padding) leaves at once.  The consumer half of the
+// last valid step is executed by nobody.  What is published, and with it every pivot, sign and flag, is what the full loop publishes.
+// The loop holds no barrier, and `barrier()` in front of the block is still executed by every wave before it leaves.  A wave that
+// left reads and writes the pivot ring no more; no ring entry is rewritten before the caller's next barrier in front of a block 0
+// (the RESET BARRIER of hk_step_sd_kernel), so the "consumed step s - 4" argument above is not needed for waves that left.
+template <int NR, int KB, int RW, bool TRIM_LAST = false, class Barrier>
 __device__ __forceinline__ void eliminate_block(cplx (&m)[NR][NR], cplx *detbuf, int D, int seq,
                                                 cplx (*rowbuf)[RW], PivotRecord *pivrec, int *weak, int tid,
                                                 Barrier &&barrier) {
@@ -245,7 +253,15 @@ __device__ __forceinline__ void eliminate_block(cplx (&m)[NR][NR], cplx *detbuf,
     barrier();
     if (ti == 0) publish_pivot_row<NR, KB, RW>(m, detbuf, live, 0, seq, rowbuf, pivrec, weak, tid);
     constexpr bool PEEL = SC_LU_PEEL_LAST != 0 && FULL;
-    for (int kt = 0; kt < (PEEL ? 15 : 16); ++kt) {
+    int kend = PEEL ? 15 : 16;
+    if constexpr (TRIM_LAST && !FULL) {
+        // the wave's last own valid step is 4 jl + w (16-lane row jl of wave w holds block row 4 w + jl); it is published inside the
+        // step before it (or in front of the loop: step 0), behind which the wave has nothing left to do
+        const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int jl = min(3, nk - 1 - 4 * w);
+        kend = jl < 0 ? 0 : 4 * jl + w;
+    }
+    for (int kt = 0; kt < kend; ++kt) {
         if (!FULL && !pivot_step_valid(kt, nk)) continue;
         int next = kt + 1;
         if (!FULL) while (next < 16 && !pivot_step_valid(next, nk)) ++next;

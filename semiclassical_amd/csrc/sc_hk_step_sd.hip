@@ -84,6 +84,12 @@
 #ifndef SC_SD_FORCE_FIXUP
 #define SC_SD_FORCE_FIXUP 0
 #endif
+#ifndef SC_SD_DEFER_TAIL
+#define SC_SD_DEFER_TAIL 1   // the determinant tail of item t runs inside phase B of item t + 1 (see "The determinant tail" below); 0: behind the end barrier
+#endif
+#ifndef SC_SD_TRIM_LAST
+#define SC_SD_TRIM_LAST 1    // last diagonal block without the steps nobody reads (TRIM_LAST of eliminate_block, sc_hk_lu.h)
+#endif
 #ifndef SC_SD_BLOCK_BARRIER
 #define SC_SD_BLOCK_BARRIER no_barrier     // wg_barrier: a workgroup barrier in front of every diagonal block
 #endif
@@ -117,6 +123,25 @@ typedef unsigned int sc_v4u __attribute__((ext_vector_type(4)));
 //     follow them are plain (they meet in the cache), the first load and the last store of a visit non-temporal.  There the kernel
 //     waits for round trips, not for HBM, and the redone rotation is latency it cannot hide (store-free measured 0.6 - 2.6 % slower).
 // Either way the kernel is bound by the elimination (FP64 VALU issue), no longer by HBM.
+// The determinant tail (SC_SD_DEFER_TAIL).  An ITEM is one sub-step of one trajectory.  Its tail -- the product of the signed
+// pivots (lu_partial_products, finish_determinant), the weak / zero-pivot handling, the branch rule and the stores of c2 / sgn /
+// c2_mid / sgn_mid / flags -- is one lane's serial work on wave 0 and computes nothing another wave needs.  It used to stand
+// between the end barrier of item t and the first barrier of item t + 1, where waves 1 - 3 waited for it.  Now thread 0 (threads
+// 0 - 15 for the partial products) runs the tail of item t INSIDE phase B of item t + 1, between the request of a row slot (slot 2,
+// or the last one for NR < 3) and the arithmetic on it, where wave 0 waits for memory anyway; the tail's own loads are issued behind
+// that slot's, so it waits for nothing the wave would not have waited for.  The last item of a workgroup has no next phase B: its
+// tail is an epilogue behind the trajectory loop.  Why the ordering holds:
+//   - detbuf[p] / weakbuf[p] are double-buffered by item parity p.  The owner lanes of item t write them inside the elimination of
+//     item t; every wave passes the end barrier of item t (and, when stepping, the prop[] barrier of item t + 1) between that
+//     and the tail's reads.  The epilogue stands behind the end barrier of the last item.
+//   - they are next written for item t + 2: reset at its top by threads of WAVE 0 only (16 NR <= 64), i.e. by the wave that ran
+//     the tail of item t earlier in its own program order; the owner lanes' writes of item t + 2 lie behind its RESET BARRIER,
+//     which wave 0 reaches only behind its phase B of item t + 1.
+//   - the tails of one trajectory run in sub-step order in the same thread.  For ks > 0 the predecessor's determinant and sign come
+//     from LDS (tailkeep), where that thread left them one tail earlier (LDS operations of a wave execute in order) -- not from
+//     c2_mid / sgn_mid, which miss the L2 at n = 1e5; those are still stored, the correlation kernels read them.  For ks = 0 they
+//     are loaded from c2[tr] / sgn[tr] at the head of the tail, and the partial products run while the loads are in flight.
+//   - every path executes the barriers it executed before: the tail contains none, and the epilogue adds none.
 // Row propagators of sub-step ks: M.work[ks][n][4][D] (hk_modes_multi_kernel); determinant and branch sign after sub-step
 // ks < KS - 1: M.c2_mid / M.sgn_mid [ks][n], after the last one: the state's own arrays.
 struct MultiArgs {
@@ -161,6 +186,8 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     __shared__ cplx detbuf[2][16 * NR];      // signed pivots, slot 16 KB + kt
     __shared__ int weakbuf[2];               // bit 0: weak in-block pivot (-> pivoted fallback), bit 1: zero pivot
     __shared__ int nextbuf[2];               // what thread 0 drew from the trajectory cursor
+    __shared__ double tailkeep[4];           // thread 0, deferred tail of a visit: (Re c2, Im c2, sgn) of the sub-step before
+    __shared__ long long tailtr;             // wave 0, deferred tail: the trajectory whose last sub-step waits for its tail (no register across the elimination)
 
     static_assert(KS == 1 || !SC_SD_DIRECT_P || NR < SC_SD_NOSTORE_MIN_NR, "a later sub-step of a visit needs the row propagators of the earlier ones (prop[])");
     const int D = A.st.dim, DD = D * D, tid = threadIdx.x;
@@ -199,6 +226,58 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     // barrier of the elimination.  Without sc_state.flags: static stride.
     int *cursor = A.st.flags ? A.st.flags + A.st.n + 1 : nullptr;
     int64_t trn = 0;
+    constexpr bool defer_tail = SC_SD_DEFER_TAIL != 0;
+    constexpr bool skip_lu = SC_SD_ABLATE_LU != 0;
+    // the tail of sub-step kp of trajectory tp, whose results lie in the buffers of parity parp: determinant from the signed pivots,
+    // weak / zero pivots, branch rule, stores.  `tl`: the thread's index as the caller has it; tp < 0: the trajectory wave 0 left in
+    // tailtr.  No barrier in here.
+    auto item_tail = [&](auto kpc, int64_t tp, int parp, int tl) {
+        constexpr int kp = decltype(kpc)::value;
+        if (tl >= 16) return;
+        if (tp < 0) tp = tailtr;
+        cplx *c2 = (cplx *)A.st.c2;
+        // previous value / destination of this sub-step's determinant and branch sign
+        const cplx *c2_in = kp == 0 ? c2 + tp : (const cplx *)MA.c2_mid + ((int64_t)(kp - 1) * A.st.n + tp);
+        const double *sg_in = kp == 0 ? A.st.sgn + tp : MA.sgn_mid + ((int64_t)(kp - 1) * A.st.n + tp);
+        cplx *c2_out = kp == KS - 1 ? c2 + tp : (cplx *)MA.c2_mid + ((int64_t)kp * A.st.n + tp);
+        double *sg_out = kp == KS - 1 ? A.st.sgn + tp : MA.sgn_mid + ((int64_t)kp * A.st.n + tp);
+        const int *weak = &weakbuf[parp];
+        // the predecessor FIRST (thread 0): from LDS where the tail of the sub-step before left it, otherwise (sub-step 0, or tails
+        // that are not deferred) from memory -- requested here so that the partial products below run under the round trip
+        constexpr bool kept = defer_tail && kp > 0;
+        cplx prev = c_make(0.0, 0.0);
+        double sg = 1.0;
+        if (defer_tail && tl == 0 && do_step) {
+            if (kept) { prev = c_make(tailkeep[0], tailkeep[1]); sg = tailkeep[2]; }
+            else { prev = *c2_in; sg = *sg_in; }
+        }
+        if (tl < 16) lu_partial_products<NR>(detbuf[parp], tl);
+        if (kp == KS - 1 && tl == 0 && (*weak & 1) && A.st.flags && !skip_lu) {
+            // c2 / sgn are left to the fully pivoted fallback, which tracks against the state's c2 / sgn: after an
+            // intermediate sub-step those are KS steps old, so hand it this sub-step's predecessor (c2_mid / sgn_mid)
+            if (KS > 1) {
+                c2[tp] = defer_tail ? prev : *c2_in;
+                A.st.sgn[tp] = defer_tail ? sg : *sg_in;
+            }
+            A.st.flags[tp] = 1;
+            atomicAdd(&A.st.flags[A.st.n], 1);   // lets the fix-up launch return at once when nothing was flagged
+        } else if (tl == 0) {
+            if (KS > 1 && kp < KS - 1 && (*weak & 1) && !skip_lu) atomicAdd(MA.unrepaired, 1);
+            const cplx c2new = (*weak & 2) ? c_make(0.0, 0.0) : finish_determinant(detbuf[parp], rows_odd);
+            double sgnew = 1.0;
+            if (do_step) {
+                if (!defer_tail) { prev = *c2_in; sg = *sg_in; }
+                const bool flip = crossed_branch_cut(prev, c2new);
+                sgnew = flip ? -sg : sg;
+                if (KS > 1) *sg_out = sgnew;
+                else if (flip) *sg_out = sgnew;
+            } else {
+                *sg_out = 1.0;
+            }
+            *c2_out = c2new;
+            if (defer_tail && kp < KS - 1) { tailkeep[0] = c2new.x; tailkeep[1] = c2new.y; tailkeep[2] = sgnew; }
+        }
+    };
     for (int64_t tr = blockIdx.x; tr < A.st.n; tr = trn) {
       sfor<0, KS>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::value;                 // sub-step of this visit
@@ -375,6 +454,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
             if (!first && do_step && pa < Dl) prv = MA.work[(((int64_t)ks * A.st.n + tr) * 4 + pk) * (int64_t)Dl + pa];
         }
         if (first || !SC_SD_XPREFETCH || NR == 1) first_requests(tr, ksc);
+        const bool had_item = !first;                    // deferred tail: is there an item before this one?
         first = false;
         __builtin_amdgcn_sched_barrier(0);
         if (NR > 1 && SC_SD_DEPTH > 1) load_slot(std::integral_constant<int, (NR > 1 ? 1 : 0)>(), tr, std::integral_constant<int, aux_load>());
@@ -392,6 +472,12 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
             if (SC_SD_DEPTH == 1 && ra > (SC_SD_XPREFETCH2 ? 1 : 0)) load_slot(rac, tr, std::integral_constant<int, aux_load>());
             if (SC_SD_DEPTH > 1 && ra + 1 < NR && ra > 0) load_slot(std::integral_constant<int, (ra + 1 < NR ? ra + 1 : 0)>(), tr, std::integral_constant<int, aux_load>());
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (defer_tail && ra == (NR < 3 ? NR - 1 : 2)) {
+                // the tail of the item before this one (see "The determinant tail"), while this slot's loads are in flight
+                if constexpr (ks > 0) item_tail(std::integral_constant<int, ks - 1>(), tr, par ^ 1, tl);
+                else if (had_item) item_tail(std::integral_constant<int, KS - 1>(), -1, par ^ 1, tl);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             finish_slot(rac);
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -399,7 +485,6 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         // ---------------- phase C: determinant in registers ----------------
         // phase ablation (tools/phase_timing.py) is a COMPILE-time switch of a variant library: a run-time flag here costs the
         // kernel 148 B/lane of scratch and 30 % of its speed
-        constexpr bool skip_lu = SC_SD_ABLATE_LU != 0;
         SD_TICK(1);
         if (ks == 0 && cursor && tl == 0) nextbuf[par] = drawn;
         // RESET BARRIER -- unconditional, in every variant of this kernel (with or without the elimination).  It orders
@@ -444,45 +529,18 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
                 }
             }
             if (!skip_lu) {
-                if (KB == 0) eliminate_block<NR, KB, 64>(m, detbuf[par], D, seq0 + 1 + KB, rowbuf, pivrec, weak, tl, no_barrier);   // the RESET BARRIER is its barrier
-                else eliminate_block<NR, KB, 64>(m, detbuf[par], D, seq0 + 1 + KB, rowbuf, pivrec, weak, tl, SC_SD_BLOCK_BARRIER);
+                constexpr bool trim = SC_SD_TRIM_LAST != 0;
+                if (KB == 0) eliminate_block<NR, KB, 64, trim>(m, detbuf[par], D, seq0 + 1 + KB, rowbuf, pivrec, weak, tl, no_barrier);   // the RESET BARRIER is its barrier
+                else eliminate_block<NR, KB, 64, trim>(m, detbuf[par], D, seq0 + 1 + KB, rowbuf, pivrec, weak, tl, SC_SD_BLOCK_BARRIER);
             }
         });
         SD_TICK(3);
         __syncthreads();
         SD_TICK(4);
         if (ks == 0 && NR == 1) trn = cursor ? (int64_t)gridDim.x + __builtin_amdgcn_readfirstlane(nextbuf[par]) : tr + gridDim.x;
-        // no barrier after this: the buffers of this parity are next written two visits on
-        cplx *c2 = (cplx *)A.st.c2;
-        // previous value / destination of this sub-step's determinant and branch sign
-        const cplx *c2_in = ks == 0 ? c2 + tr : (const cplx *)MA.c2_mid + ((int64_t)(ks - 1) * A.st.n + tr);
-        const double *sg_in = ks == 0 ? A.st.sgn + tr : MA.sgn_mid + ((int64_t)(ks - 1) * A.st.n + tr);
-        cplx *c2_out = ks == KS - 1 ? c2 + tr : (cplx *)MA.c2_mid + ((int64_t)ks * A.st.n + tr);
-        double *sg_out = ks == KS - 1 ? A.st.sgn + tr : MA.sgn_mid + ((int64_t)ks * A.st.n + tr);
-        if (tl < 16) lu_partial_products<NR>(detbuf[par], tl);
-        if (ks == KS - 1 && tl == 0 && (*weak & 1) && A.st.flags && !skip_lu) {
-            // c2 / sgn are left to the fully pivoted fallback, which tracks against the state's c2 / sgn: after an
-            // intermediate sub-step those are KS steps old, so hand it this sub-step's predecessor (c2_mid / sgn_mid)
-            if (KS > 1) {
-                c2[tr] = *c2_in;
-                A.st.sgn[tr] = *sg_in;
-            }
-            A.st.flags[tr] = 1;
-            atomicAdd(&A.st.flags[A.st.n], 1);   // lets the fix-up launch return at once when nothing was flagged
-        } else if (tl == 0) {
-            if (KS > 1 && ks < KS - 1 && (*weak & 1) && !skip_lu) atomicAdd(MA.unrepaired, 1);
-            const cplx c2new = (*weak & 2) ? c_make(0.0, 0.0) : finish_determinant(detbuf[par], rows_odd);
-            if (do_step) {
-                const cplx prev = *c2_in;
-                const double sg = *sg_in;
-                const bool flip = crossed_branch_cut(prev, c2new);
-                if (KS > 1) *sg_out = flip ? -sg : sg;
-                else if (flip) *sg_out = -sg;
-            } else {
-                *sg_out = 1.0;
-            }
-            *c2_out = c2new;
-        }
+        // no barrier after this: the buffers of this parity are next written two items on
+        if constexpr (defer_tail) { if (ks == KS - 1 && tl == 0) tailtr = tr; }       // its tail runs inside the next item, or in the epilogue
+        else item_tail(ksc, tr, par, tl);
         seq0 += 4; par ^= 1;
         SD_TICK(5);
 #ifdef SD_PHASE_CLOCK
@@ -490,6 +548,8 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
 #endif
       });
     }
+    // epilogue: the tail of the workgroup's last item, behind that item's end barrier
+    if (defer_tail && !first) item_tail(std::integral_constant<int, KS - 1>(), -1, par ^ 1, tid);
 }
 
 #ifdef SD_PHASE_CLOCK

@@ -3,7 +3,10 @@
 wave of workgroups 0 and 512 at six points of every item (variant library built with -DSD_PHASE_CLOCK).
 
     tools/mkvar.sh sdclock -DSD_PHASE_CLOCK
-    SC_LIB_PATH=$PWD/var/libsc_sdclock.so python tools/sd_phases.py [pairs|single]
+    SC_LIB_PATH=$PWD/var/libsc_sdclock.so python tools/sd_phases.py [pairs|single|visit3|visit4]
+
+With the deferred tail (SC_SD_DEFER_TAIL, sc_hk_step_sd.hip) thread 0 finishes the determinant of item t inside the streaming phase
+of item t + 1: "determinant / sign" then holds the item's bookkeeping only, and the tail shows as wave 0's longer streaming phase.
 """
 import ctypes
 import os
@@ -33,7 +36,11 @@ def main():
     prop._set_mono_layout(_lib.SC_MONO_TILED16)
     prop._launch_step_pair(desc, dt)
     m = prop._multi
-    if mode == "pairs":
+    ksub = {"pairs": 2, "single": 1, "visit3": 3, "visit4": 4}[mode]
+    if ksub > 2:
+        m = prop._visit_scratch(ksub)
+        launch = lambda: check(lib.sc_hk_step_visit(desc, prop._state, prop._hk, m["ms"], dt, ptr(m["epart"]), ksub, prop._stream()))
+    elif mode == "pairs":
         launch = lambda: check(lib.sc_hk_step_multi(desc, prop._state, prop._hk, m["ms"], dt, ptr(m["epart"]), prop._stream()))
     else:
         launch = lambda: check(lib.sc_hk_step(desc, prop._state, prop._hk, dt, 0, ptr(prop._epart), prop._stream()))
@@ -63,9 +70,9 @@ def main():
             total = (x[-1, 5] - x[0, 0]) / 100.0
             print(f"workgroup {blk * 512} wave {wave}: {items} items, {total / items:.2f} us per item | "
                   + " | ".join(f"{nm.split(' (')[0]} {v:.2f}" for nm, v in zip(names, list(d.mean(axis=0)) + [gap.mean()])))
-            if mode == "pairs" and wave == 0:
-                for ks in range(2):
-                    dd = d[ks::2].mean(axis=0)
+            if ksub > 1 and wave == 0:
+                for ks in range(ksub):
+                    dd = d[ks::ksub].mean(axis=0)
                     print(f"    sub-step {ks}: " + " | ".join(f"{v:.2f}" for v in dd))
 
 
