@@ -556,6 +556,38 @@ int sc_energy_guard(const double *energy_partials, int32_t n_blocks, double n_tr
  * ALUs (one trajectory per 16 lanes), larger D on the FP64 matrix cores (one workgroup per trajectory at a time). */
 int sc_symplectic_deviation(const sc_state *st, const double *scale, double *dev, void *stream);
 
+/* ---- Discarding trajectories that fail the symplecticity check -----------------------------------
+ * A per-trajectory mask kept[n] (one byte each, 1 = kept, all ones at t = 0) is STICKY: the entry points below only ever clear it.
+ * A discarded trajectory is a sample of value ZERO and N does not change: from its mark on, C_auto, k_ic, their second moments and
+ * their block sums are the sums of the exported per-trajectory terms (cq_out / kq_out of sc_hk_correlate(_m), the term arrays of
+ * sc_wm_correlate) over the kept trajectories with the unchanged weights 1/(N prob_i) -- so the standard errors and the batch-means
+ * errors with their unchanged N and n_b are the errors of this estimator.  The state kernels and the correlate kernels do not know
+ * the mask: a discarded trajectory is still propagated.  These entry points ADD NOTHING to the state.
+ *   sc_discard_mark      clears kept[i] and sets discarded_at[i] = step for every trajectory whose bit is set and whose deviation
+ *                        dev[i][0..2] (what sc_symplectic_deviation wrote) is NOT <= tol in all three blocks: +inf and NaN clear
+ *                        it.  Bits that are clear stay clear, their discarded_at stays what it is (the caller starts it at -1).
+ *                        *kept_count (device; zeroed on the stream first) receives the number of bits set after the mark (integer
+ *                        atomic adds: the value does not depend on their order).  tol NaN or <= 0, or a null pointer:
+ *                        SC_ERR_BAD_ARGUMENT.
+ *   sc_term_masked_sums  ONE pass over cq[n], kq[n] (complex; kq may be NULL: its sums are 0) and kept[n] that leaves, summed over
+ *                        the trajectories with kept[i] != 0,
+ *                            slot[0..3]    = Re sum cq_i, Im sum cq_i, Re sum kq_i, Im sum kq_i
+ *                            moments[0..5] = the six second-moment sums of sc_hk_correlate_m (NULL: not wanted)
+ *                            blocks[b][0..3], b < B = the slot sums over block b = (i >> 2) & (B - 1) (B = 0 and NULL: not wanted;
+ *                                            B as for sc_term_blocks, anything else SC_ERR_BAD_ARGUMENT)
+ *                        moments and blocks are independent options; sum_b blocks[b] is the slot row up to rounding.  A term of a
+ *                        discarded trajectory is selected away before any arithmetic (never multiplied by the mask): it may be
+ *                        inf or NaN.  One writer per output, no floating-point atomics, summation order a function of (n, B)
+ *                        alone: the same bits in every run.  `scratch`: sc_term_masked_scratch_doubles() doubles, free again when
+ *                        the call's work on `stream` has run.  cq / kq 16-byte aligned, kept 4-byte aligned.  Two launches:
+ *                        64 workgroups (workgroup w takes the groups of four trajectories g = w mod 64, all in block w mod B),
+ *                        then one workgroup that adds the 64 partial rows in order. */
+int sc_discard_mark(const double *dev, int64_t n, double tol, int32_t step, uint8_t *kept, int32_t *discarded_at,
+                    int64_t *kept_count, void *stream);
+int64_t sc_term_masked_scratch_doubles(void);
+int sc_term_masked_sums(const double *cq, const double *kq, const uint8_t *kept, int64_t n, int32_t B, double *scratch,
+                        double *slot, double *moments, double *blocks, void *stream);
+
 /* ---- multi-GPU flush -------------------------------------------------------------------------
  * Trajectories shard over the GPUs of a node, one process per GPU; every term of C_auto / k_ic already carries the weight
  * 1/(N_total P(q_i, p_i)) (propagators.py:837, 909), so the functions of the whole ensemble are the plain SUM of the

@@ -184,6 +184,10 @@ SIGNATURES = {
     "sc_reduce_slot": (C.c_int, [c_double_p, C.c_int32, c_double_p, C.c_int32, C.c_double, c_double_p,
                                  C.c_void_p]),
     "sc_symplectic_deviation": (C.c_int, [P(sc_state), c_double_p, c_double_p, C.c_void_p]),
+    "sc_discard_mark": (C.c_int, [c_double_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sc_term_masked_scratch_doubles": (C.c_int64, []),
+    "sc_term_masked_sums": (C.c_int, [c_double_p, c_double_p, C.c_void_p, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                      c_double_p, C.c_void_p]),
     "sc_comm_available": (C.c_int, []),
     "sc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "sc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(C.c_void_p)]),

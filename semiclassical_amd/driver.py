@@ -137,7 +137,7 @@ class CorrelationStore(object):
     BLOCK_KEYS = ('autocorrelation_blocks', 'ic_correlation_blocks', 'block_trajectories')
 
     SYMPLECTICITY_KEYS = ('symplecticity_steps', 'symplecticity_max', 'symplecticity_mean', 'symplecticity_exceeding',
-                          'symplecticity_tolerance')
+                          'symplecticity_tolerance', 'symplecticity_kept', 'symplecticity_discard')
 
     def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None):
         """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
@@ -151,10 +151,28 @@ class CorrelationStore(object):
         ``symplecticity``: the record of propagate_batch's symplecticity checks ('steps', 'max', 'mean' per check and, with a
         tolerance, 'exceeding' and 'tolerance').  Over batches the maxima pool as maxima, the means with the weights of the
         correlation functions, the counts add.  Files and batches that do not both carry the keys, or that differ in the steps
-        checked or in the tolerance, lose them (same rule again)."""
+        checked or in the tolerance, lose them (same rule again).
+        With 'discard' set in the record (the task discards the trajectories that fail the check) the
+        record also carries 'kept', the trajectories still kept after every check; the file then holds ``symplecticity_kept``
+        (counts add) and ``symplecticity_discard``.  Correlation functions with and without discarding, or discarded against
+        another tolerance or at other steps, are different estimators: pooling them is refused (ConfigurationError), never
+        resolved by dropping keys."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
+        discarding = symplecticity is not None and bool(symplecticity.get('discard', False))
+        if done > 0:
+            was_discarding = bool(stored.get('symplecticity_discard', False))
+            if was_discarding != discarding:
+                raise ConfigurationError(
+                    f"{self.path} holds correlation functions computed {'with' if was_discarding else 'without'} "
+                    f"\"discard_nonsymplectic\", this batch was computed {'with' if discarding else 'without'} it: they are "
+                    "different estimators and cannot be pooled")
+            if discarding and not self._same_checks(stored, symplecticity):
+                raise ConfigurationError(
+                    f"{self.path} holds correlation functions whose trajectories were discarded at other steps or against "
+                    "another tolerance than this batch's (\"check_symplecticity_every\", \"symplecticity_tolerance\"): they "
+                    "are different estimators and cannot be pooled")
         stored['autocorrelation'] = (ntraj * autocorrelation + done * stored['autocorrelation']) / total
         stored['ic_correlation'] = (ntraj * ic_correlation + done * stored['ic_correlation']) / total
         stored['trajectories'] = total
@@ -199,6 +217,10 @@ class CorrelationStore(object):
                 counts = np.asarray(symplecticity['exceeding'], dtype=np.int64)
                 stored['symplecticity_exceeding'] = stored['symplecticity_exceeding'] + counts if pool else counts
                 stored['symplecticity_tolerance'] = float(symplecticity['tolerance'])
+            if discarding:
+                kept = np.asarray(symplecticity['kept'], dtype=np.int64)
+                stored['symplecticity_kept'] = stored['symplecticity_kept'] + kept if pool else kept
+                stored['symplecticity_discard'] = True
         elif have_checks or symplecticity is not None:
             logger.warning("symplecticity checks dropped from %s: %s", self.path,
                            "this task does not make them (\"check_symplecticity_every\": k)" if symplecticity is None else
@@ -233,20 +255,37 @@ def make_propagator(task, Gamma_0, device):
     return propagators.HermanKlukPropagator(Gamma_0, Gamma_0, device=device)
 
 
-def _check_symplecticity(propagator, step, time, tolerance, log):
-    """one symplecticity check of the batch: (step, max, mean, trajectories above the tolerance) -- one host transfer"""
-    eps = propagator.symplectic_deviation()
-    stats = [eps.max(), eps.mean()] + ([(eps > tolerance).sum().to(eps.dtype)] if tolerance is not None else [])
-    largest, mean, *above = torch.stack(stats).tolist()
-    exceeding = int(above[0]) if above else None
+def _check_symplecticity(propagator, step, time, tolerance, log, discard=False):
+    """one symplecticity check of the batch: (step, max, mean, trajectories above the tolerance, trajectories kept) -- one host
+    transfer.  ``discard``: the check also discards the trajectories above the tolerance (propagator.discard_nonsymplectic); max
+    and mean are then taken over the trajectories that were still kept BEFORE this mark (one dead trajectory would otherwise make
+    them +inf for the rest of the run; NaN once nobody is left), the last element is the number kept after it (else None)."""
+    if discard:
+        alive = propagator.kept
+        eps = propagator.discard_nonsymplectic(tolerance)
+        count = alive.sum().to(eps.dtype)
+        lowest = torch.full_like(eps, -float("inf"))
+        stats = [torch.where(alive, eps, lowest).max(), torch.where(alive, eps, torch.zeros_like(eps)).sum() / count,
+                 (eps > tolerance).sum().to(eps.dtype), count, propagator.kept.sum().to(eps.dtype)]
+        largest, mean, above, before, kept = torch.stack(stats).tolist()
+        if before == 0:
+            largest = mean = float("nan")
+        exceeding, kept = int(above), int(kept)
+    else:
+        eps = propagator.symplectic_deviation()
+        stats = [eps.max(), eps.mean()] + ([(eps > tolerance).sum().to(eps.dtype)] if tolerance is not None else [])
+        largest, mean, *above = torch.stack(stats).tolist()
+        exceeding, kept = (int(above[0]) if above else None), None
     if log:
         tail = "" if exceeding is None else f"  above {tolerance:g}: {exceeding} of {propagator.ntraj}"
+        if kept is not None:
+            tail += f"  kept {kept} of {propagator.ntraj}"
         logger.info(f" time/fs= {time * units.autime_to_fs}  symplecticity max= {largest:9.3e}  mean= {mean:9.3e}{tail}")
-    return step, largest, mean, exceeding
+    return step, largest, mean, exceeding, kept
 
 
 def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False,
-                    error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None):
+                    error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None, discard_nonsymplectic=False):
     """C_auto(t), k_ic(t) of one batch of trajectories: the device loop leaves the raw per-step sums in a device buffer,
     ``flush`` (None on a single rank) adds the buffers of all ranks -- ONE all-reduce per batch, SURVEY 8e -- and the host
     applies the dynamical phase.  ``norm_every`` > 0 logs the wavefunction norm (the O(n^2) convergence diagnostic of
@@ -259,7 +298,12 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     ``symplecticity_every`` = k > 0 cuts the device loop at every k-th step as well and checks the symplecticity of every
     trajectory's monodromy matrix there (propagator.symplectic_deviation, this rank's trajectories only); the result then ends
     with one more element, a dict with 'steps', 'max' and 'mean' of the deviation per check and, with a
-    ``symplecticity_tolerance``, 'exceeding' (trajectories above it) and 'tolerance'.  Nothing else of the result changes."""
+    ``symplecticity_tolerance``, 'exceeding' (trajectories above it) and 'tolerance'.  Nothing else of the result changes.
+    ``discard_nonsymplectic`` (needs both): every check discards the trajectories above the tolerance for the rest of the batch
+    (propagator.discard_nonsymplectic: samples of value zero, N unchanged); 'max' and 'mean' are then over the trajectories still
+    kept before the check, and the record gains 'kept' (the number kept after every check) and 'discard' = True."""
+    if discard_nonsymplectic and not (symplecticity_every > 0 and symplecticity_tolerance is not None):
+        raise ValueError("discard_nonsymplectic needs symplecticity_every > 0 and a symplecticity_tolerance")
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
     moments = torch.zeros((nt, 6), dtype=torch.float64, device=propagator.device) if errors else None
     blocks = counts = None
@@ -275,7 +319,8 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
             if log:
                 logger.info(f" time/fs= {times[first] * units.autime_to_fs}  norm= {norm:9.6f}")
         if symplecticity_every > 0 and first % symplecticity_every == 0:
-            checks.append(_check_symplecticity(propagator, first, times[first], symplecticity_tolerance, log))
+            checks.append(_check_symplecticity(propagator, first, times[first], symplecticity_tolerance, log,
+                                               discard=discard_nonsymplectic))
         count = stop - first
         pieces.append((first, count, propagator.t))
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
@@ -299,10 +344,12 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         parts = [propagator.finalize_blocks(blocks[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
         tail = (tuple(np.concatenate(part) for part in zip(*parts)) + (np.rint(counts.numpy()).astype(np.int64),),)
     if symplecticity_every > 0:
-        steps, largest, mean, exceeding = zip(*checks)
+        steps, largest, mean, exceeding, kept = zip(*checks)
         record = {'steps': np.asarray(steps, dtype=np.int64), 'max': np.asarray(largest), 'mean': np.asarray(mean)}
         if symplecticity_tolerance is not None:
             record.update(exceeding=np.asarray(exceeding, dtype=np.int64), tolerance=float(symplecticity_tolerance))
+        if discard_nonsymplectic:
+            record.update(kept=np.asarray(kept, dtype=np.int64), discard=True)
         tail = tail + (record,)
     if moments is None:
         parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
@@ -335,6 +382,19 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         raise ConfigurationError(f"'check_symplecticity_every' should be a non-negative integer, got {check_every!r}")
     if tolerance is not None and (isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not tolerance > 0):
         raise ConfigurationError(f"'symplecticity_tolerance' should be a positive number, got {tolerance!r}")
+    # discard the trajectories that fail the check for the rest of their batch (a key the reference does not have)
+    discard = task.get('discard_nonsymplectic', False)
+    if not isinstance(discard, bool):
+        raise ConfigurationError(f"'discard_nonsymplectic' should be true or false, got {discard!r}")
+    if discard and not check_every:
+        raise ConfigurationError("'discard_nonsymplectic' needs 'check_symplecticity_every': k > 0, the steps at which the "
+                                 "trajectories are judged")
+    if discard and tolerance is None:
+        raise ConfigurationError("'discard_nonsymplectic' needs 'symplecticity_tolerance', the deviation above which a trajectory "
+                                 "is discarded")
+    if discard and world > 1:
+        raise ConfigurationError("'discard_nonsymplectic' is not available with more than one rank: the symplecticity check it "
+                                 "rests on is not")
     if check_every and world > 1:
         raise ConfigurationError("'check_symplecticity_every' is not available with more than one rank: the maximum over the "
                                  "trajectories does not fit the one sum all-reduce per batch")
@@ -402,7 +462,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
             raise ConfigurationError(f"'error_blocks' should be a power of two in 2 ... 64 (or 0), got {error_blocks}")
         out = propagate_batch(propagator, setup, dt, nt, times, norm_every=task.get('calc_norm_every', 0), flush=flush,
                               across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks,
-                              symplecticity_every=check_every, symplecticity_tolerance=tolerance)
+                              symplecticity_every=check_every, symplecticity_tolerance=tolerance, discard_nonsymplectic=discard)
         checks = None
         if check_every:
             out, checks = out[:-1], out[-1]

@@ -231,6 +231,8 @@ class HermanKlukPropagator(object):
         # _modal_basis: the constants whose A, B the monodromy blocks are expressed in, None = Cartesian (the identity of t = 0 is
         # the identity in both bases)
         self._modal_step_cache, self._modal_basis = {}, None
+        # discard mask (discard_nonsymplectic): None until the first mark -- every route then runs the launches it always ran
+        self._kept, self._discarded_at, self._kept_count, self._masked_scratch = None, None, None, None
 
         self._prepare()
         self.t = 0.0
@@ -586,23 +588,43 @@ class HermanKlukPropagator(object):
         else:
             check(lib.sc_term_blocks_at(ptr(self._cq), kq, self.ntraj, nblocks, C_void(out), ptr(cursor), self._stream()))
 
+    def _masked_sums(self, has_k, slot_ptr, mom_ptr=None, blk=None):
+        """the sums of the exported terms _cq (and _kq) over the kept trajectories, in place of _reduce_into / _term_moments /
+        _term_blocks: columns 0 ... 3 of the slot at `slot_ptr` (column 4 is not touched), the six moments at `mom_ptr`, the (B, 4)
+        block sums at blk = (address, B) -- one pass, sc_term_masked_sums"""
+        if self._masked_scratch is None:
+            self._masked_scratch = torch.empty(lib.sc_term_masked_scratch_doubles(), dtype=F64, device=self.device)
+        out, nblocks = (None, 0) if blk is None else blk
+        check(lib.sc_term_masked_sums(ptr(self._cq), ptr(self._kq) if has_k else None, ptr(self._kept), self.ntraj, nblocks,
+                                      ptr(self._masked_scratch), C_void(slot_ptr), None if mom_ptr is None else C_void(mom_ptr),
+                                      None if out is None else C_void(out), self._stream()))
+
     def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None, mom_ptr=None, blk=None):
         """per-trajectory terms + their sums for the current state into the 5-double slot at `slot_ptr` (`slot_row`: the same
         five doubles as a tensor, needed when the k_ic sum is formed by torch: position-dependent couplings; `state`: another
         view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi; `mom_ptr`: the six second-moment
         sums go to the 6 doubles there, formed inside the correlate kernel; `blk` = (address, B): the block sums of the step go
-        there -- the terms are exported and sc_term_blocks follows the correlate kernel)"""
+        there -- the terms are exported and sc_term_blocks follows the correlate kernel).  Under a discard mask the correlate kernel
+        only exports the terms; sc_term_masked_sums forms every sum from them."""
         s = self._stream()
         nac = self._nac
         generic = getattr(self, "_nac_generic", None) is not None
-        per_trajectory = per_trajectory or generic or blk is not None
-        in_kernel = mom_ptr is not None and not generic
+        masked = self._kept is not None
+        if masked and generic:
+            raise NotImplementedError("position-dependent derivative couplings are not available once trajectories have been "
+                                      "discarded (discard_nonsymplectic)")
+        per_trajectory = per_trajectory or generic or blk is not None or masked
+        in_kernel = mom_ptr is not None and not generic and not masked
         with self._timed("hk_correlate"):
             check(lib.sc_hk_correlate_m(self._state if state is None else state, self._ovl_t0, nac, ptr(self._vi), ptr(self.probi),
                                         ptr(self._nacq) if nac is not None else None, self._mc_norm(),
                                         ptr(self._cq) if per_trajectory else None,
                                         ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
                                         ptr(self._mpart) if in_kernel else None, s))
+        if masked:
+            assert cursor is None
+            self._masked_sums(nac is not None, slot_ptr, mom_ptr, blk)
+            return
         if blk is not None and not generic:
             self._term_blocks(nac is not None, blk, cursor)
         self._reduce_into(self._cpart, self._gcorr, slot_ptr, cursor, mom_ptr if in_kernel else None, self._gcorr)
@@ -675,8 +697,15 @@ class HermanKlukPropagator(object):
         blocks is the slot row; any linear functional of C(t) or k(t) evaluated per block gives its standard error
         (``hostmath.block_standard_error``, ``rates.rate_standard_error``).  Independent of ``moments``; slots and moments are the
         same bit for bit with or without blocks.
+
+        After ``discard_nonsymplectic`` (a discard mask exists): slots, moments and blocks are the sums over the kept trajectories
+        (``sc_term_masked_sums`` after every correlate launch, the intermediate states of pairs and visits included).  The loop
+        then never runs as the one-launch kernel (it exports no terms) and ``use_graph=True`` raises ``ValueError``.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
+        if use_graph and self._kept is not None:
+            raise ValueError("use_graph=True is not available once trajectories have been discarded (discard_nonsymplectic): the "
+                             "graph replay has no masked reduction")
         dt = float(dt)
         self._remember_nac(potential)
         own = slots is None
@@ -760,8 +789,9 @@ class HermanKlukPropagator(object):
     _whole_loop_ok = True           # WM needs its own per-step kernel between the steps
 
     def _whole_loop_applies(self, desc):
-        return (self._whole_loop_ok and not self.kernel_timing and not getattr(self, "profile_step_kernel", False)
-                and not self._shortcut_applies(desc)
+        # (under a discard mask the sums come from the exported terms, which the whole-loop kernels do not write)
+        return (self._whole_loop_ok and self._kept is None and not self.kernel_timing
+                and not getattr(self, "profile_step_kernel", False) and not self._shortcut_applies(desc)
                 and bool(lib.sc_hk_run_supported(desc, self._hk, self._ovl_t0)))
 
     # run() with a constant dense Hessian: from this many steps on the loop runs in normal-mode coordinates (sc_hk_run_modal; the two
@@ -1152,11 +1182,64 @@ class HermanKlukPropagator(object):
             check(lib.sc_symplectic_deviation(state, ptr(scale), ptr(dev), self._stream()))
         return dev if per_block else dev.max(dim=1).values
 
+    def discard_nonsymplectic(self, tolerance, scale=None):
+        """Discard every trajectory whose monodromy matrix has left the symplectic condition (not in the reference; DESIGN.md
+        section 4.11): runs ``symplectic_deviation(scale)`` and clears the bit of every still-kept trajectory whose deviation
+        eps_i is not <= ``tolerance`` (+inf and NaN included).  Returns the eps tensor (n,) it judged.  No host synchronisation.
+
+        The mask is sticky -- only new initial conditions bring a trajectory back -- and the state kernels do not know it: a
+        discarded trajectory is still propagated, ``y``, ``c2`` and the branch trackers are what they would have been.
+
+        The estimator: a discarded trajectory is a sample of value ZERO, N does not change.  From the mark on ``autocorrelation()``,
+        ``ic_correlation()``, ``standard_errors()`` and ``run()`` (slots, moments, blocks) sum the per-trajectory terms over
+        ``kept`` with the unchanged weights 1/(N prob_i), so the standard errors and the batch-means errors, with their unchanged
+        N and block counts, are the errors of exactly this estimator.  Who prefers the self-normalised estimate multiplies C and k
+        by N / kept_count() of that time; its error is NOT what the moments and blocks estimate, which is why it is not the
+        default.  Until the first call no mask exists and every route runs the launches it always ran; afterwards ``run()`` goes
+        step by step (pairs and visits included, never the one-launch loop) and refuses ``use_graph=True``.
+
+        Works wherever ``symplectic_deviation`` works (row-major and tiled blocks, the normal-mode basis).  Position-dependent
+        derivative couplings are not supported under a mask: ``NotImplementedError``."""
+        tol = float(tolerance)
+        if not tol > 0.0:
+            raise ValueError(f"tolerance has to be positive, got {tolerance!r}")
+        if self._nac_generic is not None:
+            raise NotImplementedError("discard_nonsymplectic is not available with position-dependent derivative couplings: their "
+                                      "k_ic terms are formed outside the masked reduction")
+        dev = self.symplectic_deviation(scale, per_block=True)
+        if self._kept is None:
+            self._kept = torch.ones(self.ntraj, dtype=torch.uint8, device=self.device)
+            self._discarded_at = torch.full((self.ntraj,), -1, dtype=torch.int32, device=self.device)
+            self._kept_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        check(lib.sc_discard_mark(ptr(dev), self.ntraj, tol, self._nsteps, ptr(self._kept), ptr(self._discarded_at),
+                                  ptr(self._kept_count), self._stream()))
+        self._corr_step = -1                  # the sums of the current step were formed under the old mask
+        return dev.max(dim=1).values
+
+    @property
+    def kept(self):
+        """bool tensor (n,): False for the trajectories discard_nonsymplectic has discarded; all True before any mark"""
+        if self._kept is None:
+            return torch.ones(self.ntraj, dtype=torch.bool, device=self.device)
+        return self._kept.bool()
+
+    @property
+    def discarded_at(self):
+        """int32 tensor (n,): the step count of the mark that discarded the trajectory, -1 = kept"""
+        if self._discarded_at is None:
+            return torch.full((self.ntraj,), -1, dtype=torch.int32, device=self.device)
+        return self._discarded_at.clone()
+
+    def kept_count(self):
+        """number of trajectories still kept (a Python int; synchronises)"""
+        return self.ntraj if self._kept_count is None else int(self._kept_count.item())
+
     def semiclassical_prefactor(self):
         return self._sgn * torch.sqrt(self._c2)
 
     def coefficients(self):
-        """expansion coefficients v_i of the wavefunction in the coherent states (reference propagators.py:657-686)"""
+        """expansion coefficients v_i of the wavefunction in the coherent states (reference propagators.py:657-686).
+        The discard mask (discard_nonsymplectic) is ignored: discarded trajectories keep their coefficients."""
         v = self.semiclassical_prefactor() * torch.exp(1j / hbar * self._act) * self._vi
         return v / (self._mc_norm() * self.probi)
 
@@ -1187,6 +1270,8 @@ class HermanKlukPropagator(object):
         the global N as ``ntraj_total`` and every rank makes the call: the ket operands of all ranks are all-gathered,
         every rank sums ITS bras against ALL kets and one all-reduce adds the partial sums -- every rank returns the norm
         of the whole wavefunction.
+
+        The discard mask (discard_nonsymplectic) is ignored: discarded trajectories contribute as ever.
         """
         from . import distributed as Dm
         group = self._norm_group(across_ranks, group)
@@ -1229,7 +1314,8 @@ class HermanKlukPropagator(object):
 
     def wavefunction(self, x):
         """frozen-Gaussian wavefunction psi(x,t) on a spatial grid x (dim,nx) -> complex ndarray (nx,)
-        (reference propagators.py:688-732 with CoherentStatesWavefunction :243-292)"""
+        (reference propagators.py:688-732 with CoherentStatesWavefunction :243-292).  The discard mask (discard_nonsymplectic) is
+        ignored: discarded trajectories contribute as ever."""
         x = torch.as_tensor(x, dtype=F64)
         d, nx = x.shape
         assert d == self.dim, "spatial grid has wrong dimensions"
@@ -1426,11 +1512,13 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         return self._wm_export
 
     def coefficients(self):
-        """coefficients v_n of the Gaussians in the WM wavefunction, eqn (75) (reference propagators.py:1391-1432)"""
+        """coefficients v_n of the Gaussians in the WM wavefunction, eqn (75) (reference propagators.py:1391-1432); the discard
+        mask is ignored, as in HermanKlukPropagator.coefficients"""
         return self._export()[0]
 
     def wavefunction(self, x):
-        """WM wavefunction psi(x,t) on a spatial grid x (dim,nx) -> complex ndarray (nx,) (reference :1434-1482)"""
+        """WM wavefunction psi(x,t) on a spatial grid x (dim,nx) -> complex ndarray (nx,) (reference :1434-1482); the discard
+        mask is ignored"""
         x = torch.as_tensor(x, dtype=F64)
         d, nx = x.shape
         assert d == self.dim, "spatial grid has wrong dimensions"
@@ -1444,7 +1532,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
     def norm(self, across_ranks=False, group=None):
         """norm |psi| of the WM wavefunction, O(n^2) with a d' x d' inverse per pair (reference :1484-1575); rank-local by
         default, across ranks (opt-in) as HermanKlukPropagator.norm: every rank sums its bras against the all-gathered
-        kets, one all-reduce"""
+        kets, one all-reduce.  The discard mask is ignored."""
         from . import distributed as Dm
         group = self._norm_group(across_ranks, group)
         dev, n, d = self.device, self.ntraj, self.dim
@@ -1476,6 +1564,11 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         knows_nac = self._wm_nac_bufs is not None or self._wm_nac_traj is not None
         if self._wm_step != self._nsteps or (knows_nac and not self._wm_has_nac):
             self._wm_launch(0)
+        if self._kept is not None:
+            # discard mask: every sum from the exported terms, over the kept trajectories (sc_term_masked_sums)
+            assert cursor is None
+            self._masked_sums(self._wm_has_nac, slot_ptr, mom_ptr, blk)
+            return
         rows = None
         if mom_ptr is not None:
             # sc_wm_correlate exports every trajectory's terms exactly once (register kernel or its pivoted re-run): their moments,
