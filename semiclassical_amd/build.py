@@ -65,12 +65,11 @@ def _compile(src, extra, tag, verbose):
     return obj
 
 
-def build(force=False, verbose=True, extra=(), out=None, more_sources=(), jobs=None):
-    """``extra``: additional hipcc flags (variant libraries: -DSC_TUNING ...), ``out``: where to write the library,
-    ``more_sources``: translation units outside csrc/ (tools/variants)."""
+def build(force=False, verbose=True, extra=(), out=None, jobs=None):
+    """``extra``: additional hipcc flags (variant libraries: -DSC_TUNING ...), ``out``: where to write the library."""
     if out is None and not extra and not force and not needs_build():
         return LIB
-    srcs = sources() + list(more_sources)
+    srcs = sources()
     tag = hashlib.sha256(" ".join(extra).encode()).hexdigest()[:8] if extra else ""
     # one hipcc per source, bounded by the CPUs this process may use (a shared host shows more than it grants) and MAX_JOBS
     jobs = jobs or min(len(srcs), len(os.sched_getaffinity(0)), int(os.environ.get("MAX_JOBS") or 16))
@@ -94,5 +93,4 @@ if __name__ == "__main__":
     flags = [a for a in argv if a != "--force"]
     if flags and target is None:
         sys.exit("extra compiler flags make a variant library: name it with --out PATH (the product library is built without)")
-    variants = sorted(glob.glob(os.path.join(ROOT, "tools", "variants", "*.hip"))) if "-DSC_TUNING" in flags else []
-    print(build(force="--force" in argv, extra=flags, out=target, more_sources=variants))
+    print(build(force="--force" in argv, extra=flags, out=target))

@@ -30,7 +30,7 @@ struct MonoArgs {
     const double *hess;         // [n][4][D][D] stage Hessians, or [D][D] when hess_stride == 0 (constant Hessian)
     int64_t hess_stride;        // doubles between the Hessian blocks of consecutive trajectories (4 D D or 0)
     int64_t stage_stride;       // doubles between consecutive stages (D D or 0)
-    double *msum;               // [n][4][D][D] RK4 sums of the monodromy blocks (only the D > 64 kernel)
+    double *msum;               // [n][4][D][D] RK4 sums of the monodromy blocks (the caller's scratch; no kernel of this file reads it)
     int panel;                  // columns of M R formed at a time in the prefactor kernel (LDS budget)
     double dt;
     int mode;                   // 0: after a step, 1: tracker initialisation (prefactor kernel only)
@@ -159,107 +159,17 @@ __global__ __launch_bounds__(128 * NT, 1) void dense_mono_mfma_kernel(MonoArgs A
     }
 }
 
-// The same RK4 for 64 < D <= 96 (NT = 5, 6).  The register file of one CU no longer holds the whole step: a workgroup
-// has NT wavefronts (one 16-column tile each) and does the two plane pairs one after the other; X0 / Y0 are re-read
-// from the (still unmodified) state at every stage and the RK4 sums live in a global scratch of the size of the
-// state (A.msum), so only the stage matrices and the accumulators stay in registers.  One Hessian image in LDS
-// (rows padded to 112 doubles), staged per stage and pair.
-#define HSB 112
-template <int NT, int KT>
-__global__ __launch_bounds__(64 * NT, 1) void dense_mono_mfma_big_kernel(MonoArgs A) {
-    extern __shared__ double2 smem2[];           // Hessian image [16 NT][HSB], 1/m [128]
-    constexpr int HB = 16 * NT * HSB;
-    double *Hs0 = (double *)smem2, *wm = Hs0 + HB;
-    const int D = A.st.dim, DD = D * D, tid = threadIdx.x, nth = 64 * NT;
-    const int lane = tid & 63, jt = tid >> 6;
-    const int col = 16 * jt + (lane & 15), rg = lane >> 4;
-    const bool colok = col < D;
-    const unsigned toff = (unsigned)(rg * D + col);
-    const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
-    for (int i = tid; i < 128; i += nth) wm[i] = i < D ? A.inv_mass[i] : 0.0;
-    for (int e = tid; e < HB; e += nth) Hs0[e] = 0.0;
-    __syncthreads();
-    for (int64_t tr = blockIdx.x; tr < A.st.n; tr += gridDim.x) {
-        const double *Hg = A.hess + tr * A.hess_stride;
-#pragma unroll 1
-        for (int pair = 0; pair < 2; ++pair) {
-            double *Mx = A.st.mono + tr * 4 * (int64_t)DD + (int64_t)pair * DD, *My = Mx + 2 * (int64_t)DD;
-            double *Sx = A.msum + tr * 4 * (int64_t)DD + (int64_t)pair * DD, *Sy = Sx + 2 * (int64_t)DD;
-            double Xs[NT][4], Ys[NT][4];
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const bool ok = colok && 16 * t + rg + 4 * r < D;
-                    Xs[t][r] = ok ? (Mx + (16 * t + 4 * r) * D)[toff] : 0.0;
-                    Ys[t][r] = ok ? (My + (16 * t + 4 * r) * D)[toff] : 0.0;
-                }
-#pragma unroll 1
-            for (int st = 0; st < 4; ++st) {
-                __syncthreads();                         // everybody is done with the previous image
-                const double *Hst = Hg + st * A.stage_stride;
-                for (int e = tid; e < DD; e += nth) Hs0[(e / D) * HSB + (e % D)] = Hst[e];
-                __syncthreads();
-                d4 acc[NT];
-#pragma unroll
-                for (int I = 0; I < NT; ++I) acc[I] = (d4){0.0, 0.0, 0.0, 0.0};
-                const double *arow = Hs0 + rg * HSB + (lane & 15);
-                double a_cur[NT], a_nxt[NT];
-#pragma unroll
-                for (int I = 0; I < NT; ++I) a_cur[I] = arow[16 * I];
-#pragma unroll
-                for (int kt = 0; kt < KT; ++kt) {
-                    if (kt + 1 < KT) {
-#pragma unroll
-                        for (int I = 0; I < NT; ++I) a_nxt[I] = arow[4 * (kt + 1) * HSB + 16 * I];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    const double b = Xs[kt >> 2][kt & 3];
-#pragma unroll
-                    for (int I = 0; I < NT; ++I)
-                        acc[I] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_cur[I], b, acc[I], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int I = 0; I < NT; ++I) a_cur[I] = a_nxt[I];
-                }
-                const double wgt = (st == 0 || st == 3) ? 1.0 : 2.0, c = (st == 2) ? dt : hh;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool ok = colok && 16 * t + rg + 4 * r < D;
-                        if (ok) {
-                            // wave-uniform row bases + one per-thread 32-bit offset (no hoisted 64-bit offsets)
-                            const int rowoff = (16 * t + 4 * r) * D;
-                            double *mx = Mx + rowoff, *my = My + rowoff, *sxp = Sx + rowoff, *syp = Sy + rowoff;
-                            const double kx = wm[16 * t + rg + 4 * r] * Ys[t][r], ky = -acc[t][r];
-                            const double x0 = mx[toff], y0 = my[toff];
-                            const double sx = (st == 0 ? 0.0 : sxp[toff]) + wgt * kx, sy = (st == 0 ? 0.0 : syp[toff]) + wgt * ky;
-                            if (st < 3) {
-                                sxp[toff] = sx; syp[toff] = sy;
-                                Xs[t][r] = fma(c, kx, x0);
-                                Ys[t][r] = fma(c, ky, y0);
-                            } else {
-                                mx[toff] = fma(h6, sx, x0);
-                                my[toff] = fma(h6, sy, y0);
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
+#define HSB 112       // row stride (doubles) of the Hessian image in LDS for 64 < D <= 96
 
-// 64 < D <= 96 with the whole RK4 step in registers (round 2; replaces the global-scratch kernel above as the default).
+// 64 < D <= 96 (NT = 5, 6) with the whole RK4 step in registers (round 2; the kernel before it kept the RK4 sums in a global
+// scratch of the size of the state and re-read X0 / Y0 at every stage).
 // The equations of motion couple the ROWS of a monodromy block through H but not its columns: a 16-column tile of
 // X = [Mqq|Mqp] together with the same tile of Y = [Mpq|Mpp] is an independent problem.  So a trajectory is cut into
 // slabs of four column tiles; a 256-thread workgroup takes one slab, every wavefront one tile for ALL rows, and keeps
 // X0, Y0, the stage matrices and the RK4 sums of its tile in registers (24 NT doubles + accumulators: the kernel is
 // compiled for one wave per SIMD = 512 registers).  No scratch traffic at all: per trajectory the state is read and
 // written once (2 x 4 D^2 x 8 B) and the four stage Hessians are read once per slab (2 NT / 4 slabs), against ~3 MB
-// through the global scratch of dense_mono_mfma_big_kernel.  One Hessian image in LDS (rows padded to 112 doubles); the
+// through such a scratch.  One Hessian image in LDS (rows padded to 112 doubles); the
 // next stage's image is fetched into registers behind the current stage's MFMAs.
 // DMA (round 3): the stage Hessians go from L2 / HBM straight into the LDS image with 16-byte LDS-DMA loads
 // (global_load_lds_dwordx4: no registers, no index arithmetic per element -- the register path spent ~2400 instructions per
@@ -856,10 +766,6 @@ extern "C" int sc_dense_mono_step(const sc_state *st, const sc_hk_consts *hk, co
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
             cus = 256;
         const int nt = (D + 15) / 16;
-        bool use_big = false;                     // the global-scratch kernel: kept for A/B in the tuning build
-#ifdef SC_TUNING
-        use_big = nt > 4 && getenv("SC_MONO_BIG") != nullptr;
-#endif
         const size_t rk4_lds = nt <= 4 ? ((size_t)2 * 16 * nt * HS + 64 + (size_t)2 * nt * (nt < 4 ? 2 : 1) * 4 * nt * 64) * sizeof(double)
                                        : ((size_t)16 * nt * HSB + 128) * sizeof(double);
 #define SC_LAUNCH_MONO(KERNEL_, NT_, KT_, WGS_, THREADS_)                                                          \
@@ -867,7 +773,7 @@ extern "C" int sc_dense_mono_step(const sc_state *st, const sc_hk_consts *hk, co
             if (hipFuncSetAttribute((const void *)KERNEL_<NT_, KT_>,                                                \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rk4_lds) != hipSuccess)        \
                 return sc_check_launch("sc_dense_mono_step (LDS attribute)");                                       \
-            const int64_t g_ = (int64_t)cus * (WGS_), items_ = st->n * (nt > 4 && !use_big ? (2 * nt + 3) / 4 : 1); \
+            const int64_t g_ = (int64_t)cus * (WGS_), items_ = st->n * (nt > 4 ? (2 * nt + 3) / 4 : 1);             \
             hipLaunchKernelGGL((KERNEL_<NT_, KT_>), dim3((unsigned)(items_ < g_ ? items_ : g_)),                    \
                                dim3(THREADS_), rk4_lds, s, a);                                                      \
         } while (0)
@@ -899,20 +805,13 @@ extern "C" int sc_dense_mono_step(const sc_state *st, const sc_hk_consts *hk, co
         case 4 * NT_ - 2: SC_LAUNCH_MONO(KERNEL_, NT_, 4 * NT_ - 2, WGS_, THREADS_); break;                         \
         case 4 * NT_ - 1: SC_LAUNCH_MONO(KERNEL_, NT_, 4 * NT_ - 1, WGS_, THREADS_); break;                         \
         case 4 * NT_: SC_LAUNCH_MONO(KERNEL_, NT_, 4 * NT_, WGS_, THREADS_); break;
-        if (use_big) {
-            switch ((D + 3) / 4) {
-                SC_MONO_CASES(dense_mono_mfma_big_kernel, 5, 1, 320)
-                SC_MONO_CASES(dense_mono_mfma_big_kernel, 6, 1, 384)
-            }
-        } else {
-            switch ((D + 3) / 4) {
-                SC_MONO_CASES(dense_mono_mfma_kernel, 1, 8, 128)
-                SC_MONO_CASES(dense_mono_mfma_kernel, 2, 4, 256)
-                SC_MONO_CASES(dense_mono_mfma_kernel, 3, 1, 384)
-                SC_MONO_CASES(dense_mono_mfma_kernel, 4, 1, 512)
-                SC_SLAB_CASES(5)
-                SC_SLAB_CASES(6)
-            }
+        switch ((D + 3) / 4) {
+            SC_MONO_CASES(dense_mono_mfma_kernel, 1, 8, 128)
+            SC_MONO_CASES(dense_mono_mfma_kernel, 2, 4, 256)
+            SC_MONO_CASES(dense_mono_mfma_kernel, 3, 1, 384)
+            SC_MONO_CASES(dense_mono_mfma_kernel, 4, 1, 512)
+            SC_SLAB_CASES(5)
+            SC_SLAB_CASES(6)
         }
 #undef SC_MONO_CASES
 #undef SC_SLAB_CASES
@@ -921,10 +820,7 @@ extern "C" int sc_dense_mono_step(const sc_state *st, const sc_hk_consts *hk, co
         const int rc = sc_check_launch("sc_dense_mono_step (RK4)");
         if (rc) return rc;
     }
-    bool reg_lu = hk->diag && st->flags != nullptr;       // diagonal widths: determinant in registers, LDS kernel as the fix-up
-#ifdef SC_TUNING
-    if (getenv("SC_PREFACTOR_LDS")) reg_lu = false;
-#endif
+    const bool reg_lu = hk->diag && st->flags != nullptr; // diagonal widths: determinant in registers, LDS kernel as the fix-up
     if (reg_lu) {
         if (hipMemsetAsync(st->flags + st->n, 0, sizeof(int32_t), s) != hipSuccess)
             return sc_check_launch("sc_dense_mono_step (flag counter)");

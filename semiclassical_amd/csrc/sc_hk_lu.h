@@ -209,12 +209,9 @@ __device__ __forceinline__ void publish_pivot_row(const cplx (&m)[NR][NR], cplx 
 // whose row lies beyond D are skipped.  The order in which rows are eliminated does not change the determinant.
 __device__ __forceinline__ bool pivot_step_valid(int kt, int nk) { return 4 * (kt & 3) + (kt >> 2) < nk; }
 
-// SC_LU_PEEL_LAST: the LAST pivot step of a full block KB < NR - 1 updates the trailing (N-1) x (N-1) row / column slots only -- row
-// slot KB and column slot KB are never read again, and nobody publishes behind it.  The step is peeled off the loop statically (its
-// leaf set of N - 1 column entries sits behind the loop, the loop itself is unchanged).
-#ifndef SC_LU_PEEL_LAST
-#define SC_LU_PEEL_LAST 1
-#endif
+// PEEL (eliminate_block): the LAST pivot step of a full block KB < NR - 1 updates the trailing (N-1) x (N-1) row / column slots only
+// -- row slot KB and column slot KB are never read again, and nobody publishes behind it.  The step is peeled off the loop statically
+// (its leaf set of N - 1 column entries sits behind the loop, the loop itself is unchanged).
 // pivot-column entries of the row slots BELOW slot KB only
 template <int NR, int KB>
 __device__ __forceinline__ void column_fetch_below(const cplx (&m)[NR][NR], cplx (&c)[NR], int pl) {
@@ -252,7 +249,7 @@ __device__ __forceinline__ void eliminate_block(cplx (&m)[NR][NR], cplx *detbuf,
     bool live = FULL ? true : 16 * KB + tj < D;
     barrier();
     if (ti == 0) publish_pivot_row<NR, KB, RW>(m, detbuf, live, 0, seq, rowbuf, pivrec, weak, tid);
-    constexpr bool PEEL = SC_LU_PEEL_LAST != 0 && FULL;
+    constexpr bool PEEL = FULL;
     int kend = PEEL ? 15 : 16;
     if constexpr (TRIM_LAST && !FULL) {
         // the wave's last own valid step is 4 jl + w (16-lane row jl of wave w holds block row 4 w + jl); it is published inside the

@@ -216,9 +216,6 @@ __global__ __launch_bounds__(256) void hk_step_kernel(StepArgs A) {
 }  // namespace
 
 int sc_launch_step_sd(const StepArgs &a, hipStream_t s);   // sc_hk_step_sd.hip
-#ifdef SC_TUNING
-int sc_launch_step_rw(const StepArgs &a, hipStream_t s);   // tools/variants/sc_hk_step_rw.hip
-#endif
 
 static int step_threads(int D) { return D * D <= 256 ? 64 : 256; }
 
@@ -252,22 +249,13 @@ extern "C" int sc_hk_step(const sc_potential *pot, const sc_state *st, const sc_
                        "diagonal-width fast path (sc_mono_convert the state first)");
     int dbg = 0;
 #ifdef SC_TUNING   // experiment knobs exist only in the tuning build (tools/mkvar.sh); the product library reads no environment
-    if (getenv("SC_FORCE_GENERAL_STEP")) fast = false;
     dbg = getenv("SC_DEBUG_SKIP_LU") ? 0x100 : 0;      // the fix-up launch is skipped (the ablated kernel is a variant library, SC_SD_ABLATE_LU)
 #endif
     if (fast) {
         StepArgs a{*pot, *st, *hk, dt, mode | dbg, energy_partials, sc_step_grid(st->n, st->dim)};
-#ifdef SC_TUNING
-        // SC_FAST_KERNEL=rw: the rejected row-wave layout of tools/variants/sc_hk_step_rw.hip
-        const char *which = getenv("SC_FAST_KERNEL");
-        if (which && which[0] == 'r') return sc_launch_step_rw(a, (hipStream_t)stream);
-#endif
         // 13 <= D <= 16: hk_step_w16_kernel pivots over the whole row (no flags, no cursor, no fix-up launch); D <= 12:
         // hk_step_sep16_kernel eliminates in a fixed order and flags weak pivots like the 256-thread kernel
-        bool small = D > SC_SEP16_MAX_D && D <= 16;
-#ifdef SC_TUNING
-        if (getenv("SC_NO_WAVE_KERNEL")) small = false;      // the 256-thread kernel is forced: it needs flags and cursor
-#endif
+        const bool small = D > SC_SEP16_MAX_D && D <= 16;
         if (!(mode & 0x400)) {      // 0x400 (internal, sc_hk_step_multi): the fast kernels have run, only the fix-up is wanted
             // flags[n]: trajectories flagged in this step, flags[n + 1]: trajectory cursor of the fast kernel
             if (!small && st->flags && hipMemsetAsync(st->flags + st->n, 0, 2 * sizeof(int32_t), (hipStream_t)stream) != hipSuccess)

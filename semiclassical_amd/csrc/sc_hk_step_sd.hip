@@ -27,7 +27,7 @@
 //            16-lane group and are fetched with DPP row_newbcast.  The four waves are NOT barrier-coupled:
 //            consumers poll a tag in the pivot record (see eliminate_block); one barrier in front of the first
 //            block and one behind the last.  The last pivot step of a full block updates only the trailing slots
-//            (SC_LU_PEEL_LAST, sc_hk_lu.h).  Pivot products (with the signs of the column choices) accumulate in
+//            (PEEL of eliminate_block, sc_hk_lu.h).  Pivot products (with the signs of the column choices) accumulate in
 //            LDS per row group; thread 0 multiplies them while the others stream the next trajectory.
 //            If the best in-block pivot is more than 16x smaller than the largest live entry of the row, the
 //            trajectory is flagged (sc_state.flags) and its determinant is recomputed by the fully pivoted
@@ -39,65 +39,30 @@
 #include "sc_hk_lu.h"
 #include "sc_row16.h"
 
-#ifndef SC_SD_DEPTH
-#define SC_SD_DEPTH 1      // row slots whose loads are in flight together (1: the schedule up to round 2)
-#endif
-#ifndef SC_SD_XPREFETCH
-#define SC_SD_XPREFETCH 1  // request row slot 0 of the next trajectory before the last diagonal block of the elimination
-#endif
-#ifndef SC_SD_XPREFETCH2
-#define SC_SD_XPREFETCH2 1 // also row slot 1 of the next trajectory (both raw buffers are free during the last diagonal block): -3 %
-#endif
-#ifndef SC_SD_XPREFETCH_AHEAD
-#define SC_SD_XPREFETCH_AHEAD 1   // diagonal blocks of the elimination that run after the next trajectory's first requests
-#endif
-// cache-policy bits of the block loads / stores (gfx942+: 1 = sc0, 2 = nt, 16 = sc1).  The blocks are touched once per step
-// and the state (11.5 GB) is far beyond every cache: non-temporal on BOTH sides is worth 2.6 % (4.69 -> 4.56 ms; loads
-// alone: nothing, stores alone: -0.5 %, scope bits: nothing).  TILED layout only: there a wave instruction covers 512
-// contiguous bytes; on the 128-byte row segments of the row-major order (unaligned at D = 60) the same hint costs 45 %
-// (4.9 -> 7.2 ms), as it does on the 8-byte-per-lane row accesses of the small-D kernels
-#ifndef SC_SD_LOAD_AUX
-#define SC_SD_LOAD_AUX 2
-#endif
-#ifndef SC_SD_MULTI_LOAD_AUX            // first sub-step of a multi-step visit whose intermediate sub-steps store their blocks
-#define SC_SD_MULTI_LOAD_AUX 2
-#endif
-#ifndef SC_SD_NOSTORE_LOAD_AUX          // ... whose intermediate sub-steps do not: the later sub-steps read the SAME lines again, so the first
-#define SC_SD_NOSTORE_LOAD_AUX 0        // load has to allocate in the L2 / memory-side cache (non-temporal: the re-read comes from HBM)
-#endif
-#ifndef SC_SD_MULTI_MID_AUX             // stores of an intermediate sub-step (where there are any), loads of every later sub-step
-#define SC_SD_MULTI_MID_AUX 0
-#endif
-#ifndef SC_SD_NOSTORE_MIN_NR            // multi-step visits: smallest NR whose intermediate sub-steps store no blocks (see KS > 1 below)
-#define SC_SD_NOSTORE_MIN_NR 3
-#endif
-#ifndef SC_SD_STORE_AUX
-#define SC_SD_STORE_AUX 2
-#endif
-#ifndef SC_SD_DIRECT_P
-#define SC_SD_DIRECT_P 0     // 1: every thread loads the P_a of its rows itself (no LDS hand-over, one barrier less per
-                           // trajectory) -- measured 4.65 ms against 4.56 ms: rejected
-#endif
+// test aids of variant libraries (tools/phase_timing.py, the fix-up tests), not schedules
 #ifndef SC_SD_ABLATE_LU
 #define SC_SD_ABLATE_LU 0  // 1: variant library without the elimination (streaming phase alone)
 #endif
 #ifndef SC_SD_FORCE_FIXUP
 #define SC_SD_FORCE_FIXUP 0
 #endif
-#ifndef SC_SD_DEFER_TAIL
-#define SC_SD_DEFER_TAIL 1   // the determinant tail of item t runs inside phase B of item t + 1 (see "The determinant tail" below); 0: behind the end barrier
-#endif
-#ifndef SC_SD_TRIM_LAST
-#define SC_SD_TRIM_LAST 1    // last diagonal block without the steps nobody reads (TRIM_LAST of eliminate_block, sc_hk_lu.h)
-#endif
-#ifndef SC_SD_BLOCK_BARRIER
-#define SC_SD_BLOCK_BARRIER no_barrier     // wg_barrier: a workgroup barrier in front of every diagonal block
-#endif
 
 namespace {
 
 typedef unsigned int sc_v2u __attribute__((ext_vector_type(2)));
 typedef unsigned int sc_v4u __attribute__((ext_vector_type(4)));
+
+// cache-policy bits of the block loads / stores (gfx942+: 1 = sc0, 2 = nt, 16 = sc1).  The blocks are touched once per step
+// and the state (11.5 GB) is far beyond every cache: non-temporal on BOTH sides is worth 2.6 % (4.69 -> 4.56 ms; loads
+// alone: nothing, stores alone: -0.5 %, scope bits: nothing).  TILED layout only: there a wave instruction covers 512
+// contiguous bytes; on the 128-byte row segments of the row-major order (unaligned at D = 60) the same hint costs 45 %
+// (4.9 -> 7.2 ms), as it does on the 8-byte-per-lane row accesses of the small-D kernels
+constexpr int AUX_NT = 2;        // non-temporal: the load of a one-step item, the first load of a visit whose intermediate sub-steps store
+                                 // their blocks, the last store of every item or visit
+constexpr int AUX_PLAIN = 0;     // stores of an intermediate sub-step (where there are any) and loads of every later sub-step; the first
+                                 // load of a visit whose intermediate sub-steps store nothing: the later sub-steps read the SAME lines again,
+                                 // so it has to allocate in the L2 / memory-side cache (non-temporal: the re-read comes from HBM)
+constexpr int NOSTORE_MIN_NR = 3;   // multi-step visits: smallest NR whose intermediate sub-steps store no blocks (see KS > 1 below)
 
 // TILED: the monodromy blocks of a trajectory are stored as 16 x 16 tiles (sc_state.mono_layout = 1, see the header):
 // tile (ra, rb) holds its part of Mqq, Mqp, Mpq, Mpp one after the other, each row-major inside the tile.  With the
@@ -108,7 +73,7 @@ typedef unsigned int sc_v4u __attribute__((ext_vector_type(4)));
 // KS > 1 (sc_hk_step_multi: KS = 2; sc_hk_step_visit: KS = 2 .. 4): KS consecutive time steps per VISIT of a trajectory; every sub-step is the one-step kernel's
 // stream-eliminate sequence, the next one follows at once by the same threads at the same addresses.  Two schemes, chosen per NR at
 // compile time (mid_store below; measurements and what else was tried: docs/NOTEBOOK.md sections 9 and 9.2):
-//   NR >= SC_SD_NOSTORE_MIN_NR (D > 32), store-free: only the LAST sub-step of a visit stores the blocks.  An earlier sub-step ks
+//   NR >= NOSTORE_MIN_NR (D > 32), store-free: only the LAST sub-step of a visit stores the blocks.  An earlier sub-step ks
 //     loads the blocks of the visit's start, applies P(0) .. P(ks) (prop[0..ks], kept in LDS for the whole visit), forms its
 //     prefactor matrix and determinant and stores nothing: nobody outside the kernel reads the blocks between the sub-steps, and
 //     the intermediate store was a full HBM write pass.  Every later sub-step loads the SAME blocks again and redoes the earlier
@@ -119,14 +84,14 @@ typedef unsigned int sc_v4u __attribute__((ext_vector_type(4)));
 //     non-temporal.  Until the last sub-step's stores the blocks in memory are those of the visit's start.  Per time step the
 //     blocks cross HBM 2 / KS times, and sub-step ks redoes ks rotations: (KS - 1) / 2 per time step on top of its own, in a
 //     kernel bound by FP64 issue -- measured at n = 1e5: KS = 3 is the fastest for every NR >= 3 (docs/NOTEBOOK.md section 9.3).
-//   NR < SC_SD_NOSTORE_MIN_NR (D <= 32), the scheme of round 4: every sub-step stores; intermediate stores and the loads that
+//   NR < NOSTORE_MIN_NR (D <= 32), the scheme of round 4: every sub-step stores; intermediate stores and the loads that
 //     follow them are plain (they meet in the cache), the first load and the last store of a visit non-temporal.  There the kernel
 //     waits for round trips, not for HBM, and the redone rotation is latency it cannot hide (store-free measured 0.6 - 2.6 % slower).
 // Either way the kernel is bound by the elimination (FP64 VALU issue), no longer by HBM.
-// The determinant tail (SC_SD_DEFER_TAIL).  An ITEM is one sub-step of one trajectory.  Its tail -- the product of the signed
+// The determinant tail.  An ITEM is one sub-step of one trajectory.  Its tail -- the product of the signed
 // pivots (lu_partial_products, finish_determinant), the weak / zero-pivot handling, the branch rule and the stores of c2 / sgn /
-// c2_mid / sgn_mid / flags -- is one lane's serial work on wave 0 and computes nothing another wave needs.  It used to stand
-// between the end barrier of item t and the first barrier of item t + 1, where waves 1 - 3 waited for it.  Now thread 0 (threads
+// c2_mid / sgn_mid / flags -- is one lane's serial work on wave 0 and computes nothing another wave needs.  It does not stand
+// between the end barrier of item t and the first barrier of item t + 1, where waves 1 - 3 would wait for it: thread 0 (threads
 // 0 - 15 for the partial products) runs the tail of item t INSIDE phase B of item t + 1, between the request of a row slot (slot 2,
 // or the last one for NR < 3) and the arithmetic on it, where wave 0 waits for memory anyway; the tail's own loads are issued behind
 // that slot's, so it waits for nothing the wave would not have waited for.  The last item of a workgroup has no next phase B: its
@@ -170,13 +135,13 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     const int pc_blk = g_sd_clock == nullptr ? -1 : (blockIdx.x == 0 ? 0 : (blockIdx.x == 512 ? 1 : -1));
     int pc_item = 0;
 #endif
-    // KS > 1: do the intermediate sub-steps of a visit store their blocks (NR < SC_SD_NOSTORE_MIN_NR), or does the last one redo them?
-    constexpr bool mid_store = KS > 1 && NR < SC_SD_NOSTORE_MIN_NR;
+    // KS > 1: do the intermediate sub-steps of a visit store their blocks (NR < NOSTORE_MIN_NR), or does the last one redo them?
+    constexpr bool mid_store = KS > 1 && NR < NOSTORE_MIN_NR;
     constexpr int NP = mid_store ? 1 : KS;
     // NR = 4 with four sub-steps: P_a requested during the previous elimination is one value too many for 128 registers (hipcc spills it
     // behind s_waitcnt vmcnt(0) in the middle of the last diagonal block); there it is requested at the top of the sub-step instead
     constexpr bool late_p = KS >= 4 && NR >= 4;
-    constexpr int aux_first = KS == 1 ? SC_SD_LOAD_AUX : (mid_store ? SC_SD_MULTI_LOAD_AUX : SC_SD_NOSTORE_LOAD_AUX);   // first load of a visit
+    constexpr int aux_first = (KS == 1 || mid_store) ? AUX_NT : AUX_PLAIN;   // first load of a visit
     __shared__ double prop[NP][4 * 64];      // P_a = (p11, p12, p21, p22) of row a; without intermediate stores one set per sub-step of a visit
     __shared__ double scl[4 * 64];           // st, 1/st, si, 1/si
     __shared__ cplx rowbuf[16][64];
@@ -189,7 +154,6 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     __shared__ double tailkeep[4];           // thread 0, deferred tail of a visit: (Re c2, Im c2, sgn) of the sub-step before
     __shared__ long long tailtr;             // wave 0, deferred tail: the trajectory whose last sub-step waits for its tail (no register across the elimination)
 
-    static_assert(KS == 1 || !SC_SD_DIRECT_P || NR < SC_SD_NOSTORE_MIN_NR, "a later sub-step of a visit needs the row propagators of the earlier ones (prop[])");
     const int D = A.st.dim, DD = D * D, tid = threadIdx.x;
     constexpr bool do_step = STEP;                   // false: prefactor and tracker initialisation only (t = 0)
     constexpr int NCL_BASE = 16 * (NR - 1);          // first column of the last column tile
@@ -211,11 +175,12 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     int seq0 = 0;                                  // tags of this workgroup's pivot records: unique per (trajectory, block)
     int par = 0;
     // raw[s][p][rb]: the four planes (Mqq, Mqp, Mpq, Mpp) of row slot ra = s (mod 2); prv: this thread's element of the
-    // row propagators P_a (st.work, computed by hk_modes_kernel, "phase A").  With SC_SD_XPREFETCH slot 0 and prv of the
-    // NEXT trajectory are requested before the last diagonal block of the current elimination starts (most of the matrix
-    // registers are dead by then): the first load round trip of a trajectory hides behind that block.
+    // row propagators P_a (st.work, computed by hk_modes_kernel, "phase A"), handed to the rows' threads through prop[].  Slots 0
+    // and 1 and prv of the NEXT item are requested before the last diagonal block of the current elimination starts (most of
+    // the matrix registers are dead by then, both raw buffers are free): the first load round trip of an item hides behind
+    // that block.
     double raw[2][4][NR];
-    double pv[2][4] = {{1.0, 0.0, 0.0, 1.0}, {1.0, 0.0, 0.0, 1.0}};     // SC_SD_DIRECT_P: P_a of the thread's row of slot ra = s (mod 2)
+    double pv[2][4] = {{1.0, 0.0, 0.0, 1.0}, {1.0, 0.0, 0.0, 1.0}};     // written by the dead block of load_slot only (see there)
     double prv = 0.0;
     bool first = true;
     // Trajectories are handed out through a device-side cursor (sc_state.flags[n + 1], zeroed by sc_hk_step): the first
@@ -226,7 +191,9 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
     // barrier of the elimination.  Without sc_state.flags: static stride.
     int *cursor = A.st.flags ? A.st.flags + A.st.n + 1 : nullptr;
     int64_t trn = 0;
-    constexpr bool defer_tail = SC_SD_DEFER_TAIL != 0;
+    // every tail is deferred (see "The determinant tail").  The constant is named once, in item_tail, for the compiler's sake alone:
+    // without that capture hipcc assigns the registers of every NR >= 2 instantiation differently; it goes with the dead block of load_slot
+    constexpr bool defer_tail = true;
     constexpr bool skip_lu = SC_SD_ABLATE_LU != 0;
     // the tail of sub-step kp of trajectory tp, whose results lie in the buffers of parity parp: determinant from the signed pivots,
     // weak / zero pivots, branch rule, stores.  `tl`: the thread's index as the caller has it; tp < 0: the trajectory wave 0 left in
@@ -242,12 +209,12 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         cplx *c2_out = kp == KS - 1 ? c2 + tp : (cplx *)MA.c2_mid + ((int64_t)kp * A.st.n + tp);
         double *sg_out = kp == KS - 1 ? A.st.sgn + tp : MA.sgn_mid + ((int64_t)kp * A.st.n + tp);
         const int *weak = &weakbuf[parp];
-        // the predecessor FIRST (thread 0): from LDS where the tail of the sub-step before left it, otherwise (sub-step 0, or tails
-        // that are not deferred) from memory -- requested here so that the partial products below run under the round trip
+        // the predecessor FIRST (thread 0): from LDS where the tail of the sub-step before left it, otherwise (sub-step 0) from
+        // memory -- requested here so that the partial products below run under the round trip
         constexpr bool kept = defer_tail && kp > 0;
         cplx prev = c_make(0.0, 0.0);
         double sg = 1.0;
-        if (defer_tail && tl == 0 && do_step) {
+        if (tl == 0 && do_step) {
             if (kept) { prev = c_make(tailkeep[0], tailkeep[1]); sg = tailkeep[2]; }
             else { prev = *c2_in; sg = *sg_in; }
         }
@@ -256,8 +223,8 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
             // c2 / sgn are left to the fully pivoted fallback, which tracks against the state's c2 / sgn: after an
             // intermediate sub-step those are KS steps old, so hand it this sub-step's predecessor (c2_mid / sgn_mid)
             if (KS > 1) {
-                c2[tp] = defer_tail ? prev : *c2_in;
-                A.st.sgn[tp] = defer_tail ? sg : *sg_in;
+                c2[tp] = prev;
+                A.st.sgn[tp] = sg;
             }
             A.st.flags[tp] = 1;
             atomicAdd(&A.st.flags[A.st.n], 1);   // lets the fix-up launch return at once when nothing was flagged
@@ -266,7 +233,6 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
             const cplx c2new = (*weak & 2) ? c_make(0.0, 0.0) : finish_determinant(detbuf[parp], rows_odd);
             double sgnew = 1.0;
             if (do_step) {
-                if (!defer_tail) { prev = *c2_in; sg = *sg_in; }
                 const bool flip = crossed_branch_cut(prev, c2new);
                 sgnew = flip ? -sg : sg;
                 if (KS > 1) *sg_out = sgnew;
@@ -275,14 +241,14 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
                 *sg_out = 1.0;
             }
             *c2_out = c2new;
-            if (defer_tail && kp < KS - 1) { tailkeep[0] = c2new.x; tailkeep[1] = c2new.y; tailkeep[2] = sgnew; }
+            if (kp < KS - 1) { tailkeep[0] = c2new.x; tailkeep[1] = c2new.y; tailkeep[2] = sgnew; }
         }
     };
     for (int64_t tr = blockIdx.x; tr < A.st.n; tr = trn) {
       sfor<0, KS>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::value;                 // sub-step of this visit
-        constexpr int aux_load = ks == 0 ? aux_first : SC_SD_MULTI_MID_AUX;
-        constexpr int aux_store = ks == KS - 1 ? SC_SD_STORE_AUX : SC_SD_MULTI_MID_AUX;
+        constexpr int aux_load = ks == 0 ? aux_first : AUX_PLAIN;
+        constexpr int aux_store = ks == KS - 1 ? AUX_NT : AUX_PLAIN;
         constexpr bool store_blocks = ks == KS - 1 || mid_store; // otherwise an intermediate sub-step leaves the blocks in memory alone
         // what is streamed next: the next sub-step of this trajectory, or the first one of the next trajectory
         constexpr int ksn = ks + 1 < KS ? ks + 1 : 0;
@@ -357,9 +323,11 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
                     }
                 }
             }
-            if (SC_SD_DIRECT_P && do_step) {
-                // the four entries of P_a of this thread's row come straight from st.work (the 16 threads of a row read the
-                // same address; rows beyond D: offset beyond the resource, zeros): no LDS hand-over, no barrier
+            if (false && do_step) {
+                // DEAD: the rejected direct load of P_a (every thread reads the P_a of its rows itself, no LDS hand-over: 4.65 ms
+                // against 4.56 ms).  It and pv[] are all that is left of that experiment: without them hipcc assigns the registers
+                // of every NR >= 2 instantiation differently (same counts, no spills), so they go only with an A/B measurement on
+                // the GPU (docs/NOTEBOOK.md, closing note)
                 const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(A.st.work + t * 4 * (int64_t)Dl, 0, 32 * Dl, 0x00020000);
                 const unsigned vw = 16 * ra + til < Dl ? 8u * (unsigned)(16 * ra + til) : OOB;
 #pragma unroll
@@ -371,12 +339,12 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         };
         auto first_requests = [&](int64_t t, auto ksnc) {    // P_a and row slot 0 of sub-step ksnc of trajectory t
             constexpr int k2 = decltype(ksnc)::value;
-            constexpr int aux2 = k2 == 0 ? aux_first : SC_SD_MULTI_MID_AUX;
+            constexpr int aux2 = k2 == 0 ? aux_first : AUX_PLAIN;
             const double *wk = KS > 1 ? MA.work + (int64_t)k2 * A.st.n * 4 * Dl : A.st.work;
-            if (!SC_SD_DIRECT_P && do_step && pa < Dl) prv = wk[(t * 4 + pk) * (int64_t)Dl + pa];
+            if (do_step && pa < Dl) prv = wk[(t * 4 + pk) * (int64_t)Dl + pa];
             load_slot(std::integral_constant<int, 0>(), t, std::integral_constant<int, aux2>());
-            // SC_SD_XPREFETCH2: row slot 1 as well (both raw buffers are free during the last diagonal block)
-            if (SC_SD_XPREFETCH2 && NR > 1) load_slot(std::integral_constant<int, (NR > 1 ? 1 : 0)>(), t, std::integral_constant<int, aux2>());
+            // row slot 1 as well (both raw buffers are free during the last diagonal block): -3 %
+            if (NR > 1) load_slot(std::integral_constant<int, (NR > 1 ? 1 : 0)>(), t, std::integral_constant<int, aux2>());
         };
         auto finish_slot = [&](auto rac) {
             constexpr int ra = decltype(rac)::value;
@@ -397,8 +365,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
                 });
             }
             constexpr int kq = mid_store ? 0 : ks;
-            const double p11 = SC_SD_DIRECT_P ? pv[ra & 1][0] : prop[kq][al], p12 = SC_SD_DIRECT_P ? pv[ra & 1][1] : prop[kq][64 + al];
-            const double p21 = SC_SD_DIRECT_P ? pv[ra & 1][2] : prop[kq][128 + al], p22 = SC_SD_DIRECT_P ? pv[ra & 1][3] : prop[kq][192 + al];
+            const double p11 = prop[kq][al], p12 = prop[kq][64 + al], p21 = prop[kq][128 + al], p22 = prop[kq][192 + al];
             const double sta = scl[al], ista = scl[64 + al];
 #pragma unroll
             for (int rb = 0; rb < NR; ++rb) {
@@ -453,13 +420,12 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         if constexpr (late_p) {                          // not requested during the previous elimination (see late_p)
             if (!first && do_step && pa < Dl) prv = MA.work[(((int64_t)ks * A.st.n + tr) * 4 + pk) * (int64_t)Dl + pa];
         }
-        if (first || !SC_SD_XPREFETCH || NR == 1) first_requests(tr, ksc);
+        if (first || NR == 1) first_requests(tr, ksc);
         const bool had_item = !first;                    // deferred tail: is there an item before this one?
         first = false;
         __builtin_amdgcn_sched_barrier(0);
-        if (NR > 1 && SC_SD_DEPTH > 1) load_slot(std::integral_constant<int, (NR > 1 ? 1 : 0)>(), tr, std::integral_constant<int, aux_load>());
-        __builtin_amdgcn_sched_barrier(0);
-        if (do_step && !SC_SD_DIRECT_P) {
+        __builtin_amdgcn_sched_barrier(0);        // both stay: dropping one changes the generated code
+        if (do_step) {
             // every wave is past the previous visit's phase B of this sub-step (the elimination barriers lie in between), so
             // prop[ks] may be overwritten without another barrier; the sets of the earlier sub-steps of this visit stay
             if (pa < D) prop[mid_store ? 0 : ks][64 * pk + pa] = prv;
@@ -467,12 +433,11 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         }
         sfor<0, NR>([&](auto rac) {
             constexpr int ra = decltype(rac)::value;
-            // SC_SD_XPREFETCH2: slots 0 and 1 were requested during the previous elimination (requesting slot 2 before slot 1 is
-            // finished as well: 4 spilled registers, 0.5 % slower)
-            if (SC_SD_DEPTH == 1 && ra > (SC_SD_XPREFETCH2 ? 1 : 0)) load_slot(rac, tr, std::integral_constant<int, aux_load>());
-            if (SC_SD_DEPTH > 1 && ra + 1 < NR && ra > 0) load_slot(std::integral_constant<int, (ra + 1 < NR ? ra + 1 : 0)>(), tr, std::integral_constant<int, aux_load>());
+            // slots 0 and 1 were requested during the previous elimination; every later slot is requested when the one before it is
+            // finished (requesting slot 2 before slot 1 is finished as well: 4 spilled registers, 0.5 % slower)
+            if (ra > 1) load_slot(rac, tr, std::integral_constant<int, aux_load>());
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (defer_tail && ra == (NR < 3 ? NR - 1 : 2)) {
+            if constexpr (ra == (NR < 3 ? NR - 1 : 2)) {
                 // the tail of the item before this one (see "The determinant tail"), while this slot's loads are in flight
                 if constexpr (ks > 0) item_tail(std::integral_constant<int, ks - 1>(), tr, par ^ 1, tl);
                 else if (had_item) item_tail(std::integral_constant<int, KS - 1>(), -1, par ^ 1, tl);
@@ -497,50 +462,39 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
         // consumed step s - 4, and a ring entry is rewritten 16 steps after its last use.
         __syncthreads();
         SD_TICK(2);
-        auto wg_barrier = [] { __syncthreads(); };
-        auto no_barrier = [] {};
-        (void)no_barrier; (void)wg_barrier;
+        auto no_barrier = [] {};       // no barrier in front of a diagonal block: the RESET BARRIER is block 0's, later blocks need none
         sfor<0, NR>([&](auto kbc) {
             constexpr int KB = decltype(kbc)::value;
             if (ks == 0 && KB == (NR > 1 ? 1 : 0)) { // behind the RESET BARRIER (NR = 1: the value is read after the last barrier)
                 if (NR > 1) trn = cursor ? (int64_t)gridDim.x + __builtin_amdgcn_readfirstlane(nextbuf[par]) : tr + gridDim.x;
             }
-            if (SC_SD_XPREFETCH && NR > 1 && KB == (NR - SC_SD_XPREFETCH_AHEAD > 1 ? NR - SC_SD_XPREFETCH_AHEAD : 1)) {
+            if (NR > 1 && KB == (NR > 2 ? NR - 1 : 1)) {       // the next item's first requests, in front of the last diagonal block
                 const int64_t tnext = ks + 1 < KS ? tr : trn;
                 if (tnext < A.st.n) {
                     if constexpr (late_p) {         // the row slots only: P_a follows at the top of the sub-step
-                        constexpr int auxn = ksn == 0 ? aux_first : SC_SD_MULTI_MID_AUX;
+                        constexpr int auxn = ksn == 0 ? aux_first : AUX_PLAIN;
                         load_slot(std::integral_constant<int, 0>(), tnext, std::integral_constant<int, auxn>());
-                        if (SC_SD_XPREFETCH2) load_slot(std::integral_constant<int, 1>(), tnext, std::integral_constant<int, auxn>());
+                        load_slot(std::integral_constant<int, 1>(), tnext, std::integral_constant<int, auxn>());
                     } else {
                         first_requests(tnext, std::integral_constant<int, ksn>());
                     }
                 } else {                            // nothing follows: end the live ranges of the old values
                     prv = 0.0;
 #pragma unroll
-                    for (int pl = 0; pl < 4; ++pl) {
-                        pv[0][pl] = 0.0;
+                    for (int pl = 0; pl < 4; ++pl)
 #pragma unroll
-                        for (int rb = 0; rb < NR; ++rb) {
-                            raw[0][pl][rb] = 0.0;
-                            if (SC_SD_XPREFETCH2) raw[1][pl][rb] = 0.0;
-                        }
-                    }
+                        for (int rb = 0; rb < NR; ++rb) { raw[0][pl][rb] = 0.0; raw[1][pl][rb] = 0.0; }
                 }
             }
-            if (!skip_lu) {
-                constexpr bool trim = SC_SD_TRIM_LAST != 0;
-                if (KB == 0) eliminate_block<NR, KB, 64, trim>(m, detbuf[par], D, seq0 + 1 + KB, rowbuf, pivrec, weak, tl, no_barrier);   // the RESET BARRIER is its barrier
-                else eliminate_block<NR, KB, 64, trim>(m, detbuf[par], D, seq0 + 1 + KB, rowbuf, pivrec, weak, tl, SC_SD_BLOCK_BARRIER);
-            }
+            // TRIM_LAST: the last diagonal block without the steps nobody reads (sc_hk_lu.h)
+            if (!skip_lu) eliminate_block<NR, KB, 64, true>(m, detbuf[par], D, seq0 + 1 + KB, rowbuf, pivrec, weak, tl, no_barrier);
         });
         SD_TICK(3);
         __syncthreads();
         SD_TICK(4);
         if (ks == 0 && NR == 1) trn = cursor ? (int64_t)gridDim.x + __builtin_amdgcn_readfirstlane(nextbuf[par]) : tr + gridDim.x;
         // no barrier after this: the buffers of this parity are next written two items on
-        if constexpr (defer_tail) { if (ks == KS - 1 && tl == 0) tailtr = tr; }       // its tail runs inside the next item, or in the epilogue
-        else item_tail(ksc, tr, par, tl);
+        if (ks == KS - 1 && tl == 0) tailtr = tr;       // the item's tail runs inside the next item, or in the epilogue
         seq0 += 4; par ^= 1;
         SD_TICK(5);
 #ifdef SD_PHASE_CLOCK
@@ -549,7 +503,7 @@ __global__ __launch_bounds__(256, MINW) void hk_step_sd_kernel(StepArgs A, Multi
       });
     }
     // epilogue: the tail of the workgroup's last item, behind that item's end barrier
-    if (defer_tail && !first) item_tail(std::integral_constant<int, KS - 1>(), -1, par ^ 1, tid);
+    if (!first) item_tail(std::integral_constant<int, KS - 1>(), -1, par ^ 1, tid);
 }
 
 #ifdef SD_PHASE_CLOCK
@@ -774,28 +728,16 @@ __global__ __launch_bounds__(256) void hk_step_w16_kernel(StepArgs A) {
 
 }  // namespace
 
-#ifdef SC_TUNING
-int sc_launch_step_ws(const StepArgs &a, hipStream_t s);       // tools/variants/sc_hk_step_ws.hip (measured, not adopted)
-#endif
-
 // launch the fast path; the caller has validated the arguments (separable potential, diag prefactor, D <= 64)
 int sc_launch_step_sd(const StepArgs &a, hipStream_t s) {
     const int D = a.st.dim, nr = (D + 15) / 16, grid = sc_step_grid(a.st.n, D);
     int occ = 4;
-    bool wave_kernel = D <= 16;
 #ifdef SC_TUNING
     if (const char *occ_env = getenv("SC_SD_OCC")) occ = atoi(occ_env);   // waves per SIMD the NR=4 kernel is compiled for
-    if (getenv("SC_NO_WAVE_KERNEL")) wave_kernel = false;
 #endif
-    if (wave_kernel) {
-        bool packed = true;
-#ifdef SC_TUNING
-        if (getenv("SC_NO_SEP16")) packed = false;
-#endif
-        if (packed) {
-            const int rc = sc_launch_step_sep16(a, grid, s);      // four trajectories per wavefront
-            if (rc != 0) return rc < 0 ? rc : SC_OK;
-        }
+    if (D <= 16) {
+        const int rc = sc_launch_step_sep16(a, grid, s);      // four trajectories per wavefront
+        if (rc != 0) return rc < 0 ? rc : SC_OK;
         // partial sums: only the first `wg` entries are written, the energy guard adds sc_step_grid() of them
         const int64_t quads = (a.st.n + 3) / 4;
         const int wg = (int)(quads < 2048 ? quads : 2048);
@@ -808,22 +750,13 @@ int sc_launch_step_sd(const StepArgs &a, hipStream_t s) {
     if ((a.mode & 0xff) == 0) hipLaunchKernelGGL(hk_modes_kernel, dim3(grid), dim3(256), 0, s, a);
     const bool step = (a.mode & 0xff) == 0;
     const bool tiled = a.st.mono_layout == SC_MONO_TILED16;
-#ifdef SC_TUNING
-    // SC_WS=1: the wave-specialised schedule (one producer + three eliminator groups per CU).  Measured on MI355X at
-    // n = 1e5, D = 60: 6.71 ms against 5.98 ms of this kernel -- the eliminations are bound by VALU issue, not by their
-    // latency, so giving them a CU of their own does not help (docs/NOTEBOOK.md section 8).
-    if (nr == 4 && step && a.mode == 0 && getenv("SC_WS")) return sc_launch_step_ws(a, s);
-#endif
-    int sdgrid = grid;         // the energy partials belong to hk_modes_kernel: this kernel's grid is free
-#ifdef SC_TUNING
-    if (const char *g = getenv("SC_SD_GRID")) sdgrid = (int)std::min<int64_t>(a.st.n, atoi(g));
-#endif
+    // the energy partials belong to hk_modes_kernel: this kernel's grid is free
 #define SC_LAUNCH_SD(NR_, OCC_)                                                                                         \
     do {                                                                                                                \
-        if (step && tiled) hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, true, true>), dim3(sdgrid), dim3(256), 0, s, a, MultiArgs{});   \
-        else if (step) hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, true, false>), dim3(sdgrid), dim3(256), 0, s, a, MultiArgs{});     \
-        else if (tiled) hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, false, true>), dim3(sdgrid), dim3(256), 0, s, a, MultiArgs{});    \
-        else hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, false, false>), dim3(sdgrid), dim3(256), 0, s, a, MultiArgs{});              \
+        if (step && tiled) hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, true, true>), dim3(grid), dim3(256), 0, s, a, MultiArgs{});   \
+        else if (step) hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, true, false>), dim3(grid), dim3(256), 0, s, a, MultiArgs{});     \
+        else if (tiled) hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, false, true>), dim3(grid), dim3(256), 0, s, a, MultiArgs{});    \
+        else hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, false, false>), dim3(grid), dim3(256), 0, s, a, MultiArgs{});              \
     } while (0)
     switch (nr) {
         case 1: SC_LAUNCH_SD(1, 4); break;
@@ -842,51 +775,48 @@ int sc_launch_step_sd(const StepArgs &a, hipStream_t s) {
     return sc_check_launch("sc_hk_step (separable/diagonal fast path)");
 }
 
-// KS = 3, 4 time steps per visit (sc_hk_step_visit; validated by the caller as for sc_launch_step_sd_multi, and 32 < D <= 64: the
-// store-free scheme): hk_modes_multi_kernel<KS>, then the block kernel with KS sub-steps per trajectory.
+// KS time steps per visit (the caller has validated: separable potential, diagonal widths, 16 < D <= 64, tiled blocks, flags
+// present): hk_modes_multi_kernel<KS>, then the block kernel with KS sub-steps per trajectory.  KS = 2 is sc_hk_step_multi's
+// launch, with its own labels and NR = 2 (D <= 32, intermediate stores) as well; KS = 3, 4 exist for the store-free scheme only.
 template <int KS>
 static int launch_step_sd_visit(const StepArgs &a, const sc_multi_scratch &ms, hipStream_t s) {
+    constexpr bool pair = KS == 2;
     const int D = a.st.dim, nr = (D + 15) / 16, grid = sc_step_grid(a.st.n, D);
     ModesMultiArgs mm{ms.work, ms.qp_mid, ms.act_mid};
     hipLaunchKernelGGL(hk_modes_multi_kernel<KS>, dim3(grid), dim3(256), 0, s, a, mm);
-    int rc = sc_check_launch("sc_hk_step_visit (modes)");
+    int rc = sc_check_launch(pair ? "sc_hk_step_multi (modes)" : "sc_hk_step_visit (modes)");
     if (rc) return rc;
     MultiArgs ma{ms.work, ms.c2_mid, ms.sgn_mid, ms.unrepaired};
-    switch (nr) {
-        case 3: hipLaunchKernelGGL((hk_step_sd_kernel<3, 4, true, true, KS>), dim3(grid), dim3(256), 0, s, a, ma); break;
-        case 4: hipLaunchKernelGGL((hk_step_sd_kernel<4, 4, true, true, KS>), dim3(grid), dim3(256), 0, s, a, ma); break;
-        default: return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_visit: %d steps per visit at D = %d", KS, D);
-    }
-    return sc_check_launch("sc_hk_step_visit (KS steps per visit)");
-}
-
-// KS time steps per visit (sc_hk_step_multi: two, sc_hk_step_visit: two to four; the caller has validated: separable potential,
-// diagonal widths, 16 < D <= 64, tiled blocks, flags present): hk_modes_multi_kernel<KS>, then the block kernel with KS sub-steps
-// per trajectory.
-int sc_launch_step_sd_multi(const StepArgs &a, const sc_multi_scratch &ms, int ksteps, hipStream_t s) {
-    if (ksteps == 3) return launch_step_sd_visit<3>(a, ms, s);
-    if (ksteps == 4) return launch_step_sd_visit<4>(a, ms, s);
-    if (ksteps != 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_visit: %d steps per visit", ksteps);
-    const int D = a.st.dim, nr = (D + 15) / 16, grid = sc_step_grid(a.st.n, D);
-    ModesMultiArgs mm{ms.work, ms.qp_mid, ms.act_mid};
-    hipLaunchKernelGGL(hk_modes_multi_kernel<2>, dim3(grid), dim3(256), 0, s, a, mm);
-    int rc = sc_check_launch("sc_hk_step_multi (modes)");
-    if (rc) return rc;
-    MultiArgs ma{ms.work, ms.c2_mid, ms.sgn_mid, ms.unrepaired};
-    switch (nr) {
-        case 2: hipLaunchKernelGGL((hk_step_sd_kernel<2, 4, true, true, 2>), dim3(grid), dim3(256), 0, s, a, ma); break;
-        case 3: hipLaunchKernelGGL((hk_step_sd_kernel<3, 4, true, true, 2>), dim3(grid), dim3(256), 0, s, a, ma); break;
+#define SC_LAUNCH_VISIT(NR_, OCC_) hipLaunchKernelGGL((hk_step_sd_kernel<NR_, OCC_, true, true, KS>), dim3(grid), dim3(256), 0, s, a, ma)
+    switch (nr < (pair ? 2 : 3) ? 0 : nr) {
+        case 2: if constexpr (pair) SC_LAUNCH_VISIT(2, 4); break;
+        case 3: SC_LAUNCH_VISIT(3, 4); break;
         case 4:
 #ifdef SC_TUNING
-            if (const char *occ_env = getenv("SC_SD_OCC")) {
-                if (atoi(occ_env) == 3) { hipLaunchKernelGGL((hk_step_sd_kernel<4, 3, true, true, 2>), dim3(grid), dim3(256), 0, s, a, ma); break; }
-                if (atoi(occ_env) == 2) { hipLaunchKernelGGL((hk_step_sd_kernel<4, 2, true, true, 2>), dim3(grid), dim3(256), 0, s, a, ma); break; }
+            if constexpr (pair) {
+                if (const char *occ_env = getenv("SC_SD_OCC")) {
+                    if (atoi(occ_env) == 3) { SC_LAUNCH_VISIT(4, 3); break; }
+                    if (atoi(occ_env) == 2) { SC_LAUNCH_VISIT(4, 2); break; }
+                }
             }
 #endif
-            hipLaunchKernelGGL((hk_step_sd_kernel<4, 4, true, true, 2>), dim3(grid), dim3(256), 0, s, a, ma); break;
-        default: return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_multi: D = %d", D);
+            SC_LAUNCH_VISIT(4, 4); break;
+        default:
+            return pair ? sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_multi: D = %d", D)
+                        : sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_visit: %d steps per visit at D = %d", KS, D);
     }
-    return sc_check_launch("sc_hk_step_multi (two steps per visit)");
+#undef SC_LAUNCH_VISIT
+    return sc_check_launch(pair ? "sc_hk_step_multi (two steps per visit)" : "sc_hk_step_visit (KS steps per visit)");
+}
+
+// sc_hk_step_multi: ksteps = 2, sc_hk_step_visit: two to four
+int sc_launch_step_sd_multi(const StepArgs &a, const sc_multi_scratch &ms, int ksteps, hipStream_t s) {
+    switch (ksteps) {
+        case 2: return launch_step_sd_visit<2>(a, ms, s);
+        case 3: return launch_step_sd_visit<3>(a, ms, s);
+        case 4: return launch_step_sd_visit<4>(a, ms, s);
+        default: return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_step_visit: %d steps per visit", ksteps);
+    }
 }
 
 #ifdef LU_PIVOT_CLOCK

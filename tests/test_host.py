@@ -209,6 +209,25 @@ def test_cursor_handover_is_fenced_in_the_source():
     assert re.search(r"nextbuf\[tid\] = 0; weakbuf\[tid\] = 0;", src)
 
 
+def test_headline_kernel_source_holds_one_schedule():
+    """the source of hk_step_sd_kernel shows the schedule that ships: its only compile-time switches are the test aids a
+    committed tool drives, and the tuning build reads two environment names"""
+    import glob
+    csrc = os.path.join(ROOT, "semiclassical_amd", "csrc")
+    tested = set()
+    for name in ("sc_hk_step_sd.hip", "sc_hk_lu.h"):
+        for line in open(os.path.join(csrc, name)):
+            m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif)\b(.*)", line.split("//")[0])
+            if m:
+                tested |= set(re.findall(r"[A-Za-z_]\w*", m.group(2))) - {"defined"}
+    env = set()
+    for f in glob.glob(os.path.join(csrc, "*.hip")):
+        env |= set(re.findall(r'getenv\(\s*"([^"]*)"', open(f).read()))
+    why = "an experiment's switch is removed from the source when the experiment is decided (its numbers stay in docs/NOTEBOOK.md)"
+    assert tested == {"SC_SD_ABLATE_LU", "SC_SD_FORCE_FIXUP", "SD_PHASE_CLOCK", "LU_PIVOT_CLOCK", "SC_TUNING"}, (why, sorted(tested))
+    assert env == {"SC_SD_OCC", "SC_DEBUG_SKIP_LU"}, (why, sorted(env))
+
+
 def test_step_physics_is_defined_once_in_the_source():
     """the per-mode RK4 (the only caller of sep_eval) and the branch rule of the sqrt tracker are written out in
     csrc/sc_common.h alone: every kernel calls sep_mode_rk4 / crossed_branch_cut"""

@@ -4,7 +4,7 @@ wrong order, is invisible on the benchmark's diagonal blocks (zeros stay zeros u
 DENSE states of tests/lu_trim_inputs.py.  The bar is bit-identity with two sc_hk_step launches: sep_propagate_row is explicit fma,
 the recomputed M1 has the bits the one-step kernel stores and reloads.
 
-The store-free scheme is compiled for NR >= 3 (D > 32, SC_SD_NOSTORE_MIN_NR in csrc/sc_hk_step_sd.hip): D = 33, 48, 60, 64 run the new
+The store-free scheme is compiled for NR >= 3 (D > 32, NOSTORE_MIN_NR in csrc/sc_hk_step_sd.hip): D = 33, 48, 60, 64 run the new
 code; D = 17 and 20 (NR = 2) run the pair kernel that still stores after every sub-step and are here so that both sides of that
 switch meet the same bar on dense blocks."""
 import numpy as np

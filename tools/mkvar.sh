@@ -1,5 +1,5 @@
 #!/bin/bash
-# build the current tree as a TUNING library (-DSC_TUNING: environment knobs, rejected kernel variants) for A/B runs:  tools/mkvar.sh NAME [extra hipcc flags]   -> var/libsc_NAME.so
+# build the current tree as a TUNING library (-DSC_TUNING: environment knobs) for A/B runs:  tools/mkvar.sh NAME [extra hipcc flags]   -> var/libsc_NAME.so
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift

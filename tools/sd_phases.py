@@ -5,7 +5,7 @@ wave of workgroups 0 and 512 at six points of every item (variant library built 
     tools/mkvar.sh sdclock -DSD_PHASE_CLOCK
     SC_LIB_PATH=$PWD/var/libsc_sdclock.so python tools/sd_phases.py [pairs|single|visit3|visit4]
 
-With the deferred tail (SC_SD_DEFER_TAIL, sc_hk_step_sd.hip) thread 0 finishes the determinant of item t inside the streaming phase
+With the deferred tail ("The determinant tail", sc_hk_step_sd.hip) thread 0 finishes the determinant of item t inside the streaming phase
 of item t + 1: "determinant / sign" then holds the item's bookkeeping only, and the tail shows as wave 0's longer streaming phase.
 """
 import ctypes
