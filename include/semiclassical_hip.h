@@ -508,6 +508,26 @@ int sc_pair_sum(const double *X1, const double *Y1, int32_t K1, const double *X2
                 const double *rs, const double *ib, const double *ik, const double *wb, const double *wk,
                 int64_t n, double *partials, void *stream);
 
+/* Reduced density of the frozen-Gaussian wavepacket along M directions u_d on a grid s[ns], behind
+ * HermanKlukPropagator.reduced_density() (not in the reference):
+ *   rho[d][k] = sqrt(h_d / pi) sum_ij wb_i wk_j exp( E_ij + beta^2 h_d - (s_k - m)^2 h_d + i 2 h_d (s_k - m) beta )   (complex),
+ * E_ij the pair exponent of sc_pair_sum_rect from the same operands X1 ... wk, m = a_bra[d][i] + a_ket[d][j],
+ * beta = b_ket[d][j] - b_bra[d][i], h_d = inv_two_sigma2[d], s_k = s[k] - s_origin[d] (the caller centres the positions on a
+ * point c and passes u_d.c).  With a = u_d.q / 2, b = u_d^T (2 Gamma_t)^+ p / hbar and
+ * 1 / h_d = 2 u_d^T (2 Gamma_t)^+ u_d its real part is  int |psi(x)|^2 delta(s_k - u_d.x) dx.
+ *   a_bra, b_bra [M][ni], a_ket, b_ket [M][nj] (trajectory index fastest), inv_two_sigma2, s_origin [M], s [ns], rho [M][ns] complex;
+ *   partials: scratch of sc_density_pair_sum_rows(ni, nj) * M * ns * 2 doubles (bra bands x shares of the kets), free again when
+ *   the call's work on `stream` has run.
+ * Two launches; one writer per output, no floating-point atomics, summation order a function of the shapes alone: the same bits
+ * in every run.  K1 <= 1024, K2 <= 1536 (D <= 512), ni <= 64 * 65535, M * ceil(ns / 256) < 2^24 -- one call takes the whole grid,
+ * the caller does not split it; beyond: SC_ERR_UNSUPPORTED.  A null pointer, M < 1, ns < 1 or K < 1: SC_ERR_BAD_ARGUMENT. */
+int64_t sc_density_pair_sum_rows(int64_t ni, int64_t nj);
+int sc_density_pair_sum(const double *X1, const double *Y1, int32_t K1, const double *X2, const double *Y2, int32_t K2,
+                        const double *rs_i, const double *rs_j, const double *ib, const double *ik, const double *wb,
+                        const double *wk, int64_t ni, int64_t nj, const double *a_bra, const double *b_bra,
+                        const double *a_ket, const double *b_ket, const double *inv_two_sigma2, int32_t M,
+                        const double *s, const double *s_origin, int32_t ns, double *partials, double *rho, void *stream);
+
 /* Frozen-Gaussian wavefunction on a spatial grid behind HermanKlukPropagator.wavefunction() (propagators.py:252-292,
  * 688-732):  phi[k] = fac sum_n v_n exp(-1/2 |Lx_k - Lq_n|^2 + i (p_n.x_k - pq_n)),  L = Gamma_t^(1/2).
  * LqT, PT [D][n] (trajectory index fastest), pq [n], v [n] complex, Lx, X [nx][D], phi [nx] complex. */

@@ -1312,6 +1312,100 @@ class HermanKlukPropagator(object):
         Dm.all_reduce_sum(slot, group)
         return float(torch.sqrt(slot[0]).item())
 
+    def _density_directions(self, directions):
+        """(M, D) fp64 host tensor of the directions of reduced_density: mode indices -> unit vectors, or the vectors given"""
+        d = self.dim
+        arr = np.asarray(directions)
+        if arr.dtype == bool or arr.size == 0:
+            raise ValueError("directions: mode indices or vectors of length D are expected")
+        if np.issubdtype(arr.dtype, np.integer) and arr.ndim <= 1:
+            idx = arr.reshape(-1)
+            if ((idx < 0) | (idx >= d)).any():
+                raise ValueError(f"directions: mode index outside 0 ... {d - 1}: {idx.tolist()}")
+            U = torch.zeros((idx.shape[0], d), dtype=F64)
+            U[torch.arange(idx.shape[0]), torch.from_numpy(idx.astype(np.int64))] = 1.0
+            return U
+        U = torch.as_tensor(arr, dtype=F64)
+        if U.dim() == 1:
+            U = U.unsqueeze(0)
+        if U.dim() != 2 or U.shape[1] != d:
+            raise ValueError(f"directions: vectors of length {d} are expected, got shape {tuple(arr.shape)}")
+        if not bool(torch.isfinite(U).all()):
+            raise ValueError("directions: non-finite component")
+        return U.contiguous()
+
+    def reduced_density(self, directions, s):
+        """Marginal density of the wavepacket along chosen directions (not in the reference):
+
+            rho_u(s) = int |psi(x)|^2 delta(s - u.x) dx
+                     = Re sum_ij v_i^* v_j O_ij (2 pi sigma^2)^-1/2 exp(-(s - mu_ij)^2 / (2 sigma^2)),
+            sigma^2 = u^T B u,  mu_ij = u.(q_i + q_j) / 2 + i u^T B (p_j - p_i) / hbar,  B = (2 Gamma_t)^+,
+
+        O_ij the overlaps and v the coefficients of ``norm()``: the integral of rho_u over s is ``norm()**2``.
+
+        ``directions``: an int or a sequence of ints (mode indices k -> unit vectors e_k), or an array (D,) or (M, D) of real
+        vectors u, not necessarily normalised (integers in a flat sequence are always mode indices).  ``s``: 1-D array of grid
+        values, in any order.  Returns a real ndarray (M, ns).
+
+        A direction has to lie in the range of Gamma_t (the marginal along a null direction of a singular Gamma_t does not
+        exist): ``ValueError`` otherwise, as for a direction of the wrong length, a zero direction, a mode index out of range and
+        an empty or non-finite grid.  For a singular Gamma_t the result is the real part of the formula with the
+        pseudo-inverse and pseudo-determinant conventions of the overlaps.
+
+        The pair sum runs in ``sc_density_pair_sum`` on the operands ``norm()`` packs (positions centred on the ensemble mean,
+        the grid shifted by u.centre).  Rank-local: this rank's trajectories with this rank's weights, no communication.  The
+        discard mask (discard_nonsymplectic) is ignored: discarded trajectories contribute as ever.  The state is not touched."""
+        dev, d, n = self.device, self.dim, self.ntraj
+        U = self._density_directions(directions)
+        sg = torch.as_tensor(np.asarray(s, dtype=np.float64))
+        if sg.dim() != 1 or sg.shape[0] == 0:
+            raise ValueError(f"s: a non-empty 1-D grid is expected, got shape {tuple(sg.shape)}")
+        if not bool(torch.isfinite(sg).all()):
+            raise ValueError("s: non-finite grid value")
+        oc = hostmath.OverlapConstants(self._Gt, self._Gt)
+        unorm = torch.linalg.norm(U, dim=1)
+        if bool((unorm == 0).any()):
+            raise ValueError("directions: zero vector")
+        # Gamma_t Gamma_t^+ = 2 Gamma_t (2 Gamma_t)^+ = 2 C projects onto the range of Gamma_t
+        outside = torch.linalg.norm(U - 2.0 * (U @ oc.C.T), dim=1) > 1.0e-8 * unorm
+        if bool(outside.any()):
+            raise ValueError(f"directions: direction(s) {torch.nonzero(outside).flatten().tolist()} outside the range of Gamma_t: "
+                             "the marginal along a null direction does not exist")
+        UB = U @ oc.B                                       # rows u^T B (B symmetric)
+        sigma2 = (UB * U).sum(1)
+        M, ns = U.shape[0], sg.shape[0]
+        A, B, Cm = (m.to(dev) for m in (oc.A, oc.B, oc.C))
+        # the operands of norm() (rank-local), packed the same way
+        centre = self._qp[:, :d].sum(0) / float(n)
+        q = self._qp[:, :d] - centre.unsqueeze(0)
+        p = self._qp[:, d:]
+        Aq, Bp, Cp = q @ A.T, p @ B.T / hbar ** 2, p @ Cm.T / hbar
+        X1 = torch.cat((q, p), 1).contiguous()
+        Y1 = torch.cat((Aq, Bp), 1).contiguous()
+        X2 = torch.cat((q, Cp, q), 1).contiguous()
+        Y2 = torch.cat((p / hbar, -q, -Cp), 1).contiguous()
+        rs = (-0.5 * (q * Aq).sum(1) - 0.5 * (p * Bp).sum(1)).contiguous()
+        cc = (q * Cp).sum(1)
+        ib = cc.contiguous()
+        ik = (cc - (p * q).sum(1) / hbar).contiguous()
+        v = self.coefficients()
+        wb, wk = (oc.fac * v.conj()).contiguous(), v.contiguous()
+        # per direction: a = u.q / 2, b = u^T B p / hbar (rows [M][n]), 1 / (2 sigma^2) and the grid's origin u.centre
+        Ud = U.to(dev)
+        a = (0.5 * (Ud @ q.T)).contiguous()
+        b = (UB.to(dev) @ p.T / hbar).contiguous()
+        h = (0.5 / sigma2).to(dev).contiguous()
+        origin = (Ud @ centre).contiguous()
+        sd = sg.to(dev).contiguous()
+        rows = lib.sc_density_pair_sum_rows(n, n)
+        partials = torch.empty((rows, M * ns, 2), dtype=F64, device=dev)
+        rho = torch.empty((M, ns, 2), dtype=F64, device=dev)
+        with self._timed("reduced_density"):
+            check(lib.sc_density_pair_sum(ptr(X1), ptr(Y1), 2 * d, ptr(X2), ptr(Y2), 3 * d, ptr(rs), ptr(rs), ptr(ib), ptr(ik),
+                                          ptr(wb), ptr(wk), n, n, ptr(a), ptr(b), ptr(a), ptr(b), ptr(h), M, ptr(sd), ptr(origin),
+                                          ns, ptr(partials), ptr(rho), self._stream()))
+        return rho[:, :, 0].cpu().numpy()
+
     def wavefunction(self, x):
         """frozen-Gaussian wavefunction psi(x,t) on a spatial grid x (dim,nx) -> complex ndarray (nx,)
         (reference propagators.py:688-732 with CoherentStatesWavefunction :243-292).  The discard mask (discard_nonsymplectic) is
@@ -1557,6 +1651,10 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         check(lib.sc_reduce_slot(ptr(partials), int(tiles), None, 0, 1.0, ptr(slot), s))
         Dm.all_reduce_sum(slot, group)
         return float(torch.sqrt(slot[0]).item())
+
+    def reduced_density(self, directions, s):
+        raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
+                                  "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
     def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, mom_ptr=None, blk=None):
         # the per-trajectory terms were produced together with the prefactor; recompute (with the stored branch
