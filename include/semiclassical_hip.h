@@ -528,6 +528,33 @@ int sc_density_pair_sum(const double *X1, const double *Y1, int32_t K1, const do
                         const double *a_ket, const double *b_ket, const double *inv_two_sigma2, int32_t M,
                         const double *s, const double *s_origin, int32_t ns, double *partials, double *rho, void *stream);
 
+/* Cross-correlation of the Herman-Kluk wavepacket with K target coherent states |q_k, p_k, Gamma_0>, behind
+ * HermanKlukPropagator.cross_correlation() and run(targets=...) (not in the reference, whose CoherentStatesOverlap,
+ * propagators.py:181-240, defines the overlap).  With dq = q_k - q_i, dp = p_k - p_i and A, B, C, fac the
+ * overlap constants of (Gamma_t, Gamma_0):
+ *   x_ik = conj(fac exp(-1/2 dq^T A dq - 1/2 hbar^-2 dp^T B dp - i/hbar p_k.dq + i/hbar dq^T C dp)) v_i,
+ *   v_i  = sgn_i sqrt(c2_i) e^{i S_i/hbar} vi_i / (mc_norm probi_i)              (as sc_hk_correlate forms it, from `st`),
+ *   out[k] = sum_i (Re x_ik, Im x_ik, (Re x_ik)^2, (Im x_ik)^2, Re x_ik Im x_ik)   -- five doubles per target, no phase.
+ * For (q_k, p_k) = (q0, p0), x_ik is the cq_i of sc_hk_correlate.  The exponent is formed from differences in transformed
+ * coordinates, La = A^(1/2), Lb = B^(1/2) / hbar:
+ *   diag != 0 (diagonal widths): La, Lb, Ct = the diagonals of La, Lb, C, [D] each; `operands` may be NULL (no pre-pass);
+ *   diag == 0: La, Lb [D][D] symmetric, Ct [D][D] = the TRANSPOSE of C; operands: scratch of n * 4 D doubles, which a
+ *              pre-pass fills with the rows [La q_i | Lb p_i | q_i | C p_i].
+ *   targets [K][5 D]: rows [La q_k | Lb p_k | q_k | C p_k | p_k], formed by the caller once per set of targets.
+ *   kept: uint8 [n] or NULL; a trajectory with kept == 0 adds zero to all five sums (its state is not read).
+ *   partials: scratch of sc_hk_cross_rows(n, K) * K * 5 doubles; operands and partials are free again when the call's work on
+ *             `stream` has run.
+ *   out [K][5]; with `cursor` (device resident) the row goes to out + 5 K *cursor, and the cursor is NOT advanced (the
+ *             reduction of the correlate launch that shares the cursor advances it: launch this one first).
+ * `st` may be a view of an intermediate state (sc_hk_step_multi, sc_hk_step_visit): only n, dim, qp, act, c2, sgn are read.
+ * Two launches (three for dense widths); no atomics, the order of every sum is a function of (n, K) alone: the same bits in
+ * every call.  D <= 512, 1 <= K <= 65535, n <= 64 * 65535; beyond: SC_ERR_UNSUPPORTED.  A null pointer or K < 1:
+ * SC_ERR_BAD_ARGUMENT. */
+int64_t sc_hk_cross_rows(int64_t n, int64_t K);
+int sc_hk_cross(const sc_state *st, const double *La, const double *Lb, const double *Ct, int32_t diag, double fac,
+                const double *targets, int32_t K, const double *vi, const double *probi, double mc_norm,
+                const uint8_t *kept, double *operands, double *partials, double *out, const int64_t *cursor, void *stream);
+
 /* Frozen-Gaussian wavefunction on a spatial grid behind HermanKlukPropagator.wavefunction() (propagators.py:252-292,
  * 688-732):  phi[k] = fac sum_n v_n exp(-1/2 |Lx_k - Lq_n|^2 + i (p_n.x_k - pq_n)),  L = Gamma_t^(1/2).
  * LqT, PT [D][n] (trajectory index fastest), pq [n], v [n] complex, Lx, X [nx][D], phi [nx] complex. */

@@ -1,0 +1,246 @@
+// Cross-correlation of the Herman-Kluk wavepacket with K target coherent states |q_k, p_k, Gamma_0> (not in the reference;
+// DESIGN.md section 4.13) -- the O(n K D) kernels behind HermanKlukPropagator.cross_correlation() and run(targets=...).  The
+// overlap is the reference's CoherentStatesOverlap, semiclassical/propagators.py:181-240 (the formula: 232-237), with the bra
+// trajectory i of width Gamma_t and the ket target k of width Gamma_0:
+//
+//   E_ik = -1/2 dq^T A dq - 1/2 hbar^-2 dp^T B dp - i/hbar p_k.dq + i/hbar dq^T C dp,      dq = q_k - q_i, dp = p_k - p_i
+//   x_ik = conj(fac exp(E_ik)) v_i,   v_i = sgn_i sqrt(c2_i) e^{i S_i/hbar} vi_i / (N (2 pi hbar)^D P_i)
+//   row k of the output: sum_i of  Re x, Im x, (Re x)^2, (Im x)^2, Re x Im x.
+//
+// The exponent is formed from DIFFERENCES in transformed coordinates, La = A^(1/2), Lb = B^(1/2) / hbar (the host's):
+//   Re E = -1/2 (|La q_k - La q_i|^2 + |Lb p_k - Lb p_i|^2),   Im E = 1/hbar sum_d dq_d ((C p_k)_d - (C p_i)_d - p_k,d)
+// -- no cancellation between large q^2 terms, nothing to centre.  Operand rows: trajectory [La q | Lb p | q | C p] (4 D), target
+// [La q_k | Lb p_k | q_k | C p_k | p_k] (5 D, formed by the host once per set of targets).
+//
+// cross_operands_kernel (dense widths only): the trajectory rows into caller-owned scratch, three D x D mat-vecs per trajectory,
+//   one trajectory per wavefront pass.  Diagonal widths need no pre-pass: the tile kernel scales q and p while it stages them.
+// cross_tile_kernel: one workgroup of 256 threads owns 64 trajectories (blockIdx.y, a "band") x 64 targets (blockIdx.x); thread
+//   (ti, tj) owns the 4 x 4 pairs of trajectories 4 ti + a and targets 4 tj + b (the mapping of pair_sum_kernel, phase A).  The
+//   d-loop is staged through LDS in chunks of CK; then one c_exp per pair, the product with v_i (formed once per trajectory by
+//   the first 64 threads exactly as hk_correlate_kernel forms it) and the three moment products.  The thread adds its 4
+//   trajectories in registers, the 16 threads of a target column add through LDS in a fixed order: one store of 5 doubles per
+//   target into partials[band][K][5].
+// cross_reduce_kernel: adds the bands in a fixed order (16 contiguous slices, then the slices) into the output row.
+// No atomics; the order of every sum is a function of (n, K) alone: the same bits in every call.  Discarded trajectories
+// (`kept`) and the rows beyond n are staged as zero operands with v = 0: they add exact zeros and never meet a non-finite value.
+#include "sc_common.h"
+
+namespace {
+
+#define CT 64      // tile edge
+#define CK 16      // d chunk
+#define CROW (CT + 2)   // row stride: 16-byte aligned, so that a thread's four values are two 16-byte LDS reads (with CT + 1 they are
+                        // two-address 8-byte reads at half the LDS rate: 0.33 instead of 0.22 ms at n = 1e5, K = 64, D = 60)
+
+// the LDS of the tile kernel: the d-chunk of both operand sets, reused for the column reduction
+struct alignas(16) CrossStage {
+    double ta[CK][CROW], tb[CK][CROW], tq[CK][CROW], tc[CK][CROW];      // trajectories: La q, Lb p, q, C p
+    double ka[CK][CROW], kb[CK][CROW], kq[CK][CROW], kg[CK][CROW];      // targets: La q_k, Lb p_k, q_k, C p_k - p_k
+};
+
+struct CrossArgs {
+    sc_state st;
+    const double *La, *Lb, *Cm;     // diagonal widths: [D] each (the tile kernel scales); dense: unused here
+    const double *operands;         // dense widths: [n][4 D] from cross_operands_kernel
+    const double *targets;          // [K][5 D]
+    int K;
+    double fac, mc_norm;
+    const double *vi, *probi;
+    const uint8_t *kept;            // may be NULL
+    double *partials;               // [bands][K][5]
+};
+
+// four consecutive doubles of a staged row, from a 16-byte aligned address
+__device__ __forceinline__ void load4(const double *p, double (&o)[4]) {
+    const double2 lo = ((const double2 *)p)[0], hi = ((const double2 *)p)[1];
+    o[0] = lo.x; o[1] = lo.y; o[2] = hi.x; o[3] = hi.y;
+}
+
+template <bool DIAG>
+__global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
+    __shared__ CrossStage S;
+    __shared__ double2 vs[CT];      // v_i of the band's trajectories (0: beyond n, or discarded)
+    __shared__ int live[CT];
+    static_assert(sizeof(CrossStage) >= sizeof(double) * 16 * 5 * CT, "the column reduction reuses the staging buffers");
+    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
+    const int D = A.st.dim;
+    const int64_t n = A.st.n, i0 = (int64_t)blockIdx.y * CT;
+    const int k0 = blockIdx.x * CT;
+    const int iv = (int)min((int64_t)CT, n - i0), kv = min(CT, A.K - k0);      // valid trajectories / targets of the tile
+    if (tid < CT) {
+        cplx v = c_make(0.0, 0.0);
+        const int64_t tr = i0 + tid;
+        const bool in = tid < iv && (!A.kept || A.kept[tr]);
+        if (in) {
+            // as hk_correlate_kernel: the signed principal root, the action's phase, the initial overlap, the Monte-Carlo weight
+            const cplx c = c_scale(c_sqrt(((const cplx *)A.st.c2)[tr]), A.st.sgn[tr]);
+            const cplx ph = c_exp(c_make(0.0, A.st.act[tr] / SC_HBAR));
+            const double w = 1.0 / (A.mc_norm * A.probi[tr]);
+            v = c_scale(c_mul(((const cplx *)A.vi)[tr], c_mul(c, ph)), w);
+        }
+        vs[tid] = v;
+        live[tid] = in;
+    }
+    double re[4][4], im[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { re[a][b] = 0.0; im[a][b] = 0.0; }
+    for (int d0 = 0; d0 < D; d0 += CK) {
+        __syncthreads();                                   // live[] is written; the last readers of the chunk before are done
+        for (int e = tid; e < CK * CT; e += 256) {
+            const int r = e / CK, k = e - r * CK, d = d0 + k;      // row r of the tile, column k of the chunk
+            double a = 0.0, b = 0.0, q = 0.0, c = 0.0;
+            if (d < D && live[r]) {
+                if (DIAG) {
+                    const double *qp = A.st.qp + (i0 + r) * 2 * D;
+                    const double p = qp[D + d];
+                    q = qp[d];
+                    a = A.La[d] * q; b = A.Lb[d] * p; c = A.Cm[d] * p;
+                } else {
+                    const double *row = A.operands + (i0 + r) * 4 * D;
+                    a = row[d]; b = row[D + d]; q = row[2 * D + d]; c = row[3 * D + d];
+                }
+            }
+            S.ta[k][r] = a; S.tb[k][r] = b; S.tq[k][r] = q; S.tc[k][r] = c;
+            a = 0.0; b = 0.0; q = 0.0; c = 0.0;
+            if (d < D && r < kv) {
+                const double *row = A.targets + (size_t)(k0 + r) * 5 * D;
+                a = row[d]; b = row[D + d]; q = row[2 * D + d]; c = row[3 * D + d] - row[4 * D + d];
+            }
+            S.ka[k][r] = a; S.kb[k][r] = b; S.kq[k][r] = q; S.kg[k][r] = c;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < CK; ++k) {
+            double xa[4], xb[4], xq[4], xc[4], ya[4], yb[4], yq[4], yg[4];
+            load4(&S.ta[k][4 * ti], xa); load4(&S.tb[k][4 * ti], xb); load4(&S.tq[k][4 * ti], xq); load4(&S.tc[k][4 * ti], xc);
+            load4(&S.ka[k][4 * tj], ya); load4(&S.kb[k][4 * tj], yb); load4(&S.kq[k][4 * tj], yq); load4(&S.kg[k][4 * tj], yg);
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const double da = ya[b] - xa[a], db = yb[b] - xb[a], dq = yq[b] - xq[a];
+                    re[a][b] = fma(da, da, re[a][b]);
+                    re[a][b] = fma(db, db, re[a][b]);
+                    im[a][b] = fma(dq, yg[b] - xc[a], im[a][b]);
+                }
+        }
+    }
+    // x_ik = conj(fac exp(E)) v_i; the thread's four trajectories are added per target in registers
+    double sum[4][5];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) sum[b][c] = 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const cplx o = c_scale(c_exp(c_make(-0.5 * re[a][b], -im[a][b] * (1.0 / SC_HBAR))), A.fac);
+            const cplx x = c_mul(o, vs[4 * ti + a]);
+            sum[b][0] += x.x; sum[b][1] += x.y;
+            sum[b][2] = fma(x.x, x.x, sum[b][2]); sum[b][3] = fma(x.y, x.y, sum[b][3]); sum[b][4] = fma(x.x, x.y, sum[b][4]);
+        }
+    }
+    __syncthreads();                                       // the staging buffers are free
+    double (*red)[5][CT] = (double (*)[5][CT])&S;          // [ti][column][target]
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int c = 0; c < 5; ++c) red[ti][c][4 * tj + b] = sum[b][c];
+    __syncthreads();
+    for (int e = tid; e < 5 * kv; e += 256) {
+        const int t = e / 5, c = e - 5 * t;
+        double s = 0.0;
+        for (int g = 0; g < 16; ++g) s += red[g][c][t];
+        A.partials[((size_t)blockIdx.y * A.K + k0) * 5 + e] = s;
+    }
+}
+
+// dense widths: operands[i] = [La q_i | Lb p_i | q_i | C p_i].  La and Lb are symmetric, Ct is the TRANSPOSE of C: element (a, b)
+// of all three is read at [b D + a], consecutive lanes consecutive addresses.  One trajectory per wavefront pass.
+__global__ __launch_bounds__(256) void cross_operands_kernel(sc_state st, const double *La, const double *Lb, const double *Ct,
+                                                             double *operands) {
+    extern __shared__ double smem[];
+    const int D = st.dim, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double *qp = smem + (size_t)wave * 2 * D;
+    for (int64_t tr = (int64_t)blockIdx.x * 4 + wave; tr < st.n; tr += (int64_t)gridDim.x * 4) {
+        for (int a = lane; a < 2 * D; a += 64) qp[a] = st.qp[tr * 2 * D + a];
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xC07F);                // lgkmcnt(0): the wave's own LDS writes have landed
+        double *row = operands + tr * 4 * D;
+        for (int a = lane; a < D; a += 64) {
+            double ya = 0.0, yb = 0.0, yc = 0.0;
+            for (int b = 0; b < D; ++b) {
+                ya = fma(La[(size_t)b * D + a], qp[b], ya);
+                yb = fma(Lb[(size_t)b * D + a], qp[D + b], yb);
+                yc = fma(Ct[(size_t)b * D + a], qp[D + b], yc);
+            }
+            row[a] = ya; row[D + a] = yb; row[2 * D + a] = qp[a]; row[3 * D + a] = yc;
+        }
+        __builtin_amdgcn_wave_barrier();                   // every lane has read qp before the next trajectory overwrites it
+    }
+}
+
+// out[e] = sum over the bands of partials[band][e], e < total = 5 K: the bands in 16 contiguous slices, each added in order by
+// one thread, then the slices in order
+__global__ __launch_bounds__(256) void cross_reduce_kernel(const double *partials, int64_t bands, int64_t total, double *out,
+                                                           const long long *cursor) {
+    __shared__ double red[16][16];
+    const int sl = threadIdx.x >> 4, el = threadIdx.x & 15;
+    const int64_t e = (int64_t)blockIdx.x * 16 + el;
+    const int64_t per = (bands + 15) / 16, b0 = sl * per, b1 = min(b0 + per, bands);
+    double s = 0.0;
+    if (e < total)
+        for (int64_t b = b0; b < b1; ++b) s += partials[b * total + e];
+    red[sl][el] = s;
+    __syncthreads();
+    if (sl == 0 && e < total) {
+        double t = 0.0;
+        for (int g = 0; g < 16; ++g) t += red[g][el];
+        if (cursor) out += total * *cursor;
+        out[e] = t;
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t sc_hk_cross_rows(int64_t n, int64_t K) {
+    if (n <= 0 || K <= 0) return 0;
+    return (n + CT - 1) / CT;
+}
+
+extern "C" int sc_hk_cross(const sc_state *st, const double *La, const double *Lb, const double *Ct, int32_t diag, double fac,
+                           const double *targets, int32_t K, const double *vi, const double *probi, double mc_norm,
+                           const uint8_t *kept, double *operands, double *partials, double *out, const int64_t *cursor,
+                           void *stream) {
+    if (!st || !La || !Lb || !Ct || !targets || !vi || !probi || !partials || !out)
+        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_cross: null argument");
+    if (K < 1 || st->dim < 1 || st->n < 0)
+        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_cross: K=%d, D=%d, n=%lld", K, st->dim, (long long)st->n);
+    if (!diag && !operands) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_cross: dense widths need the operand scratch [n][4 D]");
+    if (st->dim > 512) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_cross: D=%d outside D <= 512", st->dim);
+    if (K > 65535) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_cross: K=%d targets outside K <= 65535", K);
+    const int64_t bands = (st->n + CT - 1) / CT;
+    if (bands > 65535)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_cross: n=%lld trajectories outside n <= %d", (long long)st->n, CT * 65535);
+    hipStream_t s = (hipStream_t)stream;
+    if (bands > 0) {
+        if (!diag) {
+            const int64_t blocks = (st->n + 3) / 4;
+            hipLaunchKernelGGL(cross_operands_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256),
+                               (size_t)4 * 2 * st->dim * sizeof(double), s, *st, La, Lb, Ct, operands);
+            const int rc = sc_check_launch("sc_hk_cross (operands)");
+            if (rc != SC_OK) return rc;
+        }
+        CrossArgs a{*st, La, Lb, Ct, operands, targets, K, fac, mc_norm, vi, probi, kept, partials};
+        const dim3 grid((unsigned)((K + CT - 1) / CT), (unsigned)bands);
+        if (diag) hipLaunchKernelGGL(cross_tile_kernel<true>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(cross_tile_kernel<false>, grid, dim3(256), 0, s, a);
+        const int rc = sc_check_launch("sc_hk_cross");
+        if (rc != SC_OK) return rc;
+    }
+    const int64_t total = (int64_t)5 * K;
+    hipLaunchKernelGGL(cross_reduce_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, s, partials, bands, total, out,
+                       (const long long *)cursor);
+    return sc_check_launch("sc_hk_cross (reduction)");
+}

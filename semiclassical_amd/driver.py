@@ -116,7 +116,9 @@ class CorrelationStore(object):
     def __init__(self, path):
         self.path = path
 
-    def start(self, task, propagator_name, times, setup):
+    def start(self, task, propagator_name, times, setup, cross_targets=None):
+        """``cross_targets``: (q, p) of the task's "cross_correlation_targets", or None: a file that is added to has to hold
+        exactly these (ConfigurationError otherwise, before any trajectory runs)"""
         fresh = task['results'].get('overwrite', True) is True or not os.path.exists(self.path)
         if fresh:
             nt = len(times)
@@ -131,6 +133,24 @@ class CorrelationStore(object):
         assert np.array_equal(previous['times'], times.numpy()), \
             f"Time steps in {self.path} differ. Delete the old file or change the grid for time propagation."
         assert previous['propagator'] == propagator_name, "Data produced with different propagators cannot be added."
+        if previous['trajectories'] > 0:
+            self._check_cross_targets(previous, cross_targets)
+
+    CROSS_KEYS = ('cross_targets_q', 'cross_targets_p', 'cross_correlation')
+
+    CROSS_ERROR_KEYS = ('cross_correlation_second_moment', 'cross_correlation_error')
+
+    def _check_cross_targets(self, stored, targets):
+        """the stored cross-correlation functions belong to exactly the targets (q, p) of the task (None: the task has none)"""
+        have = 'cross_targets_q' in stored
+        if have != (targets is not None):
+            raise ConfigurationError(
+                f"{self.path} holds {'cross-correlation functions' if have else 'no cross-correlation functions'}, this task "
+                f"{'has no' if have else 'has'} \"cross_correlation_targets\": they cannot be pooled")
+        if have and not (np.array_equal(stored['cross_targets_q'], targets[0]) and np.array_equal(stored['cross_targets_p'], targets[1])):
+            raise ConfigurationError(
+                f"{self.path} holds cross-correlation functions with other targets than this task's "
+                "(\"cross_correlation_targets\"): they are different estimators and cannot be pooled")
 
     ERROR_KEYS = ('autocorrelation_error', 'ic_correlation_error', 'autocorrelation_second_moment', 'ic_correlation_second_moment')
 
@@ -139,7 +159,7 @@ class CorrelationStore(object):
     SYMPLECTICITY_KEYS = ('symplecticity_steps', 'symplecticity_max', 'symplecticity_mean', 'symplecticity_exceeding',
                           'symplecticity_tolerance', 'symplecticity_kept', 'symplecticity_discard')
 
-    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None):
+    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None, cross=None):
         """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
         per-sample second moments (rows (S_rr, S_ii, S_ri) times the batch size, phase applied) of the batch, folded the same
         way; the standard errors of the pooled means follow from them.  Files and batches that do not both carry them lose
@@ -156,10 +176,17 @@ class CorrelationStore(object):
         record also carries 'kept', the trajectories still kept after every check; the file then holds ``symplecticity_kept``
         (counts add) and ``symplecticity_discard``.  Correlation functions with and without discarding, or discarded against
         another tolerance or at other steps, are different estimators: pooling them is refused (ConfigurationError), never
-        resolved by dropping keys."""
+        resolved by dropping keys.
+        ``cross``: the record of the batch's cross-correlation functions: 'q', 'p' (K, D) the targets,
+        'correlation' (nt, K) and, with standard errors, 'second_moment' (nt, K, 3) as for the autocorrelation.  The file then holds
+        ``cross_targets_q``, ``cross_targets_p``, ``cross_correlation`` (pooled with the weights of ``autocorrelation``) and, by the
+        keep-or-drop rule of the second moments, ``cross_correlation_second_moment`` and ``cross_correlation_error``.  Stored
+        targets that differ from the batch's (or exist on one side only) are refused (ConfigurationError)."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
+        if done > 0:
+            self._check_cross_targets(stored, None if cross is None else (cross['q'], cross['p']))
         discarding = symplecticity is not None and bool(symplecticity.get('discard', False))
         if done > 0:
             was_discarding = bool(stored.get('symplecticity_discard', False))
@@ -227,6 +254,23 @@ class CorrelationStore(object):
                            "the stored trajectories have none, or were checked at other steps or against another tolerance")
             for key in self.SYMPLECTICITY_KEYS:
                 stored.pop(key, None)
+        if cross is not None:
+            pool = done > 0
+            new = np.asarray(cross['correlation'], dtype=complex)
+            stored['cross_targets_q'], stored['cross_targets_p'] = (np.asarray(cross[key], dtype=np.float64) for key in ('q', 'p'))
+            stored['cross_correlation'] = (ntraj * new + done * stored['cross_correlation']) / total if pool else new
+            moment = cross.get('second_moment', None)
+            have_moment = 'cross_correlation_second_moment' in stored
+            if moment is not None and (have_moment or not pool):
+                key = 'cross_correlation_second_moment'
+                stored[key] = (ntraj * moment + done * stored[key]) / total if pool else np.asarray(moment, dtype=np.float64)
+                stored['cross_correlation_error'] = hostmath.standard_errors(stored['cross_correlation'], stored[key] / total, total)
+            elif have_moment or moment is not None:
+                logger.warning("standard errors of the cross-correlation functions dropped from %s: %s", self.path,
+                               "the stored trajectories have no second moments" if moment is not None else
+                               "this task does not compute them (\"standard_errors\": true)")
+                for key in self.CROSS_ERROR_KEYS:
+                    stored.pop(key, None)
         stored.pop('ic_rate', None)          # a rate computed from the old correlation function is stale now
         stored.pop('ic_rate_error', None)
         logger.info(f"<phi(0)|phi(0)>= {stored['autocorrelation'][0]}")
@@ -285,7 +329,7 @@ def _check_symplecticity(propagator, step, time, tolerance, log, discard=False):
 
 
 def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False,
-                    error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None, discard_nonsymplectic=False):
+                    error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None, discard_nonsymplectic=False, targets=None):
     """C_auto(t), k_ic(t) of one batch of trajectories: the device loop leaves the raw per-step sums in a device buffer,
     ``flush`` (None on a single rank) adds the buffers of all ranks -- ONE all-reduce per batch, SURVEY 8e -- and the host
     applies the dynamical phase.  ``norm_every`` > 0 logs the wavefunction norm (the O(n^2) convergence diagnostic of
@@ -301,12 +345,22 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     ``symplecticity_tolerance``, 'exceeding' (trajectories above it) and 'tolerance'.  Nothing else of the result changes.
     ``discard_nonsymplectic`` (needs both): every check discards the trajectories above the tolerance for the rest of the batch
     (propagator.discard_nonsymplectic: samples of value zero, N unchanged); 'max' and 'mean' are then over the trajectories still
-    kept before the check, and the record gains 'kept' (the number kept after every check) and 'discard' = True."""
+    kept before the check, and the record gains 'kept' (the number kept after every check) and 'discard' = True.
+    ``targets`` = (Q, P), arrays (K, D): the cross-correlation functions with these target coherent states (propagator.run(targets=...));
+    the result then ends with one more element still, the record {'q', 'p', 'correlation' (nt, K)} and, with ``errors``,
+    'second_moment' (nt, K, 3), the per-sample second moments as (M_C, M_k).  Single rank only: the flush does not carry them."""
+    if targets is not None and flush is not None:
+        raise ValueError("targets are not available with more than one rank: the flush buffer does not carry the cross-correlation rows")
     if discard_nonsymplectic and not (symplecticity_every > 0 and symplecticity_tolerance is not None):
         raise ValueError("discard_nonsymplectic needs symplecticity_every > 0 and a symplecticity_tolerance")
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
     moments = torch.zeros((nt, 6), dtype=torch.float64, device=propagator.device) if errors else None
-    blocks = counts = None
+    blocks = counts = cross = None
+    if targets is not None:
+        Q, P = (np.asarray(a, dtype=np.float64) for a in targets)
+        if Q.ndim != 2 or Q.shape[0] == 0:
+            raise ValueError(f"targets: arrays of shape (K, D) with K > 0 are expected, got {Q.shape}")
+        cross = torch.zeros((nt, Q.shape[0], 5), dtype=torch.float64, device=propagator.device)
     if error_blocks:
         blocks = torch.zeros((nt, error_blocks, 4), dtype=torch.float64, device=propagator.device)
         counts = torch.from_numpy(propagator.block_counts(propagator.ntraj, error_blocks)).to(torch.float64)
@@ -325,7 +379,8 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         pieces.append((first, count, propagator.t))
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
                        moments=None if moments is None else moments[first:first + count],
-                       blocks=None if blocks is None else blocks[first:first + count])
+                       blocks=None if blocks is None else blocks[first:first + count],
+                       **({} if cross is None else dict(targets=(Q, P), cross=cross[first:first + count])))
     if symplecticity_every > 0 and pieces:
         # The clock of a piece is t0 + (dt + dt + ...), which differs from the uncut loop's 0 + dt + dt + ... in the last bits, and
         # with it the dynamical phase.  The check must leave every bit of the correlation functions as it is: the phase is taken
@@ -351,6 +406,19 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         if discard_nonsymplectic:
             record.update(kept=np.asarray(kept, dtype=np.int64), discard=True)
         tail = tail + (record,)
+    if cross is not None:
+        n = propagator._ntraj_norm
+        raw = cross.cpu().numpy()
+        X, m3 = [], []
+        for first, count, t0 in pieces:
+            times_ = t0 + hostmath.time_grid(count, dt)
+            part = raw[first:first + count]
+            X.append((part[:, :, 0] + 1j * part[:, :, 1]) * np.exp(1j / units.hbar * times_ * setup.zero_point_energy)[:, None])
+            m3.append(hostmath.rotate_second_moments(part[:, :, 2:5], (times_ * setup.zero_point_energy / units.hbar)[:, None]))
+        record = {'q': Q, 'p': P, 'correlation': np.concatenate(X)}
+        if errors:
+            record['second_moment'] = n * np.concatenate(m3)
+        tail = tail + (record,)
     if moments is None:
         parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
                  for first, count, t0 in pieces]
@@ -360,6 +428,21 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     C, k, mC, mk = (np.concatenate(part) for part in zip(*parts))
     n = propagator._ntraj_norm
     return (C, k, n * mC, n * mk) + tail
+
+
+def _load_targets(path, dim):
+    """(q, p), float64 (K, D), of a "cross_correlation_targets" file"""
+    try:
+        with np.load(path, allow_pickle=False) as handle:
+            q, p = (np.array(handle[key], dtype=np.float64) for key in ('q', 'p'))
+    except (OSError, KeyError, ValueError) as err:
+        raise ConfigurationError(f"'cross_correlation_targets': {path} should be an npz file with arrays q and p ({err})")
+    if q.ndim != 2 or q.shape != p.shape or q.shape[0] == 0 or q.shape[1] != dim:
+        raise ConfigurationError(f"'cross_correlation_targets': q and p of shape (K, {dim}) with K > 0 are expected in {path}, got "
+                                 f"{q.shape} and {p.shape}")
+    if not (np.isfinite(q).all() and np.isfinite(p).all()):
+        raise ConfigurationError(f"'cross_correlation_targets': non-finite entry in {path}")
+    return q, p
 
 
 def run_semiclassical_dynamics(task, device='cuda', comm=None):
@@ -398,7 +481,17 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     if check_every and world > 1:
         raise ConfigurationError("'check_symplecticity_every' is not available with more than one rank: the maximum over the "
                                  "trajectories does not fit the one sum all-reduce per batch")
+    # cross-correlation functions with target coherent states (a key the reference does not have): an npz file with
+    # arrays q and p (K, D), atomic units, in the coordinates of q0
+    targets_file = task.get('cross_correlation_targets', None)
+    if targets_file is not None and task.get('propagator', 'HK') == "WM":
+        raise ConfigurationError("'cross_correlation_targets' is not available with the WM propagator: its Gaussians have "
+                                 "per-trajectory widths and another prefactor")
+    if targets_file is not None and world > 1:
+        raise ConfigurationError("'cross_correlation_targets' is not available with more than one rank: the flush buffer does not "
+                                 "carry the cross-correlation rows")
     setup = build_problem(task)
+    targets = None if targets_file is None else _load_targets(targets_file, int(setup.q0.shape[0]))
 
     dt = task['time_step_fs'] / units.autime_to_fs
     nt = task['num_steps']
@@ -415,7 +508,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
 
     store = CorrelationStore(task['results'].get('correlations', 'correlations.npz'))
     if writer:
-        store.start(task, task.get('propagator', 'HK'), times, setup)
+        store.start(task, task.get('propagator', 'HK'), times, setup, cross_targets=targets)
 
     seed = task.get('manual_seed', None)
     if seed is not None:
@@ -462,7 +555,11 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
             raise ConfigurationError(f"'error_blocks' should be a power of two in 2 ... 64 (or 0), got {error_blocks}")
         out = propagate_batch(propagator, setup, dt, nt, times, norm_every=task.get('calc_norm_every', 0), flush=flush,
                               across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks,
-                              symplecticity_every=check_every, symplecticity_tolerance=tolerance, discard_nonsymplectic=discard)
+                              symplecticity_every=check_every, symplecticity_tolerance=tolerance, discard_nonsymplectic=discard,
+                              targets=targets)
+        cross = None
+        if targets is not None:
+            out, cross = out[:-1], out[-1]
         checks = None
         if check_every:
             out, checks = out[:-1], out[-1]
@@ -471,7 +568,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         assert not np.isnan(ic_correlation).any(), f"encountered NaN's in IC correlation : {ic_correlation}"
         if writer:
             store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:4] if errors else None,
-                            blocks=out[-1] if error_blocks else None, symplecticity=checks)
+                            blocks=out[-1] if error_blocks else None, symplecticity=checks, cross=cross)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -233,6 +233,7 @@ class HermanKlukPropagator(object):
         self._modal_step_cache, self._modal_basis = {}, None
         # discard mask (discard_nonsymplectic): None until the first mark -- every route then runs the launches it always ran
         self._kept, self._discarded_at, self._kept_count, self._masked_scratch = None, None, None, None
+        self._cross = None            # constants and scratch of cross_correlation(): depend on Gamma_0 and n
 
         self._prepare()
         self.t = 0.0
@@ -599,13 +600,16 @@ class HermanKlukPropagator(object):
                                       ptr(self._masked_scratch), C_void(slot_ptr), None if mom_ptr is None else C_void(mom_ptr),
                                       None if out is None else C_void(out), self._stream()))
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None, mom_ptr=None, blk=None):
+    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None, mom_ptr=None, blk=None,
+                          cross=None):
         """per-trajectory terms + their sums for the current state into the 5-double slot at `slot_ptr` (`slot_row`: the same
         five doubles as a tensor, needed when the k_ic sum is formed by torch: position-dependent couplings; `state`: another
         view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi; `mom_ptr`: the six second-moment
         sums go to the 6 doubles there, formed inside the correlate kernel; `blk` = (address, B): the block sums of the step go
         there -- the terms are exported and sc_term_blocks follows the correlate kernel).  Under a discard mask the correlate kernel
-        only exports the terms; sc_term_masked_sums forms every sum from them."""
+        only exports the terms; sc_term_masked_sums forms every sum from them.  `cross` = (targets, address): the (K, 5) sums of
+        the cross-correlation with the targets (_cross_targets) of the same state go to the address, sc_hk_cross after the
+        correlate kernel."""
         s = self._stream()
         nac = self._nac
         generic = getattr(self, "_nac_generic", None) is not None
@@ -621,6 +625,8 @@ class HermanKlukPropagator(object):
                                         ptr(self._cq) if per_trajectory else None,
                                         ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
                                         ptr(self._mpart) if in_kernel else None, s))
+        if cross is not None:
+            self._launch_cross(cross[0], cross[1], state=state, cursor=cursor)
         if masked:
             assert cursor is None
             self._masked_sums(nac is not None, slot_ptr, mom_ptr, blk)
@@ -664,7 +670,86 @@ class HermanKlukPropagator(object):
         k = complex(self._slot_host[2], self._slot_host[3])
         return k * np.exp(1j / hbar * self.t * energy0_es)
 
-    def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None):
+    # ---- cross-correlation with target coherent states (not in the reference) ----
+    def _cross_constants(self):
+        """La = A^(1/2), Lb = B^(1/2) / hbar and C of the overlap <q_i, p_i, Gamma_t|q_k, p_k, Gamma_0> on the host and as sc_hk_cross
+        takes them (diagonals for diagonal widths; else La, Lb and the transpose of C), plus the call's scratch -- once per state"""
+        if self._cross is None:
+            oc = hostmath.OverlapConstants(self._Gt, self._G0h)
+            sym = lambda m: 0.5 * (m + m.T)
+            La, Lb = hostmath.psd_sqrt_real(sym(oc.A)), hostmath.psd_sqrt_real(sym(oc.B)) / hbar
+            dev, n, d = self.device, self.ntraj, self.dim
+            if oc.diag:
+                bufs = [torch.diagonal(m).contiguous().to(dev) for m in (La, Lb, oc.C)]
+            else:
+                bufs = [La.contiguous().to(dev), Lb.contiguous().to(dev), oc.C.T.contiguous().to(dev)]
+            self._cross = {"La": La, "Lb": Lb, "C": oc.C, "diag": bool(oc.diag), "fac": float(oc.fac), "bufs": bufs,
+                           "operands": None if oc.diag else torch.empty((n, 4 * d), dtype=F64, device=dev), "partials": None}
+        return self._cross
+
+    def _cross_targets(self, q_targets, p_targets):
+        """validated targets and their operand rows [La q_k | Lb p_k | q_k | C p_k | p_k] on the device"""
+        if not self._cross_ok:
+            raise NotImplementedError(f"{type(self).__name__} has no cross-correlation with target coherent states: its Gaussians "
+                                      "have per-trajectory widths and another prefactor")
+        try:
+            Q, P = np.asarray(q_targets, dtype=np.float64), np.asarray(p_targets, dtype=np.float64)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"targets: real arrays of shape (K, {self.dim}) are expected ({err})")
+        if Q.ndim != 2 or Q.shape != P.shape or Q.shape[1] != self.dim:
+            raise ValueError(f"targets: q_targets and p_targets of shape (K, {self.dim}) are expected, got {Q.shape} and {P.shape}")
+        if Q.shape[0] == 0:
+            raise ValueError("targets: at least one target is expected (K = 0)")
+        if not (np.isfinite(Q).all() and np.isfinite(P).all()):
+            raise ValueError("targets: non-finite entry")
+        cc = self._cross_constants()
+        Qt, Pt = torch.from_numpy(Q.copy()), torch.from_numpy(P.copy())
+        rows = torch.cat((Qt @ cc["La"].T, Pt @ cc["Lb"].T, Qt, Pt @ cc["C"].T, Pt), 1).contiguous().to(self.device)
+        K = int(Q.shape[0])
+        need = int(lib.sc_hk_cross_rows(self.ntraj, K)) * K * 5
+        if cc["partials"] is None or cc["partials"].numel() < need:
+            cc["partials"] = torch.empty(need, dtype=F64, device=self.device)
+        return {"K": K, "rows": rows, "q": Q, "p": P}
+
+    def _launch_cross(self, targets, out_ptr, state=None, cursor=None):
+        """the (K, 5) cross-correlation sums of `state` (default: the current one) into the doubles at `out_ptr`, or into row *cursor
+        of the (., K, 5) buffer there (the cursor is read, not advanced); honours the discard mask"""
+        cc = self._cross_constants()
+        b = cc["bufs"]
+        with self._timed("hk_cross"):
+            check(lib.sc_hk_cross(self._state if state is None else state, ptr(b[0]), ptr(b[1]), ptr(b[2]), int(cc["diag"]),
+                                  cc["fac"], ptr(targets["rows"]), targets["K"], ptr(self._vi), ptr(self.probi), self._mc_norm(),
+                                  ptr(self._kept), ptr(cc["operands"]), ptr(cc["partials"]), C_void(out_ptr),
+                                  None if cursor is None else ptr(cursor), self._stream()))
+
+    def cross_correlation(self, q_targets, p_targets, energy0_es=0.0, standard_errors=False):
+        """C_k(t) = e^{i t E0/hbar} <phi_k|psi(t)> for the current step, phi_k = |q_k, p_k, Gamma_0> the coherent states at the rows
+        of ``q_targets``, ``p_targets`` (K, D) (not in the reference): a complex ndarray (K,).  Linear in the
+        ensemble like ``autocorrelation()``, which it equals for (q_k, p_k) = (q0, p0).  With ``standard_errors`` the result is
+        ``(C, sigma)``, sigma = sigma_Re + i sigma_Im per target (``hostmath.standard_errors``).  Trajectories discarded by
+        ``discard_nonsymplectic`` count as samples of value zero, N unchanged.  Synchronises; the state is not touched: the steps
+        that follow give the bits they would have given without the call.  ``ValueError`` for targets of the wrong shape, with
+        non-finite entries or K = 0."""
+        targets = self._cross_targets(q_targets, p_targets)
+        out = torch.zeros((1, targets["K"], 5), dtype=F64, device=self.device)
+        self._launch_cross(targets, out.data_ptr())
+        self.synchronize()
+        C, sigma = self.finalize_cross(out, self.t, 0.0, energy0_es, self._ntraj_norm)
+        return (C[0], sigma[0]) if standard_errors else C[0]
+
+    @staticmethod
+    def finalize_cross(cross, t0, dt, energy0_es, ntraj_norm):
+        """(C, sigma), complex (nt, K): the cross-correlation functions C_k(t) and their Monte-Carlo standard errors
+        sigma_Re + i sigma_Im from the raw rows (nt, K, 5) of run(..., cross=...) (summed over ranks when sharded): the dynamical phase
+        of finalize_slots, the rotation of the second moments and the error algebra of finalize_moments"""
+        raw = cross.detach().cpu().numpy() if isinstance(cross, torch.Tensor) else np.asarray(cross)
+        times = t0 + hostmath.time_grid(raw.shape[0], dt)
+        C = (raw[:, :, 0] + 1j * raw[:, :, 1]) * np.exp(1j / hbar * times * energy0_es)[:, None]
+        m3 = hostmath.rotate_second_moments(raw[:, :, 2:5], (times * energy0_es / hbar)[:, None])
+        return C, hostmath.standard_errors(C, m3, ntraj_norm)
+
+    def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
+            targets=None, cross=None):
         """The caller loop of cli.py:401-436 on the device: ``nt`` times (C_auto, k_ic, step), no host sync.
 
         Returns ``(autocorrelation[nt], ic_correlation[nt])`` as complex NumPy arrays.  With ``slots`` (a
@@ -701,11 +786,42 @@ class HermanKlukPropagator(object):
         After ``discard_nonsymplectic`` (a discard mask exists): slots, moments and blocks are the sums over the kept trajectories
         (``sc_term_masked_sums`` after every correlate launch, the intermediate states of pairs and visits included).  The loop
         then never runs as the one-launch kernel (it exports no terms) and ``use_graph=True`` raises ``ValueError``.
+
+        Cross-correlation functions: ``targets`` = (Q, P), arrays (K, D) of target coherent states (``cross_correlation``): a
+        ``sc_hk_cross`` launch follows every correlate launch, the intermediate states of pairs and visits included.  With
+        ``slots=None`` the returned tuple gains ``X`` (nt, K) complex at its end, and ``sigma_X`` after it with ``standard_errors=True``.
+        With ``slots`` given ``cross`` is required: a contiguous float64 device tensor (>= nt, K, 5) that receives the raw rows
+        (Re X, Im X, S_rr, S_ii, S_ri per target, no phase; plain sums with the global N in the weight, so the buffers of ranks add)
+        for ``finalize_cross``.  With targets the loop never runs as the one-launch kernel (it exports no per-step state): on those
+        shapes C and k are the step-at-a-time loop's; everywhere else C, k, moments, blocks and the final state are the same bit for
+        bit with or without targets.  ``use_graph=True`` with targets raises ``ValueError``.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
         if use_graph and self._kept is not None:
             raise ValueError("use_graph=True is not available once trajectories have been discarded (discard_nonsymplectic): the "
                              "graph replay has no masked reduction")
+        if targets is None and cross is not None:
+            raise ValueError("cross= receives the sums of run(targets=...): pass the targets as well")
+        if targets is not None:
+            if use_graph:
+                raise ValueError("use_graph=True is not available with targets: the graph replay has no cross-correlation launch")
+            if slots is not None and cross is None:
+                raise ValueError("run(slots=..., targets=...) leaves the raw sums on the device: pass cross=, a float64 device tensor "
+                                 "(>= nt, K, 5), to receive those of the targets")
+            try:
+                q_targets, p_targets = targets
+            except (TypeError, ValueError):
+                raise ValueError("targets: a pair (q_targets, p_targets) of arrays (K, D) is expected")
+            targets = self._cross_targets(q_targets, p_targets)
+            if cross is None:
+                cross = torch.zeros((nt, targets["K"], 5), dtype=F64, device=self.device)
+            elif not (isinstance(cross, torch.Tensor) and cross.dtype == F64 and cross.dim() == 3 and cross.shape[0] >= nt
+                      and tuple(cross.shape[1:]) == (targets["K"], 5) and cross.is_contiguous() and cross.device == self.device):
+                raise ValueError(f"cross has to be a contiguous float64 tensor of shape (>= {nt}, {targets['K']}, 5) on {self.device}, "
+                                 f"got {getattr(cross, 'dtype', type(cross))} {tuple(getattr(cross, 'shape', ()))} on "
+                                 f"{getattr(cross, 'device', '?')}")
+        xbase = None if targets is None else cross.data_ptr()
+        xrow = (lambda k: None) if xbase is None else (lambda k: (targets, xbase + 40 * targets["K"] * k))
         dt = float(dt)
         self._remember_nac(potential)
         own = slots is None
@@ -729,8 +845,9 @@ class HermanKlukPropagator(object):
         fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model") and self.dim <= 64
                  and self._nac_generic is None)
         desc = self._potential_descriptor(potential, dt) if fused else None
-        if fused and self._whole_loop_applies(desc):
-            # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run)
+        if fused and targets is None and self._whole_loop_applies(desc):
+            # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run; it exports no per-step state
+            # for the targets of a cross-correlation)
             self._run_whole_loop(desc, dt, nt, slots, potential, moments, blocks)
         elif (use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing
               and self._modal_step_constants(potential, desc, dt) is None):
@@ -741,14 +858,15 @@ class HermanKlukPropagator(object):
             kmax = self._visit_steps_for(desc) if pairs else 1
             k = 0
             while k < nt:
-                self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k], mom_ptr=mrow(k), blk=brow(k))
+                self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k], mom_ptr=mrow(k), blk=brow(k),
+                                       cross=xrow(k))
                 ks = min(kmax, nt - k) if pairs else 1       # never a visit longer than the steps left
                 if ks == 2:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
                     self._launch_correlate(base + 40 * (k + 1), per_trajectory=False, state=self._multi["state_mid"],
-                                           mom_ptr=mrow(k + 1), blk=brow(k + 1))
+                                           mom_ptr=mrow(k + 1), blk=brow(k + 1), cross=xrow(k + 1))
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -758,7 +876,7 @@ class HermanKlukPropagator(object):
                     self._launch_step_visit(desc, dt, ks)
                     for j in range(1, ks):
                         self._launch_correlate(base + 40 * (k + j), per_trajectory=False, state=self._multi["states_mid"][j - 1],
-                                               mom_ptr=mrow(k + j), blk=brow(k + j))
+                                               mom_ptr=mrow(k + j), blk=brow(k + j), cross=xrow(k + j))
                     for _ in range(ks):
                         self.t += dt
                     k += ks
@@ -770,10 +888,14 @@ class HermanKlukPropagator(object):
         if not own:
             return None
         self.synchronize()
+        tail = ()
+        if targets is not None:
+            X, sigma_X = self.finalize_cross(cross[:nt], t0, dt, energy0_es, self._ntraj_norm)
+            tail = (X, sigma_X) if standard_errors else (X,)
         if standard_errors:
-            return self.finalize_slots(slots, t0, dt, energy0_es) + self.finalize_moments(slots, moments, t0, dt, energy0_es,
-                                                                                          self._ntraj_norm)
-        return self.finalize_slots(slots, t0, dt, energy0_es)
+            return (self.finalize_slots(slots, t0, dt, energy0_es)
+                    + self.finalize_moments(slots, moments, t0, dt, energy0_es, self._ntraj_norm) + tail)
+        return self.finalize_slots(slots, t0, dt, energy0_es) + tail
 
     def standard_errors(self, energy0_es=0.0):
         """(sigma_C, sigma_k) of the current step: the Monte-Carlo standard errors sigma_Re + i sigma_Im of autocorrelation() and
@@ -787,6 +909,7 @@ class HermanKlukPropagator(object):
         return complex(sc[0]), complex(sk[0])
 
     _whole_loop_ok = True           # WM needs its own per-step kernel between the steps
+    _cross_ok = True                # WM has per-trajectory widths and another prefactor: no cross-correlation
 
     def _whole_loop_applies(self, desc):
         # (under a discard mask the sums come from the exported terms, which the whole-loop kernels do not write)
@@ -1494,6 +1617,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
     _tiled_fast_path = False        # the Filinov matrix is built from the row-major blocks after every step
     _whole_loop_ok = False          # ... by its own kernel, between the steps
     _multi_ok = False
+    _cross_ok = False               # cross_correlation() and run(targets=...) raise NotImplementedError
 
     def __init__(self, Gamma_i, Gamma_t, alpha, beta, device='cuda'):
         super().__init__(Gamma_i, Gamma_t, device=device)      # the Filinov matrix needs the dense monodromy blocks
@@ -1656,7 +1780,8 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, mom_ptr=None, blk=None):
+    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, mom_ptr=None, blk=None, cross=None):
+        assert cross is None          # run(targets=...) is refused before the loop starts
         # the per-trajectory terms were produced together with the prefactor; recompute (with the stored branch
         # signs, no tracking) only if the coupling vector was not known at that time
         knows_nac = self._wm_nac_bufs is not None or self._wm_nac_traj is not None
