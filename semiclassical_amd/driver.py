@@ -407,17 +407,11 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
             record.update(kept=np.asarray(kept, dtype=np.int64), discard=True)
         tail = tail + (record,)
     if cross is not None:
-        n = propagator._ntraj_norm
-        raw = cross.cpu().numpy()
-        X, m3 = [], []
-        for first, count, t0 in pieces:
-            times_ = t0 + hostmath.time_grid(count, dt)
-            part = raw[first:first + count]
-            X.append((part[:, :, 0] + 1j * part[:, :, 1]) * np.exp(1j / units.hbar * times_ * setup.zero_point_energy)[:, None])
-            m3.append(hostmath.rotate_second_moments(part[:, :, 2:5], (times_ * setup.zero_point_energy / units.hbar)[:, None]))
-        record = {'q': Q, 'p': P, 'correlation': np.concatenate(X)}
+        parts = [propagator.phased_cross(cross[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
+        X, m3 = (np.concatenate(part) for part in zip(*parts))
+        record = {'q': Q, 'p': P, 'correlation': X}
         if errors:
-            record['second_moment'] = n * np.concatenate(m3)
+            record['second_moment'] = propagator._ntraj_norm * m3
         tail = tail + (record,)
     if moments is None:
         parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)

@@ -17,6 +17,7 @@ Differences a caller can observe:
   * ``run()`` executes the caller loop of cli.py:401-436 (correlate,
     correlate, step -- nt times) without any host synchronisation.
 """
+import collections
 import logging
 
 import numpy as np
@@ -72,6 +73,58 @@ def _resolve_device(device):
     if dev.index is None:
         dev = torch.device('cuda', torch.cuda.current_device())
     return dev
+
+
+# One step's row of run()'s output buffers as the launches take it: the addresses of its slot, of its moments, blocks = (address, B)
+# and of its cross rows, None where there is no such buffer.  slots[k] is the slot as a tensor, formed only where torch adds the k_ic
+# sum to it (position-dependent couplings).
+_Row = collections.namedtuple("_Row", "slot moments blocks cross slots k")
+
+
+class _StepRows(object):
+    """The per-step output buffers of run(): what a row of each holds, how far apart the rows lie, where row k is.  The kernels write
+    exactly these doubles at base + stride k for k < nt: anything that is not that buffer is refused.  Reads no propagator state."""
+    #   buffer     a row, in doubles      bytes from row to row
+    #   slots      SLOT = 5               40
+    #   moments    MOMENT = 6             48
+    #   blocks     (B, BLOCK = 4)         32 B
+    #   cross      (K, CROSS = 5)         40 K
+    SLOT, MOMENT, BLOCK, CROSS = 5, 6, 4, 5
+
+    def __init__(self, device, nt, slots, moments=None, blocks=None, cross=None, K=None):
+        device = torch.device(device)
+        self._check("slots", slots, nt, (self.SLOT,), device)
+        if moments is not None:
+            self._check("moments", moments, nt, (self.MOMENT,), device)
+        if blocks is not None:
+            self._check("blocks", blocks, nt, ("B", self.BLOCK), device)
+            if not hostmath.valid_error_blocks(int(blocks.shape[1])):
+                raise ValueError(f"the number of blocks has to be a power of two in 2 ... 64, got {int(blocks.shape[1])}")
+        if cross is not None:
+            self._check("cross", cross, nt, (K, self.CROSS), device)
+        self.slots, self.moments = slots, moments
+        self.B, self.K = (None if t is None else int(t.shape[1]) for t in (blocks, cross))
+        self._base = tuple(None if t is None else t.data_ptr() for t in (slots, moments, blocks, cross))
+
+    @staticmethod
+    def _check(name, t, nt, row, device):           # row: the trailing shape ("B": any size)
+        if not (isinstance(t, torch.Tensor) and t.dtype == F64 and t.dim() == 1 + len(row) and t.shape[0] >= nt
+                and all(w == "B" or w == have for w, have in zip(row, t.shape[1:])) and t.is_contiguous() and t.device == device):
+            raise ValueError(f"{name} has to be a contiguous float64 tensor of shape (>= {nt}, {', '.join(map(str, row))}) on {device}, "
+                             f"got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', '?')}")
+
+    def row(self, k):
+        """row k.  Row 0 is also the base the cursor routes take, row k0 the start of the piece a whole-loop launch fills from k0 on"""
+        slot, mom, blk, cross = self._base
+        return _Row(slot + 8 * self.SLOT * k, None if mom is None else mom + 8 * self.MOMENT * k,
+                    None if blk is None else (blk + 8 * self.BLOCK * self.B * k, self.B),
+                    None if cross is None else cross + 8 * self.CROSS * self.K * k, self.slots, k)
+
+    @staticmethod
+    def single(slot=None, moments=None, cross=None):
+        """the row of buffers that hold one row each: scratch of the caller's own, of any shape, not validated"""
+        at = lambda t: None if t is None else t.data_ptr()
+        return _Row(at(slot), at(moments), None, at(cross), None if slot is None else slot.view(1, -1), 0)
 
 
 class HermanKlukPropagator(object):
@@ -559,20 +612,20 @@ class HermanKlukPropagator(object):
     def _mc_norm(self):
         return self._ntraj_norm * (2 * np.pi * hbar) ** self.dim
 
-    def _reduce_into(self, partials, count, slot_ptr, cursor, mom_ptr=None, mom_rows=None):
-        """sums of the per-workgroup partials into the slot at `slot_ptr`, or into row *cursor of the slot buffer; with `mom_ptr`
-        also the six moment sums of the first `mom_rows` rows of self._mpart into the moment row there (with a cursor: the same
+    def _reduce_into(self, partials, count, row, cursor, mom_rows=None):
+        """sums of the per-workgroup partials into the slot of `row`, or into row *cursor of the slot buffer that starts there; with
+        `mom_rows` also the six moment sums of the first `mom_rows` rows of self._mpart into the moment row (with a cursor: the same
         launch, one advance)"""
         s = self._stream()
         if cursor is None:
-            check(lib.sc_reduce_slot(ptr(partials), count, None, 0, 1.0, C_void(slot_ptr), s))
-            if mom_ptr is not None:
-                check(lib.sc_reduce_moments(ptr(self._mpart), mom_rows, C_void(mom_ptr), s))
-        elif mom_ptr is None:
-            check(lib.sc_reduce_slot_at(ptr(partials), count, C_void(slot_ptr), ptr(cursor), s))
+            check(lib.sc_reduce_slot(ptr(partials), count, None, 0, 1.0, C_void(row.slot), s))
+            if mom_rows is not None:
+                check(lib.sc_reduce_moments(ptr(self._mpart), mom_rows, C_void(row.moments), s))
+        elif mom_rows is None:
+            check(lib.sc_reduce_slot_at(ptr(partials), count, C_void(row.slot), ptr(cursor), s))
         else:
-            check(lib.sc_reduce_slot_moments_at(ptr(partials), count, ptr(self._mpart), mom_rows, C_void(slot_ptr),
-                                                C_void(mom_ptr), ptr(cursor), s))
+            check(lib.sc_reduce_slot_moments_at(ptr(partials), count, ptr(self._mpart), mom_rows, C_void(row.slot),
+                                                C_void(row.moments), ptr(cursor), s))
 
     def _term_moments(self, has_k):
         """moment partials of the exported per-trajectory terms _cq (and _kq) into self._mpart; returns their row count"""
@@ -589,29 +642,27 @@ class HermanKlukPropagator(object):
         else:
             check(lib.sc_term_blocks_at(ptr(self._cq), kq, self.ntraj, nblocks, C_void(out), ptr(cursor), self._stream()))
 
-    def _masked_sums(self, has_k, slot_ptr, mom_ptr=None, blk=None):
+    def _masked_sums(self, has_k, row):
         """the sums of the exported terms _cq (and _kq) over the kept trajectories, in place of _reduce_into / _term_moments /
-        _term_blocks: columns 0 ... 3 of the slot at `slot_ptr` (column 4 is not touched), the six moments at `mom_ptr`, the (B, 4)
-        block sums at blk = (address, B) -- one pass, sc_term_masked_sums"""
+        _term_blocks: columns 0 ... 3 of the slot of `row` (column 4 is not touched), its six moments, its (B, 4) block sums --
+        one pass, sc_term_masked_sums"""
         if self._masked_scratch is None:
             self._masked_scratch = torch.empty(lib.sc_term_masked_scratch_doubles(), dtype=F64, device=self.device)
-        out, nblocks = (None, 0) if blk is None else blk
+        out, nblocks = (None, 0) if row.blocks is None else row.blocks
         check(lib.sc_term_masked_sums(ptr(self._cq), ptr(self._kq) if has_k else None, ptr(self._kept), self.ntraj, nblocks,
-                                      ptr(self._masked_scratch), C_void(slot_ptr), None if mom_ptr is None else C_void(mom_ptr),
+                                      ptr(self._masked_scratch), C_void(row.slot), None if row.moments is None else C_void(row.moments),
                                       None if out is None else C_void(out), self._stream()))
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, state=None, mom_ptr=None, blk=None,
-                          cross=None):
-        """per-trajectory terms + their sums for the current state into the 5-double slot at `slot_ptr` (`slot_row`: the same
-        five doubles as a tensor, needed when the k_ic sum is formed by torch: position-dependent couplings; `state`: another
-        view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi; `mom_ptr`: the six second-moment
-        sums go to the 6 doubles there, formed inside the correlate kernel; `blk` = (address, B): the block sums of the step go
-        there -- the terms are exported and sc_term_blocks follows the correlate kernel).  Under a discard mask the correlate kernel
-        only exports the terms; sc_term_masked_sums forms every sum from them.  `cross` = (targets, address): the (K, 5) sums of
-        the cross-correlation with the targets (_cross_targets) of the same state go to the address, sc_hk_cross after the
-        correlate kernel."""
+    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None):
+        """per-trajectory terms + their sums for the current state into `row` (_StepRows): the 5-double slot; the six second-moment
+        sums, formed inside the correlate kernel; the block sums -- the terms are exported and sc_term_blocks follows the correlate
+        kernel.  `state`: another view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi.  Under a
+        discard mask the correlate kernel only exports the terms; sc_term_masked_sums forms every sum from them.  `targets`
+        (_cross_targets): the (K, 5) sums of the cross-correlation of the same state with them go to the row's cross rows,
+        sc_hk_cross after the correlate kernel."""
         s = self._stream()
         nac = self._nac
+        mom_ptr, blk = row.moments, row.blocks
         generic = getattr(self, "_nac_generic", None) is not None
         masked = self._kept is not None
         if masked and generic:
@@ -625,18 +676,18 @@ class HermanKlukPropagator(object):
                                         ptr(self._cq) if per_trajectory else None,
                                         ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
                                         ptr(self._mpart) if in_kernel else None, s))
-        if cross is not None:
-            self._launch_cross(cross[0], cross[1], state=state, cursor=cursor)
+        if targets is not None:
+            self._launch_cross(targets, row.cross, state=state, cursor=cursor)
         if masked:
             assert cursor is None
-            self._masked_sums(nac is not None, slot_ptr, mom_ptr, blk)
+            self._masked_sums(nac is not None, row)
             return
         if blk is not None and not generic:
             self._term_blocks(nac is not None, blk, cursor)
-        self._reduce_into(self._cpart, self._gcorr, slot_ptr, cursor, mom_ptr if in_kernel else None, self._gcorr)
+        self._reduce_into(self._cpart, self._gcorr, row, cursor, self._gcorr if in_kernel else None)
         if generic:
-            assert slot_row is not None and cursor is None
-            self._generic_kic(slot_row)
+            assert cursor is None
+            self._generic_kic(row.slots[row.k])
             if blk is not None:
                 self._term_blocks(True, blk)
             if mom_ptr is not None:
@@ -647,7 +698,7 @@ class HermanKlukPropagator(object):
     def _correlate_current(self, need_nac):
         if self._corr_step == self._nsteps and (self._corr_has_nac or not need_nac):
             return
-        self._launch_correlate(self._slot.data_ptr(), slot_row=self._slot)
+        self._launch_correlate(self._rows.single(self._slot))
         self._corr_step, self._corr_has_nac = self._nsteps, (self._nac is not None or self._nac_generic is not None)
         self._slot_host = self._slot.cpu().numpy().copy()          # host sync
         self._check_energy_guard()
@@ -732,20 +783,27 @@ class HermanKlukPropagator(object):
         non-finite entries or K = 0."""
         targets = self._cross_targets(q_targets, p_targets)
         out = torch.zeros((1, targets["K"], 5), dtype=F64, device=self.device)
-        self._launch_cross(targets, out.data_ptr())
+        self._launch_cross(targets, self._rows.single(cross=out).cross)
         self.synchronize()
         C, sigma = self.finalize_cross(out, self.t, 0.0, energy0_es, self._ntraj_norm)
         return (C[0], sigma[0]) if standard_errors else C[0]
 
     @staticmethod
-    def finalize_cross(cross, t0, dt, energy0_es, ntraj_norm):
-        """(C, sigma), complex (nt, K): the cross-correlation functions C_k(t) and their Monte-Carlo standard errors
-        sigma_Re + i sigma_Im from the raw rows (nt, K, 5) of run(..., cross=...) (summed over ranks when sharded): the dynamical phase
-        of finalize_slots, the rotation of the second moments and the error algebra of finalize_moments"""
+    def phased_cross(cross, t0, dt, energy0_es):
+        """(C, m3): the cross-correlation functions C_k(t), complex (nt, K), and the second-moment sums (S_rr, S_ii, S_ri) of the
+        phased terms (nt, K, 3) from the raw rows (nt, K, 5) of run(..., cross=...): the dynamical phase of finalize_slots and the
+        rotation of phased_moments"""
         raw = cross.detach().cpu().numpy() if isinstance(cross, torch.Tensor) else np.asarray(cross)
         times = t0 + hostmath.time_grid(raw.shape[0], dt)
         C = (raw[:, :, 0] + 1j * raw[:, :, 1]) * np.exp(1j / hbar * times * energy0_es)[:, None]
-        m3 = hostmath.rotate_second_moments(raw[:, :, 2:5], (times * energy0_es / hbar)[:, None])
+        return C, hostmath.rotate_second_moments(raw[:, :, 2:5], (times * energy0_es / hbar)[:, None])
+
+    @staticmethod
+    def finalize_cross(cross, t0, dt, energy0_es, ntraj_norm):
+        """(C, sigma), complex (nt, K): the cross-correlation functions C_k(t) and their Monte-Carlo standard errors
+        sigma_Re + i sigma_Im from the raw rows (nt, K, 5) of run(..., cross=...) (summed over ranks when sharded): phased_cross and
+        the error algebra of finalize_moments"""
+        C, m3 = HermanKlukPropagator.phased_cross(cross, t0, dt, energy0_es)
         return C, hostmath.standard_errors(C, m3, ntraj_norm)
 
     def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
@@ -815,13 +873,6 @@ class HermanKlukPropagator(object):
             targets = self._cross_targets(q_targets, p_targets)
             if cross is None:
                 cross = torch.zeros((nt, targets["K"], 5), dtype=F64, device=self.device)
-            elif not (isinstance(cross, torch.Tensor) and cross.dtype == F64 and cross.dim() == 3 and cross.shape[0] >= nt
-                      and tuple(cross.shape[1:]) == (targets["K"], 5) and cross.is_contiguous() and cross.device == self.device):
-                raise ValueError(f"cross has to be a contiguous float64 tensor of shape (>= {nt}, {targets['K']}, 5) on {self.device}, "
-                                 f"got {getattr(cross, 'dtype', type(cross))} {tuple(getattr(cross, 'shape', ()))} on "
-                                 f"{getattr(cross, 'device', '?')}")
-        xbase = None if targets is None else cross.data_ptr()
-        xrow = (lambda k: None) if xbase is None else (lambda k: (targets, xbase + 40 * targets["K"] * k))
         dt = float(dt)
         self._remember_nac(potential)
         own = slots is None
@@ -831,42 +882,31 @@ class HermanKlukPropagator(object):
             slots = torch.zeros((nt, 5), dtype=F64, device=self.device)
             if standard_errors and moments is None:
                 moments = torch.zeros((nt, 6), dtype=F64, device=self.device)
-        else:
-            self._check_slots(slots, nt)
-        if moments is not None:
-            self._check_slots(moments, nt, width=6, name="moments")
-        nblocks = None if blocks is None else self._check_blocks(blocks, nt)
-        bbase = None if blocks is None else blocks.data_ptr()
-        brow = (lambda k: None) if bbase is None else (lambda k: (bbase + 32 * nblocks * k, nblocks))
+        rows = self._rows(self.device, nt, slots, moments, blocks, cross, None if targets is None else targets["K"])
         t0 = self.t
-        base = slots.data_ptr()
-        mbase = None if moments is None else moments.data_ptr()
-        mrow = (lambda k: None) if mbase is None else (lambda k: mbase + 48 * k)
         fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model") and self.dim <= 64
                  and self._nac_generic is None)
         desc = self._potential_descriptor(potential, dt) if fused else None
         if fused and targets is None and self._whole_loop_applies(desc):
             # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run; it exports no per-step state
             # for the targets of a cross-correlation)
-            self._run_whole_loop(desc, dt, nt, slots, potential, moments, blocks)
+            self._run_whole_loop(desc, dt, nt, rows, potential)
         elif (use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing
               and self._modal_step_constants(potential, desc, dt) is None):
             # (the normal-mode step runs the plain loop: its first step may change the basis of the blocks)
-            self._run_graph(potential, dt, nt, desc, slots, mbase, brow(0))
+            self._run_graph(potential, dt, nt, desc, rows)
         else:
             pairs = fused and nt >= 2 and self._multi_applies(desc)
             kmax = self._visit_steps_for(desc) if pairs else 1
             k = 0
             while k < nt:
-                self._launch_correlate(base + 40 * k, per_trajectory=False, slot_row=slots[k], mom_ptr=mrow(k), blk=brow(k),
-                                       cross=xrow(k))
+                self._launch_correlate(rows.row(k), per_trajectory=False, targets=targets)
                 ks = min(kmax, nt - k) if pairs else 1       # never a visit longer than the steps left
                 if ks == 2:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
-                    self._launch_correlate(base + 40 * (k + 1), per_trajectory=False, state=self._multi["state_mid"],
-                                           mom_ptr=mrow(k + 1), blk=brow(k + 1), cross=xrow(k + 1))
+                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, targets=targets)
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -875,8 +915,7 @@ class HermanKlukPropagator(object):
                     # and blocks comes from the j-th intermediate state
                     self._launch_step_visit(desc, dt, ks)
                     for j in range(1, ks):
-                        self._launch_correlate(base + 40 * (k + j), per_trajectory=False, state=self._multi["states_mid"][j - 1],
-                                               mom_ptr=mrow(k + j), blk=brow(k + j), cross=xrow(k + j))
+                        self._launch_correlate(rows.row(k + j), self._multi["states_mid"][j - 1], per_trajectory=False, targets=targets)
                     for _ in range(ks):
                         self.t += dt
                     k += ks
@@ -903,11 +942,12 @@ class HermanKlukPropagator(object):
         coupling is known (call ic_correlation(potential) first).  Synchronises."""
         slot = torch.zeros((1, 5), dtype=F64, device=self.device)
         mom = torch.zeros((1, 6), dtype=F64, device=self.device)
-        self._launch_correlate(slot.data_ptr(), slot_row=slot[0], mom_ptr=mom.data_ptr())
+        self._launch_correlate(self._rows.single(slot, mom))
         self.synchronize()
         sc, sk = self.finalize_moments(slot, mom, self.t, 0.0, energy0_es, self._ntraj_norm)
         return complex(sc[0]), complex(sk[0])
 
+    _rows = _StepRows               # widths, strides and validation of the output buffers of run()
     _whole_loop_ok = True           # WM needs its own per-step kernel between the steps
     _cross_ok = True                # WM has per-trajectory widths and another prefactor: no cross-correlation
 
@@ -1005,7 +1045,7 @@ class HermanKlukPropagator(object):
             self._to_normal_modes(self._modal_basis, forward=False)
             self._modal_basis = None
 
-    def _run_whole_loop(self, desc, dt, nt, slots, potential=None, moments=None, blocks=None):
+    def _run_whole_loop(self, desc, dt, nt, rows, potential=None):
         self._leave_modal()
         if desc.kind not in _lib.SEPARABLE_KINDS:
             self._blocks_structurally_diagonal = False
@@ -1015,7 +1055,7 @@ class HermanKlukPropagator(object):
         # (<= 84 MB of partials at 4096 slots, reused: the launches are ordered on the stream), the state stays on the device
         # in between and is read / written once per launch (<= 1 KB per trajectory at D <= 12: negligible against 512 steps)
         chunk = min(nt, 512)
-        mom = moments is not None
+        mom = rows.moments is not None
         partials = torch.empty(lib.sc_hk_run_scratch_doubles(self.ntraj, self.dim, chunk, int(mom)), dtype=F64, device=self.device)
         nac = self._nac
         modal = self._modal_constants(potential, desc, dt) if nt >= self.normal_modes_from else None
@@ -1023,21 +1063,21 @@ class HermanKlukPropagator(object):
             self._to_normal_modes(modal, forward=True)
         for k0 in range(0, nt, chunk):
             k = min(chunk, nt - k0)
-            tail = (ptr(partials), slots.data_ptr() + 40 * k0, ptr(self._elog), self._stream())
+            first = rows.row(k0)              # this launch fills the piece of the buffers from step k0 on
+            tail = (ptr(partials), first.slot, ptr(self._elog), self._stream())
             head = (self._ovl_t0, nac, ptr(self._vi), ptr(self.probi), ptr(self._nacq) if nac is not None else None, self._mc_norm(), dt, k)
             if mom:
-                tail = tail[:3] + (C_void(moments.data_ptr() + 48 * k0), tail[3])
+                tail = tail[:3] + (C_void(first.moments), tail[3])
             if modal is not None:
                 run = lib.sc_hk_run_modal_m if mom else lib.sc_hk_run_modal
                 check(run(desc, self._state, modal["hk"], *head, ptr(modal["phi"]), *tail))
             else:
                 run = lib.sc_hk_run_m if mom else lib.sc_hk_run
                 check(run(desc, self._state, self._hk, *head, *tail))
-            if blocks is not None:
+            if first.blocks is not None:
                 # block sums of this launch's per-wavefront partials, before the next launch reuses the scratch
-                nblocks = blocks.shape[1]
-                check(lib.sc_hk_run_blocks(ptr(partials), self.ntraj, self.dim, k, nblocks,
-                                           C_void(blocks.data_ptr() + 32 * nblocks * k0), self._stream()))
+                out, nblocks = first.blocks
+                check(lib.sc_hk_run_blocks(ptr(partials), self.ntraj, self.dim, k, nblocks, C_void(out), self._stream()))
         if modal is not None:
             self._to_normal_modes(modal, forward=False)
         self._run_scratch = partials          # alive until the stream has consumed it
@@ -1133,13 +1173,13 @@ class HermanKlukPropagator(object):
             check(lib.sc_energy_guard(C_void(m["epart"].data_ptr() + 8 * sub * self._gstep), self._gstep, float(n), ptr(self._elog), s))
         self._nsteps += ks
 
-    def _run_graph(self, potential, dt, nt, desc, slots, mbase=None, blk=None):
+    def _run_graph(self, potential, dt, nt, desc, rows):
         """first iteration eagerly (lazy set-up, layout conversion), then one captured iteration replayed nt - 1 times"""
-        base = slots.data_ptr()
+        base = rows.row(0)
         cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
 
         def iteration():
-            self._launch_correlate(base, per_trajectory=False, cursor=cursor, mom_ptr=mbase, blk=blk)
+            self._launch_correlate(base, cursor=cursor, per_trajectory=False)
             self._launch_step(potential, dt, desc=desc, remembered=True)
         iteration()
         graph = torch.cuda.CUDAGraph()
@@ -1156,26 +1196,6 @@ class HermanKlukPropagator(object):
         if hasattr(self, "_wm_step"):
             self._wm_step = self._nsteps      # the WM terms of the current state were produced by the last replay
         self._graph = graph                  # keeps the captured launch parameters alive until the work has run
-
-    def _check_slots(self, slots, nt, width=5, name="slots"):
-        """the kernels write `width` doubles at slots + 8 width k for k < nt: refuse anything that is not exactly that buffer"""
-        if not (isinstance(slots, torch.Tensor) and slots.dtype == F64 and slots.dim() == 2 and slots.shape[1] == width
-                and slots.shape[0] >= nt and slots.is_contiguous() and slots.device == self.device):
-            raise ValueError(f"{name} has to be a contiguous float64 tensor of shape (>= {nt}, {width}) on {self.device}, got "
-                             f"{getattr(slots, 'dtype', type(slots))} {tuple(getattr(slots, 'shape', ()))} on "
-                             f"{getattr(slots, 'device', '?')}")
-
-    def _check_blocks(self, blocks, nt):
-        """the kernels write B x 4 doubles at blocks + 32 B k for k < nt: refuse anything that is not exactly that buffer; returns B"""
-        if not (isinstance(blocks, torch.Tensor) and blocks.dtype == F64 and blocks.dim() == 3 and blocks.shape[2] == 4
-                and blocks.shape[0] >= nt and blocks.is_contiguous() and blocks.device == self.device):
-            raise ValueError(f"blocks has to be a contiguous float64 tensor of shape (>= {nt}, B, 4) on {self.device}, got "
-                             f"{getattr(blocks, 'dtype', type(blocks))} {tuple(getattr(blocks, 'shape', ()))} on "
-                             f"{getattr(blocks, 'device', '?')}")
-        nblocks = int(blocks.shape[1])
-        if not hostmath.valid_error_blocks(nblocks):
-            raise ValueError(f"the number of blocks has to be a power of two in 2 ... 64, got {nblocks}")
-        return nblocks
 
     @staticmethod
     def block_counts(n, B):
@@ -1780,8 +1800,8 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
-    def _launch_correlate(self, slot_ptr, per_trajectory=True, cursor=None, slot_row=None, mom_ptr=None, blk=None, cross=None):
-        assert cross is None          # run(targets=...) is refused before the loop starts
+    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None):
+        assert state is None and targets is None          # no pairs or visits; run(targets=...) is refused before the loop starts
         # the per-trajectory terms were produced together with the prefactor; recompute (with the stored branch
         # signs, no tracking) only if the coupling vector was not known at that time
         knows_nac = self._wm_nac_bufs is not None or self._wm_nac_traj is not None
@@ -1790,21 +1810,19 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         if self._kept is not None:
             # discard mask: every sum from the exported terms, over the kept trajectories (sc_term_masked_sums)
             assert cursor is None
-            self._masked_sums(self._wm_has_nac, slot_ptr, mom_ptr, blk)
+            self._masked_sums(self._wm_has_nac, row)
             return
-        rows = None
-        if mom_ptr is not None:
-            # sc_wm_correlate exports every trajectory's terms exactly once (register kernel or its pivoted re-run): their moments,
-            # in a pass of its own (not fused into the WM kernels)
-            rows = self._term_moments(self._wm_has_nac)
-        if blk is not None:
-            self._term_blocks(self._wm_has_nac, blk, cursor)         # the same exported terms; before the cursor advances
-        self._reduce_into(self._wpart, self._gwm, slot_ptr, cursor, mom_ptr, rows)
+        # sc_wm_correlate exports every trajectory's terms exactly once (register kernel or its pivoted re-run): their moments,
+        # in a pass of its own (not fused into the WM kernels)
+        mom_rows = self._term_moments(self._wm_has_nac) if row.moments is not None else None
+        if row.blocks is not None:
+            self._term_blocks(self._wm_has_nac, row.blocks, cursor)         # the same exported terms; before the cursor advances
+        self._reduce_into(self._wpart, self._gwm, row, cursor, mom_rows)
 
     def _correlate_current(self, need_nac):
         if self._corr_step == self._nsteps and (self._corr_has_nac or not need_nac):
             return
-        self._launch_correlate(self._slot.data_ptr())
+        self._launch_correlate(self._rows.single(self._slot))
         self._corr_step, self._corr_has_nac = self._nsteps, self._wm_has_nac
         self._slot_host = self._slot.cpu().numpy().copy()
         self._check_energy_guard()

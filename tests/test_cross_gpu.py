@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import cases
+from tests.lib_spy import LibSpy as _Spy
 from tests.test_cross_host import exact_overlaps, overlap_constants, psd_sqrt, restated_cross, width_targets, within_five_sigma
 
 pytestmark = pytest.mark.gpu
@@ -240,23 +241,6 @@ def test_c_abi_refusals():
 
 
 # ------------------------------------------------------------------------------------------- 7. run(targets=...)
-
-class _Spy(object):
-    """counts the calls the propagators module makes to the C-ABI"""
-
-    def __init__(self, monkeypatch):
-        from semiclassical_amd import propagators as PR
-        self.real, self.seen = PR.lib, {}
-        monkeypatch.setattr(PR, "lib", self)
-
-    def __getattr__(self, name):
-        fn = getattr(self.real, name)
-
-        def counted(*a):
-            self.seen[name] = self.seen.get(name, 0) + 1
-            return fn(*a)
-        return counted
-
 
 ROUTES = [
     # case, nt, attributes, the entry point that has to run, bit-identical rows promised

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import cases, engine_cases, symplectic_ref as R
+from tests.lib_spy import LibSpy as _Spy
 
 pytestmark = pytest.mark.gpu
 torch.set_default_dtype(torch.float64)
@@ -305,23 +306,6 @@ def assert_run_against_host(run, rows, n, label):
         assert_within_bound(mom[k], want[1], scale[1], n, f"{label} step {k} moments")
         assert_within_bound(blocks[k], want[2], scale[2], n, f"{label} step {k} blocks")
         assert np.all(scale[0] > 0), "a column of kept terms is all zero: the comparison says nothing"
-
-
-class _Spy(object):
-    """counts the calls the propagators module makes to the C-ABI"""
-
-    def __init__(self, monkeypatch):
-        from semiclassical_amd import propagators as PR
-        self.real, self.seen = PR.lib, {}
-        monkeypatch.setattr(PR, "lib", self)
-
-    def __getattr__(self, name):
-        fn = getattr(self.real, name)
-
-        def counted(*a):
-            self.seen[name] = self.seen.get(name, 0) + 1
-            return fn(*a)
-        return counted
 
 
 def test_routes_agree_d33(monkeypatch):

@@ -9,31 +9,13 @@ import pytest
 import torch
 
 from tests import cases, engine_cases
+from tests.lib_spy import LibSpy
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 torch.set_default_dtype(torch.float64)
 
 TOL = 1e-12
-
-
-def _spy(monkeypatch, names):
-    """count the calls of the named C-ABI entry points made by the propagators module"""
-    from semiclassical_amd import propagators as PR
-    real, seen = PR.lib, {}
-
-    class Lib(object):
-        def __getattr__(self, name):
-            fn = getattr(real, name)
-            if name not in names:
-                return fn
-
-            def counted(*a):
-                seen[name] = seen.get(name, 0) + 1
-                return fn(*a)
-            return counted
-    monkeypatch.setattr(PR, "lib", Lib())
-    return seen
 
 
 def _group(terms, local, B):
@@ -82,7 +64,7 @@ def _check_route(monkeypatch, make, pot, dt, nt, B, entry, setup=None, kw=None, 
         slots = torch.zeros((nt, 5), device=prop.device)
         mom = torch.zeros((nt, 6), device=prop.device) if moments else None
         blocks = torch.full((nt + 1, B, 4), 7.5, device=prop.device) if with_blocks else None
-        seen = _spy(monkeypatch, {entry}) if with_blocks else {}
+        seen = LibSpy(monkeypatch, {entry}).seen if with_blocks else {}
         prop.run(pot, dt, nt, slots=slots, moments=mom, blocks=blocks, **kw)
         prop.synchronize()
         monkeypatch.undo()
@@ -154,7 +136,7 @@ def test_whole_loop_constant_dense_hessian(monkeypatch, nt, entry):
     args, G, q0, p0 = _random_case(6, 0, False, 77)
     pot = P.MolecularHarmonicPotential.from_arrays(*args, origin=-0.3)
     make = _sampled(G, q0, 203, p0=p0)
-    seen = _spy(monkeypatch, {entry})
+    seen = LibSpy(monkeypatch, {entry}).seen
     probe = make()
     probe.run(pot, 4.0, nt, slots=torch.zeros((nt, 5), device=probe.device))
     probe.synchronize()
@@ -175,7 +157,7 @@ def test_tiled_fast_path(monkeypatch, setup, kw, entry, also):
     """D = 20 separable, five steps: two pairs and a single last step; one launch per step; the captured graph"""
     pot, G, q0 = _morse(20, 3)
     make = _sampled(G, q0, 203)
-    seen = _spy(monkeypatch, {also})
+    seen = LibSpy(monkeypatch, {also}).seen
     probe = make()
     if setup:
         setup(probe)

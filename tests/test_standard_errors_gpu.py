@@ -39,7 +39,7 @@ def _reference_moments(name, nt, setup=None):
         prop.ic_correlation(pot)
         mom = torch.zeros(6, dtype=torch.float64, device=prop.device)
         slot = torch.zeros(5, dtype=torch.float64, device=prop.device)
-        prop._launch_correlate(slot.data_ptr(), slot_row=slot, mom_ptr=mom.data_ptr())
+        prop._launch_correlate(prop._rows.single(slot, mom))
         want = _six(prop._cq, prop._kq)
         _close(mom.cpu().numpy(), want.cpu().numpy(), STEP_TOL)
         rows.append(want.cpu().numpy())

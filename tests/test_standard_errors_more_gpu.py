@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import cases, engine_cases
+from tests.lib_spy import LibSpy
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,24 +78,6 @@ def test_moments_match_the_oracle_terms(name, tol):
 
 
 # ------------------------------------------------------------------------------------------------ further routes
-def _spy(monkeypatch, names):
-    from semiclassical_amd import propagators as PR
-    real, seen = PR.lib, {}
-
-    class Lib(object):
-        def __getattr__(self, name):
-            fn = getattr(real, name)
-            if name not in names:
-                return fn
-
-            def counted(*a):
-                seen[name] = seen.get(name, 0) + 1
-                return fn(*a)
-            return counted
-    monkeypatch.setattr(PR, "lib", Lib())
-    return seen
-
-
 def _generic(D, n, nt, dt=1.0):
     """the coupled quartic of tests/branch_cases.py (no device descriptor: dense, position-dependent Hessian), at a step short
     enough that the energy guard stays quiet over nt steps from its wide initial spread"""
@@ -215,13 +198,13 @@ def test_moments_on_the_remaining_routes(monkeypatch, name, build, route):
         runs.append((slots.cpu().numpy(), None if moments is None else moments.cpu().numpy()))
     assert np.array_equal(runs[0][0][:, :4], runs[1][0][:, :4]), "C or k changed with moments on"
     prop = make()
-    seen = _spy(monkeypatch, SPIED)
+    seen = LibSpy(monkeypatch, SPIED).seen
     rows, flags = [], []
     for _ in range(nt):
         prop.ic_correlation(pot)
         mom = torch.zeros(6, device=prop.device)
         slot = torch.zeros(5, device=prop.device)
-        prop._launch_correlate(slot.data_ptr(), slot_row=slot, mom_ptr=mom.data_ptr())
+        prop._launch_correlate(prop._rows.single(slot, mom))
         want = _six(prop._cq, prop._kq).cpu().numpy()
         assert np.all(_rel_cols(mom.cpu().numpy()[None], want[None]) < 1e-12)
         if hasattr(prop, "_wm_flags"):
