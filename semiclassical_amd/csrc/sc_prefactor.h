@@ -12,13 +12,18 @@ __device__ cplx lds_lu_det(cplx *A, int d, int *ipiv) {
     cplx det = c_make(1.0, 0.0);
     for (int k = 0; k < d; ++k) {
         if (wave == 0) {
-            // candidate rows i = k + lane (and k + lane + 64 for d > 64): the larger one per lane, then a DPP maximum
+            // candidate rows k + lane, k + lane + 64, k + lane + 128, ... up to d - 1, i.e. the whole column below the diagonal:
+            // the largest one per lane (strictly larger, so a lane's lower row wins a tie), then a DPP maximum over the lanes
             int i = k + lane;
             const bool valid = i < d;
             double mag = valid ? c_abs2(A[i * d + k]) : 0.0;
             if (i + 64 < d) {
                 const double m2 = c_abs2(A[(i + 64) * d + k]);
                 if (m2 > mag) { mag = m2; i += 64; }
+            }
+            for (int r = k + lane + 128; r < d; r += 64) {        // d > 128 only (the any-dimension kernel)
+                const double m2 = c_abs2(A[r * d + k]);
+                if (m2 > mag) { mag = m2; i = r; }
             }
             int bi = wave_pivot_row(mag, i, valid);
             if (bi < 0) bi = k;

@@ -111,13 +111,49 @@ def test_gdml_large_against_extended_precision():
         assert dh <= 3.0 * do + 1e-15, (name, dh, do)
 
 
+class _PrefactorReference(object):
+    """Reference for c2 = det(prefactor matrix) and for the branch sign of its square root, for the first `check` trajectories:
+    the determinant, in extended precision (tests/det_cases.py), of the prefactor matrix formed from the ORACLE's monodromy
+    blocks, and the rule of the sqrt tracker (reference propagators.py:1045-1047) applied to the sequence of these values,
+    starting from c2 = 1 at t = 0.  Not oracle.c2 and the oracle's tracker: torch.det on the host was seen 1e-6 ... 3e-5 away
+    from this reference and, in other processes, with the opposite sign at D = 168 and 300, which also flips signs of the
+    oracle's tracker; the kernels stay within 2e-13 of the reference."""
+
+    def __init__(self, width, check=2, history=()):
+        self.width, self.check, self.history = width, check, []
+        self.prev, self.sgn = np.ones(check, dtype=np.complex128), np.ones(check)
+        for c2 in history:
+            self._track(c2)
+
+    def _track(self, c2):
+        flip = (self.prev.real < 0) & (c2.real < 0) & (self.prev.imag * c2.imag < 0)
+        self.sgn = np.where(flip, -self.sgn, self.sgn)
+        self.prev = c2
+        self.history.append(c2)
+
+    def matches(self, prop, oracle, what):
+        """advance the reference to the oracle's current blocks and compare the engine's c2 (1e-8, the tolerance of
+        test_more_than_64_dimensions_through_the_dense_path) and sign with it"""
+        from tests import det_cases as dc
+        n = self.check
+        mono = np.stack([b.permute(2, 0, 1)[:n].numpy() for b in oracle.monodromy_matrices()], axis=1)
+        s = np.full(mono.shape[-1], np.sqrt(self.width))
+        want = np.array([dc.det_longdouble(m) for m in dc.prefactor_diag_numpy(mono, s, s)])
+        self._track(want.astype(np.complex128))
+        err = dc.rel_err(cnp(prop._c2)[:n], want)
+        print(f"{what}: c2 vs extended precision {err.max():.2e}, oracle's c2 vs the same "
+              f"{dc.rel_err(oracle.c2.numpy()[:n], want).max():.2e}, signs {self.sgn}")
+        assert err.max() < 1e-8, (what, err)
+        assert np.array_equal(cnp(prop._sgn)[:n], self.sgn), (what, cnp(prop._sgn), self.sgn)
+
+
 @pytest.mark.parametrize("N,M", [(56, 30), (100, 14)])
 def test_gdml_large_hk_steps_and_run_match_oracle(N, M):
     """D = 168 and D = 300: HK steps through sc_gdml_stage x 4 and the any-dimension monodromy kernels, then run() from
-    the initial conditions: q, p, S and the four monodromy blocks against the oracle.  The prefactor c2 and with it C(t),
-    k_ic(t) are not compared: at these dimensions (D > 130) the HK prefactor of the any-dimension kernels disagrees with
-    the oracle's and run() returns NaN correlation functions, from the blocks this route reproduces to 1e-16 (DESIGN
-    section 8)."""
+    the initial conditions: q, p, S and the four monodromy blocks against the oracle, the prefactor c2 and the sign of its
+    square root against an extended-precision determinant of the oracle's blocks (_PrefactorReference).  C(t) and k_ic(t) are NaN in the oracle itself for these widths: its overlap normalisation forms
+    det(Gamma_i + Gamma_0) = 80^D, which overflows a double from D = 162 on (and the sampling density underflows to 0 at
+    D = 300); the engine has to return NaN in the same places."""
     from oracle import sc_oracle as orc
     from semiclassical_amd.gdml import MolecularGDMLPotential
     from semiclassical_amd import propagators as PR
@@ -135,9 +171,11 @@ def test_gdml_large_hk_steps_and_run_match_oracle(N, M):
     oprop.initial_conditions(q0, 0.0 * q0, G, ntraj=ntraj)
     prop = PR.HermanKlukPropagator(G, G, device="cuda")
     prop.set_initial_conditions(q0, 0.0 * q0, G, oprop.zi, oprop.probi)
+    pre = _PrefactorReference(40.0)
     for _ in range(2):
         oprop.step(opot, dt)
         prop.step(pot, dt)
+        pre.matches(prop, oprop, f"D = {3 * N}, step")
     dy = cases.rel_err(cnp(prop.y), oprop.y.numpy())
     print(f"two HK steps at D = {3 * N}: y {dy:.2e}")
     assert dy < 1e-12
@@ -146,13 +184,19 @@ def test_gdml_large_hk_steps_and_run_match_oracle(N, M):
     ref = orc.HKOracle(G, G)
     torch.manual_seed(4)
     ref.initial_conditions(q0, 0.0 * q0, G, ntraj=ntraj)
-    orc.run_loop(ref, opot, dt, nt, E0)
+    rc, rk = orc.run_loop(ref, opot, dt, nt, E0)
     prop = PR.HermanKlukPropagator(G, G, device="cuda")
     prop.set_initial_conditions(q0, 0.0 * q0, G, ref.zi, ref.probi)
     c, k = prop.run(pot, dt, nt, E0)
     dy = cases.rel_err(cnp(prop.y), ref.y.numpy())
     print(f"run() at D = {3 * N}: y after {nt} steps {dy:.2e}")
     assert dy < 1e-12
+    # the first two steps of run() are the two steps above (same initial conditions): the branch rule sees the same c2 history
+    _PrefactorReference(40.0, history=pre.history).matches(prop, ref, f"D = {3 * N}, run()")
+    c, k = np.asarray(c), np.asarray(k)
+    assert np.array_equal(np.isnan(c), np.isnan(rc)) and np.array_equal(np.isnan(k), np.isnan(rk))
+    np.testing.assert_allclose(c, rc, rtol=1e-8, atol=0.0, equal_nan=True)
+    np.testing.assert_allclose(k, rk, rtol=1e-8, atol=0.0, equal_nan=True)
 
 
 def test_gdml_refuses_171_atoms():
