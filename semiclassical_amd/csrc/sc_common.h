@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "semiclassical_hip.h"
 
 #define SC_HBAR 1.0   // reference semiclassical/units.py:8
@@ -242,6 +244,57 @@ __device__ __forceinline__ bool crossed_branch_cut(cplx prev, cplx det) {
     return prev.x < 0.0 && det.x < 0.0 && prev.y * det.y < 0.0;
 }
 
+// What one trajectory contributes to C_auto(t) and k_ic(t), defined ONCE like the step physics above: every HK route calls
+// these.  Do not reorder an operation here, and do not merge or split these functions without comparing the results of every
+// caller bit for bit: hipcc contracts products and sums into fused multiply-adds per kernel, and the cut into functions decides
+// which ("One definition of the correlation terms").
+//
+// <q, p, Gamma_t | qk, pk, Gamma_0> from the four exponent sums dq.A.dq, dp.B.dp, pk.dq, dq.C.dp (propagators.py:232-237)
+// (fac = sc_overlap_consts.fac.  These helpers take scalars, not the structs of constants: with a reference to a part of the
+// kernel's argument block the whole-loop kernels are compiled with other branches and other register counts.)
+__device__ __forceinline__ cplx overlap_value(double fac, double sA, double sB, double sP, double sC) {
+    const cplx ex = c_make(-0.5 * sA - 0.5 / (SC_HBAR * SC_HBAR) * sB, (-sP + sC) / SC_HBAR);
+    return c_scale(c_exp(ex), fac);
+}
+
+// those four sums for diagonal width matrices, and the two coupling sums of nacQ: this lane's mode, summed over the lanes by
+// `sum` (wave_sum or row_sum) one term after the other -- with all terms formed first hk_correlate_kernel needs 8 VGPRs more
+template <class SUM>
+__device__ __forceinline__ void overlap_sums_diag(double qk, double pk, double ocA, double ocB, double ocC, double q, double p, SUM sum,
+                                                  double &sA, double &sB, double &sP, double &sC) {
+    const double dq = qk - q, dpp = pk - p;
+    sA = sum(dq * ocA * dq); sB = sum(dpp * ocB * dpp); sP = sum(pk * dq); sC = sum(dq * ocC * dpp);
+}
+template <class SUM>
+__device__ __forceinline__ void nac_sums(double nq0, double np0, double nrn, double ngn, double q, double p, SUM sum, double &sR, double &sG) {
+    sR = sum((nq0 - q) * nrn); sG = sum((p - np0) * ngn);
+}
+
+// the trajectory's own factors: the signed principal root of the prefactor's square, and the action phase (propagators.py:784-807)
+__device__ __forceinline__ cplx signed_root(cplx c2, double sgn) { return c_scale(c_sqrt(c2), sgn); }
+__device__ __forceinline__ cplx action_phase(double S) { return c_exp(c_make(0.0, S / SC_HBAR)); }
+
+// conj(vt) = <q0, p0, Gamma_0 | q, p, Gamma_t> as the terms of C_auto take it.  A function of its own next to the product with
+// `fac`: hipcc folds the sign into that product and then forms a b + c d of the next complex product as one multiply and one fused
+// multiply-add -- WHICH product it fuses, and with it the last bit of the terms, follows from where the sign sits
+__device__ __forceinline__ cplx overlap_value_conj(double fac, double sA, double sB, double sP, double sC) {
+    const cplx vt = overlap_value(fac, sA, sB, sP, sC);
+    return c_conj(vt);
+}
+
+// term of C_auto: conj(vt) vi (c ph) w with cvt = overlap_value_conj(...), vi the initial overlap, c = signed_root(...), ph =
+// action_phase(...), w the Monte-Carlo weight; the callers form cvt, c, ph, w in this order, between their loads
+__device__ __forceinline__ cplx corr_c_term(cplx cvt, cplx vi, cplx c, cplx ph, double w) {
+    return c_scale(c_mul(c_mul(cvt, vi), c_mul(c, ph)), w);
+}
+
+// term of k_ic from the term of C_auto: nacQ nacq cq / hbar^2 with n2, p0n1 of sc_nac_consts (propagators.py:886-909).  The
+// caller keeps its `if (nac)` around the call: with the branch in here hk_run_sep16_kernel needs 80 bytes of scratch per lane more.
+__device__ __forceinline__ cplx corr_k_term(double n2, double p0n1, double sR, double sG, cplx nacq, cplx cq) {
+    const cplx nacQ = c_make(n2 + sR, -(p0n1 + sG) / SC_HBAR);
+    return c_scale(c_mul(c_mul(nacQ, nacq), cq), 1.0 / (SC_HBAR * SC_HBAR));
+}
+
 // The partition of a batch into B blocks for the Monte-Carlo error bars (batch means), defined ONCE: the
 // block of the trajectory with rank-local index i.  Groups of four consecutive trajectories go round robin to the blocks; B is a
 // power of two in 2 ... 64.  The trajectories are independent draws, so any fixed partition is valid; this one is what the
@@ -251,6 +304,19 @@ __host__ __device__ __forceinline__ bool sc_error_blocks_valid(int B) { return B
 
 #define SC_SEP16_MAX_D 12   // D <= 12: hk_step_sep16_kernel (four trajectories per wavefront); 13 .. 16: hk_step_w16_kernel
 int sc_launch_step_sep16(const StepArgs &a, int grid_entries, hipStream_t s);   // sc_hk_step_sep16.hip: 1 launched, 0 not taken
+// the KIND x DP instantiations of the separable kernels for D <= SC_SEP16_MAX_D, chosen ONCE: f(dp, kind) is called with
+// std::integral_constant<int, DP> (D rounded up to 4, 8, 12) and std::integral_constant<int, KIND> (the potential family)
+template <class F>
+inline void sc_sep16_dispatch(int kind, int D, F &&f) {
+    auto with_dp = [&](auto dp) {
+        if (kind == SC_POT_MORSE) f(dp, std::integral_constant<int, SC_POT_MORSE>{});
+        else if (kind == SC_POT_HARMONIC_SEP) f(dp, std::integral_constant<int, SC_POT_HARMONIC_SEP>{});
+        else f(dp, std::integral_constant<int, SC_POT_EPS_MORSE>{});
+    };
+    if (D <= 4) with_dp(std::integral_constant<int, 4>{});
+    else if (D <= 8) with_dp(std::integral_constant<int, 8>{});
+    else with_dp(std::integral_constant<int, 12>{});
+}
 int sc_launch_step_sd_multi(const StepArgs &a, const sc_multi_scratch &ms, int ksteps, hipStream_t s);    // sc_hk_step_sd.hip: ksteps = 2 .. 4 steps per visit
 int sc_launch_step_lin(const StepArgs &a, int grid, hipStream_t s);   // sc_hk_step_lin.hip: 1 launched, 0 shape not built
 

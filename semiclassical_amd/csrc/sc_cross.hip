@@ -72,9 +72,9 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
         const int64_t tr = i0 + tid;
         const bool in = tid < iv && (!A.kept || A.kept[tr]);
         if (in) {
-            // as hk_correlate_kernel: the signed principal root, the action's phase, the initial overlap, the Monte-Carlo weight
-            const cplx c = c_scale(c_sqrt(((const cplx *)A.st.c2)[tr]), A.st.sgn[tr]);
-            const cplx ph = c_exp(c_make(0.0, A.st.act[tr] / SC_HBAR));
+            // signed_root and action_phase (sc_common.h: what hk_correlate_kernel calls), the initial overlap, the Monte-Carlo weight
+            const cplx c = signed_root(((const cplx *)A.st.c2)[tr], A.st.sgn[tr]);
+            const cplx ph = action_phase(A.st.act[tr]);
             const double w = 1.0 / (A.mc_norm * A.probi[tr]);
             v = c_scale(c_mul(((const cplx *)A.vi)[tr], c_mul(c, ph)), w);
         }

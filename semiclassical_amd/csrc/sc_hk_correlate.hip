@@ -57,11 +57,6 @@ __device__ __forceinline__ void overlap_sums(const sc_overlap_consts &oc, const 
     sA = wave_sum(sA); sB = wave_sum(sB); sP = wave_sum(sP); sC = wave_sum(sC);
 }
 
-__device__ __forceinline__ cplx overlap_value(const sc_overlap_consts &oc, double sA, double sB, double sP, double sC) {
-    const cplx ex = c_make(-0.5 * sA - 0.5 / (SC_HBAR * SC_HBAR) * sB, (-sP + sC) / SC_HBAR);
-    return c_scale(c_exp(ex), oc.fac);
-}
-
 __global__ __launch_bounds__(256) void overlap_kernel(OverlapArgs A) {
     extern __shared__ double smem[];
     const int D = A.oc.dim, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(256) void overlap_kernel(OverlapArgs A) {
     for (int64_t tr = (int64_t)blockIdx.x * nw + wave; tr < A.n; tr += (int64_t)gridDim.x * nw) {
         double sA, sB, sP, sC;
         overlap_sums(A.oc, A.qp + tr * 2 * D, dvec, sA, sB, sP, sC);
-        if (lane == 0) ((cplx *)A.out)[tr] = overlap_value(A.oc, sA, sB, sP, sC);
+        if (lane == 0) ((cplx *)A.out)[tr] = overlap_value(A.oc.fac, sA, sB, sP, sC);
     }
 }
 
@@ -167,10 +162,10 @@ __global__ __launch_bounds__(256) void hk_correlate_kernel(typename CorrArgsOf<M
                     const double *nx = A.st.qp + (base + j + 1) * 2 * D;
                     qn = own ? nx[lane] : 0.0; pn = own ? nx[D + lane] : 0.0;
                 }
-                const double dq = qk - q, dpp = pk - p;
-                double sA = wave_sum(dq * ocA * dq), sB = wave_sum(dpp * ocB * dpp), sP = wave_sum(pk * dq), sC = wave_sum(dq * ocC * dpp);
-                double sR = 0, sG = 0;
-                if (A.has_nac) { sR = wave_sum((nq0 - q) * nrn); sG = wave_sum((p - np0) * ngn); }
+                auto sum = [](double v) { return wave_sum(v); };
+                double sA, sB, sP, sC, sR = 0, sG = 0;
+                overlap_sums_diag(qk, pk, ocA, ocB, ocC, q, p, sum, sA, sB, sP, sC);
+                if (A.has_nac) nac_sums(nq0, np0, nrn, ngn, q, p, sum, sR, sG);
                 if (lane == j) { mA = sA; mB = sB; mP = sP; mC = sC; mR = sR; mG = sG; }
             }
         } else {
@@ -190,19 +185,16 @@ __global__ __launch_bounds__(256) void hk_correlate_kernel(typename CorrArgsOf<M
         }
         if (lane < cnt) {
             const int64_t tr = base + lane;
-            const cplx vt = overlap_value(A.oc, mA, mB, mP, mC);
-            const cplx c = c_scale(c_sqrt(((const cplx *)A.st.c2)[tr]), A.st.sgn[tr]);
-            const cplx ph = c_exp(c_make(0.0, A.st.act[tr] / SC_HBAR));
+            const cplx cvt = overlap_value_conj(A.oc.fac, mA, mB, mP, mC);
+            const cplx c = signed_root(((const cplx *)A.st.c2)[tr], A.st.sgn[tr]);
+            const cplx ph = action_phase(A.st.act[tr]);
             const double w = 1.0 / (A.mc_norm * A.probi[tr]);
-            cplx cq = c_mul(c_mul(c_conj(vt), ((const cplx *)A.vi)[tr]), c_mul(c, ph));
-            cq = c_scale(cq, w);
+            const cplx cq = corr_c_term(cvt, ((const cplx *)A.vi)[tr], c, ph, w);
             acc[0] += cq.x; acc[1] += cq.y;
             if (A.cq_out) ((cplx *)A.cq_out)[tr] = cq;
             cplx kq = c_make(0.0, 0.0);
             if (A.has_nac) {
-                const cplx nacQ = c_make(A.nc.n2 + mR, -(A.nc.p0n1 + mG) / SC_HBAR);
-                kq = c_mul(c_mul(nacQ, ((const cplx *)A.nacq)[tr]), cq);
-                kq = c_scale(kq, 1.0 / (SC_HBAR * SC_HBAR));
+                kq = corr_k_term(A.nc.n2, A.nc.p0n1, mR, mG, ((const cplx *)A.nacq)[tr], cq);
                 acc[2] += kq.x; acc[3] += kq.y;
                 if (A.kq_out) ((cplx *)A.kq_out)[tr] = kq;
             }
@@ -270,15 +262,8 @@ __global__ __launch_bounds__(256) void hk_correlate_rows16_kernel(typename CorrA
                 constexpr int b = decltype(bc)::value;
                 if (b < D) { fmac_bc<b>(ya, dq, rowA[b]); fmac_bc<b>(yb, dpp, rowB[b]); fmac_bc<b>(yc, dpp, rowC[b]); }
             });
-            double t[6] = {dq * ya, dpp * yb, pk * dq, dq * yc, (nq0 - q) * nrn, (p - np0) * ngn}, s[6] = {0, 0, 0, 0, 0, 0};
-            dpp_guard(t);
-            sfor<0, 16>([&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                if (k < D) {
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) fmac_bc<k>(s[i], t[i], one);
-                }
-            });
+            double s[6] = {dq * ya, dpp * yb, pk * dq, dq * yc, (nq0 - q) * nrn, (p - np0) * ngn};
+            sum_rows<16>(s, one, D);                           // over the lanes k < D
             if (r == j) {
 #pragma unroll
                 for (int i = 0; i < 6; ++i) m[i] = s[i];
@@ -286,19 +271,16 @@ __global__ __launch_bounds__(256) void hk_correlate_rows16_kernel(typename CorrA
         }
         const int64_t tr = batch * 64 + lane;                  // lane (g, r) parked trajectory base + r
         if (tr < n) {
-            const cplx vt = overlap_value(A.oc, m[0], m[1], m[2], m[3]);
-            const cplx c = c_scale(c_sqrt(((const cplx *)A.st.c2)[tr]), A.st.sgn[tr]);
-            const cplx ph = c_exp(c_make(0.0, A.st.act[tr] / SC_HBAR));
+            const cplx cvt = overlap_value_conj(A.oc.fac, m[0], m[1], m[2], m[3]);
+            const cplx c = signed_root(((const cplx *)A.st.c2)[tr], A.st.sgn[tr]);
+            const cplx ph = action_phase(A.st.act[tr]);
             const double w = 1.0 / (A.mc_norm * A.probi[tr]);
-            cplx cq = c_mul(c_mul(c_conj(vt), ((const cplx *)A.vi)[tr]), c_mul(c, ph));
-            cq = c_scale(cq, w);
+            const cplx cq = corr_c_term(cvt, ((const cplx *)A.vi)[tr], c, ph, w);
             acc[0] += cq.x; acc[1] += cq.y;
             if (A.cq_out) ((cplx *)A.cq_out)[tr] = cq;
             cplx kq = c_make(0.0, 0.0);
             if (nac) {
-                const cplx nacQ = c_make(A.nc.n2 + m[4], -(A.nc.p0n1 + m[5]) / SC_HBAR);
-                kq = c_mul(c_mul(nacQ, ((const cplx *)A.nacq)[tr]), cq);
-                kq = c_scale(kq, 1.0 / (SC_HBAR * SC_HBAR));
+                kq = corr_k_term(A.nc.n2, A.nc.p0n1, m[4], m[5], ((const cplx *)A.nacq)[tr], cq);
                 acc[2] += kq.x; acc[3] += kq.y;
                 if (A.kq_out) ((cplx *)A.kq_out)[tr] = kq;
             }

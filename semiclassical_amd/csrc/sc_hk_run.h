@@ -1,5 +1,5 @@
-// Arguments shared by the whole-loop kernels behind sc_hk_run (sc_hk_run_sep16.hip: separable potentials;
-// sc_hk_run_lin.hip: constant dense Hessian).
+// Arguments and launchers shared by the whole-loop kernels behind sc_hk_run (sc_hk_run_sep16.hip: separable
+// potentials; sc_hk_run_lin.hip: constant dense Hessian) and their host side (sc_hk_run.hip).
 #pragma once
 #include "sc_common.h"
 
@@ -23,8 +23,11 @@ struct RunArgs {
 int sc_launch_run_lin(const RunArgs &a, int grid, hipStream_t s, int launch, bool moments = false);
 int sc_launch_run_lin_plain(const RunArgs &a, int grid, hipStream_t s, int launch);
 int sc_launch_run_lin_m(const RunArgs &a, int grid, hipStream_t s, int launch);
-// sc_hk_run_sep16_m.hip: the separable whole-loop kernel of sc_hk_run_m for potential `kind`, D <= 12; returns sc_check_launch
-int sc_launch_run_sep16_m(const RunArgs &a, int grid, hipStream_t s, int kind, int D);
+// sc_hk_run_sep16.hip: the separable whole-loop kernel for a.step.pot.kind, D <= 12; 1 = launched, < 0 on error.
+// moments: the kernels of sc_hk_run_m (sc_hk_run_sep16_m.hip, sc_launch_run_sep16_m).
+int sc_launch_run_sep16(const RunArgs &a, int grid, hipStream_t s, bool moments);
+int sc_launch_run_sep16_plain(const RunArgs &a, int grid, hipStream_t s);
+int sc_launch_run_sep16_m(const RunArgs &a, int grid, hipStream_t s);
 
 // sc_hk_run_m: the second moments (Re C)^2, (Im C)^2, Re C Im C, (Re k)^2, (Im k)^2, Re k Im k of the trajectories whose terms sit
 // in v5[0..3] of the row heads, summed over the wavefront and added to its moment slot of step k -- one writer per slot, as for

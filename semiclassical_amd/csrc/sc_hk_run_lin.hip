@@ -6,12 +6,14 @@
 // kernel is bound by reading and writing the 4 D^2 monodromy doubles of every trajectory (9.6 KB at D = 12) each step.
 // Here a trajectory is loaded ONCE into the registers of its 16-lane row -- lane a holds row a of the four monodromy blocks
 // (96 registers at D = 12), q_a, p_a -- runs all nsteps steps there and is written back once; per step only five partial
-// sums per wavefront leave the chip (the scheme of sc_hk_run_sep16.hip).
+// sums per wavefront leave the chip (the scheme of sc_hk_run_sep16.hip).  This file holds the
+// kernel and its launcher; the entry points, the checks and the reductions are in sc_hk_run.hip.
 //
 // Per step and trajectory, in the order of the caller loop, with the arithmetic (and operation order) of the step-at-a-time
 // kernels, so that both paths agree to rounding:
 //   terms of C_auto, k_ic from the CURRENT state    hk_correlate_rows16_kernel: y = A dq, B dp, C dp as fused broadcast
-//                                                   multiply-adds, sums over the modes, scalar tail   (propagators.py:784-911)
+//                                                   multiply-adds, sums over the modes (sum_rows, sc_row16.h), then the scalar
+//                                                   tail every route calls (sc_common.h: overlap_value ... corr_k_term)   (:784-911)
 //   RK4 stages of (q, p), action, <T+V> at k4       hk_step_lin_kernel                                 (:86-119, 313-383)
 //   [X; Y] <- Phi(dt) [X; Y]                        one product with the step matrix (sc_potential.lin_prop), half by half
 //   prefactor matrix, determinant, branch tracker   real sandwiches L (M R) (sc_hk_consts.real_lr), fixed pivot order; a weak
@@ -161,23 +163,13 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
                 };
                 times_row(ya, dq, cA); times_row(yb, dpp, cB); times_row(yc, dpp, cC);
                 const double nq0 = cv[112 + r], np0 = cv[128 + r], nrn = cv[144 + r], ngn = cv[160 + r];
-                double t[6] = {dq * ya, dpp * yb, pk * dq, dq * yc, (nq0 - q) * nrn, (p - np0) * ngn}, s[6] = {0, 0, 0, 0, 0, 0};
-                dpp_guard(t);
-                sfor<0, D>([&](auto kc) {
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) fmac_bc<decltype(kc)::value>(s[i], t[i], one);
-                });
-                const cplx ex = c_make(-0.5 * s[0] - 0.5 / (SC_HBAR * SC_HBAR) * s[1], (-s[2] + s[3]) / SC_HBAR);
-                const cplx vt = c_scale(c_exp(ex), R.oc.fac);
-                const cplx c = c_scale(c_sqrt(c2), sgn);
-                const cplx ph = c_exp(c_make(0.0, S / SC_HBAR));
-                cplx cq = c_mul(c_mul(c_conj(vt), vi), c_mul(c, ph));
-                cq = c_scale(cq, wgt);
+                double s[6] = {dq * ya, dpp * yb, pk * dq, dq * yc, (nq0 - q) * nrn, (p - np0) * ngn};
+                sum_rows<D>(s, one);
+                const cplx cvt = overlap_value_conj(R.oc.fac, s[0], s[1], s[2], s[3]);
+                const cplx cq = corr_c_term(cvt, vi, signed_root(c2, sgn), action_phase(S), wgt);
                 v5[0] = cq.x; v5[1] = cq.y; v5[2] = 0.0; v5[3] = 0.0;
                 if (nac) {
-                    const cplx nacQ = c_make(R.nc.n2 + s[4], -(R.nc.p0n1 + s[5]) / SC_HBAR);
-                    cplx kq = c_mul(c_mul(nacQ, nacq), cq);
-                    kq = c_scale(kq, 1.0 / (SC_HBAR * SC_HBAR));
+                    const cplx kq = corr_k_term(R.nc.n2, R.nc.p0n1, s[4], s[5], nacq, cq);
                     v5[2] = kq.x; v5[3] = kq.y;
                 }
             }
@@ -206,18 +198,13 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
                     qn += w * kq; pn += w * kp;
                     kqs = kq; kps = kp;
                 });
-                double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-                dpp_guard(red5);
-                sfor<0, D>([&](auto kc) {
+                sum_rows<D>(red5, one);
 #pragma unroll
-                    for (int i = 0; i < 5; ++i) fmac_bc<decltype(kc)::value>(s5[i], red5[i], one);
-                });
-#pragma unroll
-                for (int s = 0; s < 4; ++s) s5[s] -= A.pot.scalar0;
-                s5[4] += A.pot.scalar0;
+                for (int s = 0; s < 4; ++s) red5[s] -= A.pot.scalar0;
+                red5[4] += A.pot.scalar0;
                 if (r < D) { q = q + h6 * qn; p = p + h6 * pn; }
-                S = S + h6 * (s5[0] + 2.0 * s5[1] + 2.0 * s5[2] + s5[3]);
-                v5[4] = s5[4];
+                S = S + h6 * (red5[0] + 2.0 * red5[1] + 2.0 * red5[2] + red5[3]);
+                v5[4] = red5[4];
             }
             // ---- [X; Y] <- Phi [X; Y], one half (Mqq, Mpq | Mqp, Mpp) at a time: row g of the old blocks comes from lane g
             //      inside the multiply-add, Phi[r][g] from LDS ----
@@ -314,6 +301,7 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
             c2 = det;
             // ---- this wavefront's share of step k: one writer per slot ----
             if constexpr (MOM) run_moments_share<MOM>(R, v5, head, k, slot, lane);
+            // (the hand-over is written out in both whole-loop kernels: as a shared function it moves hk_run_lin_kernel's registers)
 #pragma unroll
             for (int i = 0; i < 5; ++i) v5[i] = wave_sum(head ? v5[i] : 0.0);
             if (lane == 0) {

@@ -7,11 +7,14 @@
 // the four monodromy blocks), runs all nsteps steps there and is written back once; between steps nothing touches HBM
 // but the five partial sums of the step.  Trajectories are independent, so there is no grid-wide synchronisation: every
 // wavefront adds its four trajectories' terms of step k into its own slot partials[k][slot] (one writer per slot: the
-// sums are deterministic), and hk_run_reduce_kernel adds the slots of a step in a fixed order afterwards.
+// sums are deterministic), and hk_run_reduce_kernel (sc_hk_run.hip) adds the slots of a step in a fixed order afterwards.  This file holds the kernel and its launcher; the entry points, the checks and the reductions that serve both
+// whole-loop kernels are in sc_hk_run.hip.
 //
 // Per step and trajectory, in this order (= the order of the caller loop):
-//   terms of C_auto and k_ic from the CURRENT state       hk_correlate_kernel's arithmetic, sums over the modes by the same
-//                                                         rotate-and-add tree (propagators.py:784-843, 845-911)
+//   terms of C_auto and k_ic from the CURRENT state       overlap_sums_diag, nac_sums, overlap_value_conj, signed_root, action_phase,
+//                                                         corr_c_term, corr_k_term (sc_common.h: the functions
+//                                                         hk_correlate_kernel calls), sums over the modes by a rotate-and-add
+//                                                         tree (propagators.py:784-843, 845-911)
 //   RK4 of (q_a, p_a), action, <T+V> at the k4 stage,     sep_mode_rk4, sep_row_propagator, sep_propagate_row (sc_common.h: the
 //   row propagators P_a applied to the monodromy rows     functions hk_step_sep16_kernel calls; propagators.py:86-119, 313-383)
 //   prefactor row, determinant, branch tracker            prefactor_element_diag, crossed_branch_cut (sc_common.h);
@@ -74,21 +77,15 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
             // ---- terms of the correlation functions from the current state (hk_correlate_kernel, diagonal widths) ----
             double v5[5];
             {
-                const double dq = qk - q, dpp = pk - p;
-                const double sA = row_sum(dq * ocA * dq), sB = row_sum(dpp * ocB * dpp), sP = row_sum(pk * dq), sC = row_sum(dq * ocC * dpp);
-                double sR = 0.0, sG = 0.0;
-                if (nac) { sR = row_sum((nq0 - q) * nrn); sG = row_sum((p - np0) * ngn); }
-                const cplx ex = c_make(-0.5 * sA - 0.5 / (SC_HBAR * SC_HBAR) * sB, (-sP + sC) / SC_HBAR);
-                const cplx vt = c_scale(c_exp(ex), R.oc.fac);
-                const cplx c = c_scale(c_sqrt(c2), sgn);
-                const cplx ph = c_exp(c_make(0.0, S / SC_HBAR));
-                cplx cq = c_mul(c_mul(c_conj(vt), vi), c_mul(c, ph));
-                cq = c_scale(cq, wgt);
+                auto sum = [](double v) { return row_sum(v); };
+                double sA, sB, sP, sC, sR = 0.0, sG = 0.0;
+                overlap_sums_diag(qk, pk, ocA, ocB, ocC, q, p, sum, sA, sB, sP, sC);
+                if (nac) nac_sums(nq0, np0, nrn, ngn, q, p, sum, sR, sG);
+                const cplx cvt = overlap_value_conj(R.oc.fac, sA, sB, sP, sC);
+                const cplx cq = corr_c_term(cvt, vi, signed_root(c2, sgn), action_phase(S), wgt);
                 v5[0] = cq.x; v5[1] = cq.y; v5[2] = 0.0; v5[3] = 0.0;
                 if (nac) {
-                    const cplx nacQ = c_make(R.nc.n2 + sR, -(R.nc.p0n1 + sG) / SC_HBAR);
-                    cplx kq = c_mul(c_mul(nacQ, nacq), cq);
-                    kq = c_scale(kq, 1.0 / (SC_HBAR * SC_HBAR));
+                    const cplx kq = corr_k_term(R.nc.n2, R.nc.p0n1, sR, sG, nacq, cq);
                     v5[2] = kq.x; v5[3] = kq.y;
                 }
             }
@@ -102,6 +99,7 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
             {
                 double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
                 dpp_guard(red5);
+                // sum_rows (sc_row16.h) written out: with the call hipcc spills 2 to 6 VGPRs more at DP = 12
                 sfor<0, DP>([&](auto kc) {            // sums over the lanes k < DP (lanes beyond D hold zeros): as hk_step_sep16_kernel
 #pragma unroll
                     for (int i = 0; i < 5; ++i) fmac_bc<decltype(kc)::value>(s5[i], red5[i], one);
@@ -136,6 +134,7 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
             c2 = det;
             // ---- this wavefront's share of step k: one writer per slot ----
             if constexpr (MOM) run_moments_share<MOM>(R, v5, head, k, slot, lane);
+            // (the hand-over is written out in both whole-loop kernels: as a shared function it moves hk_run_lin_kernel's registers)
 #pragma unroll
             for (int i = 0; i < 5; ++i) v5[i] = sum_row_heads(v5[i], head);
             if (lane == 0) {
@@ -164,212 +163,29 @@ __global__ __launch_bounds__(256, SC_RUN_OCC) void hk_run_sep16_kernel(RunArgs R
     }
 }
 
-#ifndef SC_RUN_MOMENTS_TU
-// slots of one step added in a fixed order -> out[k][0..3], mean <T+V> of the step -> out[k][4]
-__global__ __launch_bounds__(256) void hk_run_reduce_kernel(const double *partials, int slots, double n_traj, double *out) {
-    __shared__ double red[32];
-    const int k = blockIdx.x;
-    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < slots; i += 256) {
-        const double *pp = partials + ((size_t)k * slots + i) * 5;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) v[j] += pp[j];
-    }
-    block_sum<5>(v, red);
-    if (threadIdx.x < 5) out[(size_t)k * 5 + threadIdx.x] = threadIdx.x < 4 ? v[threadIdx.x] : v[4] / n_traj;
-}
-
-// moment slots of one step added in a fixed order -> out[k][0..5]
-__global__ __launch_bounds__(256) void hk_run_reduce_moments_kernel(const double *mpart, int slots, double *out) {
-    __shared__ double red[24];
-    const int k = blockIdx.x;
-    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < slots; i += 256) {
-        const double *pp = mpart + ((size_t)k * slots + i) * 6;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) v[j] += pp[j];
-    }
-    block_sum<6>(v, red);
-    if (threadIdx.x < 6) out[(size_t)k * 6 + threadIdx.x] = v[threadIdx.x];
-}
-
-// the energy guard over the steps of a fused run, in order (propagators.py:385-398; sc_energy_guard step by step)
-__global__ void hk_run_guard_kernel(const double *out, int nsteps, double *elog) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double prev = elog[1], worst = elog[2], count = elog[3], last = elog[0];
-    for (int k = 0; k < nsteps; ++k) {
-        const double mean = out[(size_t)k * 5 + 4];
-        last = prev;
-        if (count >= 1.0) { const double change = fabs(mean - prev); if (change > worst) worst = change; }
-        prev = mean; count += 1.0;
-    }
-    elog[0] = last; elog[1] = prev; elog[2] = worst; elog[3] = count;
-}
-
-#endif  // SC_RUN_MOMENTS_TU
 
 }  // namespace
 
-#ifdef SC_RUN_MOMENTS_TU
 // this file is compiled twice: on its own with the kernels of sc_hk_run (MOM = false), and included by sc_hk_run_sep16_m.hip with
 // SC_RUN_MOMENTS_TU defined for those of sc_hk_run_m (MOM = true) -- a translation unit of their own, so that the instantiations
 // without moments are compiled exactly as before
-int sc_launch_run_sep16_m(const RunArgs &a, int grid, hipStream_t s, int kind, int D) {
-#define SC_RUN_K(DP_, KIND_) hipLaunchKernelGGL((hk_run_sep16_kernel<DP_, KIND_, true>), dim3(grid), dim3(256), 0, s, a)
-#define SC_RUN(DP_)                                                                     \
-    do {                                                                                \
-        if (kind == SC_POT_MORSE) SC_RUN_K(DP_, SC_POT_MORSE);                          \
-        else if (kind == SC_POT_HARMONIC_SEP) SC_RUN_K(DP_, SC_POT_HARMONIC_SEP);       \
-        else SC_RUN_K(DP_, SC_POT_EPS_MORSE);                                           \
-    } while (0)
-    if (D <= 4) SC_RUN(4);
-    else if (D <= 8) SC_RUN(8);
-    else SC_RUN(12);
-#undef SC_RUN
-#undef SC_RUN_K
-    return sc_check_launch("sc_hk_run_m (fused steps)");
-}
+#ifdef SC_RUN_MOMENTS_TU
+#define SC_RUNSEP_MOM true
+#define SC_RUNSEP_ENTRY sc_launch_run_sep16_m
 #else
-
-extern "C" int sc_hk_run_slots(int64_t n, int32_t dim) {
-    (void)dim;
-    const int64_t groups = (n + 15) / 16;
-    return 4 * (int)(groups < 1024 ? (groups > 0 ? groups : 1) : 1024);
+#define SC_RUNSEP_MOM false
+#define SC_RUNSEP_ENTRY sc_launch_run_sep16_plain
+#endif
+int SC_RUNSEP_ENTRY(const RunArgs &a, int grid, hipStream_t s) {
+    sc_sep16_dispatch(a.step.pot.kind, a.step.st.dim, [&](auto dp, auto kind) {
+        hipLaunchKernelGGL((hk_run_sep16_kernel<decltype(dp)::value, decltype(kind)::value, SC_RUNSEP_MOM>), dim3(grid), dim3(256), 0, s, a);
+    });
+    const int rc = sc_check_launch(SC_RUNSEP_MOM ? "sc_hk_run_m (fused steps)" : "sc_hk_run (fused steps)");
+    return rc == SC_OK ? 1 : rc;
 }
 
-// constant dense Hessian with its step matrix, D <= 16 at the shapes sc_hk_run_lin.hip instantiates (real L, R)
-static bool run_lin_shape(const sc_potential *pot, const sc_hk_consts *hk, bool modal = false) {
-    if (pot->kind != SC_POT_HARMONIC_DENSE || (!modal && !pot->lin_prop) || pot->dim > 16 || hk->dim != pot->dim) return false;
-    static const double some = 0.0;
-    RunArgs probe{};
-    probe.step.st.dim = pot->dim;
-    probe.step.hk = *hk;
-    probe.mode_prop = modal ? &some : nullptr;
-    return sc_launch_run_lin(probe, 0, nullptr, 0) == 1;
+#ifndef SC_RUN_MOMENTS_TU
+int sc_launch_run_sep16(const RunArgs &a, int grid, hipStream_t s, bool moments) {
+    return moments ? sc_launch_run_sep16_m(a, grid, s) : sc_launch_run_sep16_plain(a, grid, s);
 }
-
-extern "C" int sc_hk_run_supported(const sc_potential *pot, const sc_hk_consts *hk, const sc_overlap_consts *ovl) {
-    if (!pot || !hk || !ovl) return 0;
-    const bool sep = sc_pot_is_separable(pot->kind);
-    if (sep && hk->diag && ovl->diag && pot->dim <= SC_SEP16_MAX_D) return 1;
-    return run_lin_shape(pot, hk) ? 1 : 0;
-}
-
-static int run_whole_loop(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
-                          const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                          double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
-                          double *moments_out, void *stream);
-
-extern "C" int64_t sc_hk_run_scratch_doubles(int64_t n, int32_t dim, int32_t nsteps, int32_t moments) {
-    if (nsteps <= 0) return 0;
-    return (int64_t)(moments ? 11 : 5) * sc_hk_run_slots(n, dim) * (int64_t)nsteps;
-}
-
-extern "C" int sc_hk_run(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
-                         const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                         double dt, int32_t nsteps, double *partials, double *slots_out, double *elog, void *stream) {
-    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, nullptr, partials, slots_out, elog, nullptr,
-                          stream);
-}
-
-extern "C" int sc_hk_run_m(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
-                           const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                           double dt, int32_t nsteps, double *partials, double *slots_out, double *elog, double *moments_out,
-                           void *stream) {
-    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, nullptr, partials, slots_out, elog,
-                          moments_out, stream);
-}
-
-extern "C" int sc_hk_run_modal_supported(const sc_potential *pot, const sc_hk_consts *hk, const sc_overlap_consts *ovl) {
-    if (!pot || !hk || !ovl) return 0;
-    return run_lin_shape(pot, hk, true) ? 1 : 0;
-}
-
-extern "C" int sc_hk_run_modal(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
-                               const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                               double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
-                               void *stream) {
-    return sc_hk_run_modal_m(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, mode_prop, partials, slots_out, elog,
-                             nullptr, stream);
-}
-
-extern "C" int sc_hk_run_modal_m(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
-                                 const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                                 double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
-                                 double *moments_out, void *stream) {
-    if (!mode_prop) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run_modal: null mode_prop");
-    if (!pot || !hk || !ovl_t0 || !sc_hk_run_modal_supported(pot, hk, ovl_t0))
-        return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_run_modal: needs a constant dense Hessian and dense real prefactor constants at an "
-                       "instantiated shape D <= 16 (use sc_hk_run)");
-    return run_whole_loop(pot, st, hk, ovl_t0, nc, vi, probi, nacq, mc_norm, dt, nsteps, mode_prop, partials, slots_out, elog,
-                          moments_out, stream);
-}
-
-static int run_whole_loop(const sc_potential *pot, const sc_state *st, const sc_hk_consts *hk, const sc_overlap_consts *ovl_t0,
-                          const sc_nac_consts *nc, const double *vi, const double *probi, const double *nacq, double mc_norm,
-                          double dt, int32_t nsteps, const double *mode_prop, double *partials, double *slots_out, double *elog,
-                          double *moments_out, void *stream) {
-    if (!pot || !st || !hk || !ovl_t0 || !vi || !probi || !partials || !slots_out || !elog)
-        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run: null argument");
-    if (nc && !nacq) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run: nac constants without nacq");
-    if (!mode_prop && !sc_hk_run_supported(pot, hk, ovl_t0))
-        return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_run: needs a separable potential with diagonal width matrices and D <= %d, or a "
-                       "constant dense Hessian with its step matrix (sc_potential.lin_prop) at an instantiated shape D <= 16 "
-                       "(use the step-by-step entry points)", SC_SEP16_MAX_D);
-    const bool lin = pot->kind == SC_POT_HARMONIC_DENSE;
-    if (lin && !mode_prop && pot->lin_dt != dt)
-        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run: the step matrix was built for dt = %g, the call asks for %g", pot->lin_dt, dt);
-    if (pot->dim != st->dim || hk->dim != st->dim || ovl_t0->dim != st->dim)
-        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_run: dimension mismatch");
-    if (int rq = sc_require_rowmajor(st, "sc_hk_run")) return rq;
-    if (st->n <= 0 || nsteps <= 0) return SC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    RunArgs a;
-    a.step = StepArgs{*pot, *st, *hk, dt, 0, nullptr, 0};
-    a.oc = *ovl_t0; a.has_nac = nc != nullptr;
-    if (nc) a.nc = *nc; else a.nc = sc_nac_consts{};
-    a.vi = vi; a.probi = probi; a.nacq = nacq; a.mc_norm = mc_norm; a.nsteps = nsteps; a.partials = partials;
-    a.slots = sc_hk_run_slots(st->n, st->dim);
-    a.mode_prop = mode_prop;
-    const bool mom = moments_out != nullptr;
-    if (hipMemsetAsync(partials, 0, sizeof(double) * (size_t)sc_hk_run_scratch_doubles(st->n, st->dim, nsteps, mom), s) != hipSuccess)
-        return sc_check_launch("sc_hk_run (partials)");
-    const int grid = a.slots / 4, D = st->dim;
-    if (lin) {
-        int rc = sc_launch_run_lin(a, grid, s, 1, mom);
-        if (rc < 0) return rc;
-        if (rc == 0) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_run: shape D=%d d'=%d not instantiated", D, hk->dprime);
-        hipLaunchKernelGGL(hk_run_reduce_kernel, dim3(nsteps), dim3(256), 0, s, partials, a.slots, (double)st->n, slots_out);
-        if (mom)
-            hipLaunchKernelGGL(hk_run_reduce_moments_kernel, dim3(nsteps), dim3(256), 0, s, partials + (size_t)5 * a.slots * nsteps,
-                               a.slots, moments_out);
-        hipLaunchKernelGGL(hk_run_guard_kernel, dim3(1), dim3(64), 0, s, slots_out, nsteps, elog);
-        return sc_check_launch("sc_hk_run (reduction)");
-    }
-#define SC_RUN_K(DP_, KIND_) hipLaunchKernelGGL((hk_run_sep16_kernel<DP_, KIND_, false>), dim3(grid), dim3(256), 0, s, a)
-#define SC_RUN(DP_)                                                                     \
-    do {                                                                                \
-        if (pot->kind == SC_POT_MORSE) SC_RUN_K(DP_, SC_POT_MORSE);                     \
-        else if (pot->kind == SC_POT_HARMONIC_SEP) SC_RUN_K(DP_, SC_POT_HARMONIC_SEP);  \
-        else SC_RUN_K(DP_, SC_POT_EPS_MORSE);                                           \
-    } while (0)
-    int rc;
-    if (mom) {
-        rc = sc_launch_run_sep16_m(a, grid, s, pot->kind, D);
-    } else {
-        if (D <= 4) SC_RUN(4);
-        else if (D <= 8) SC_RUN(8);
-        else SC_RUN(12);
-        rc = sc_check_launch("sc_hk_run (fused steps)");
-    }
-#undef SC_RUN
-#undef SC_RUN_K
-    if (rc) return rc;
-    hipLaunchKernelGGL(hk_run_reduce_kernel, dim3(nsteps), dim3(256), 0, s, partials, a.slots, (double)st->n, slots_out);
-    if (mom)
-        hipLaunchKernelGGL(hk_run_reduce_moments_kernel, dim3(nsteps), dim3(256), 0, s, partials + (size_t)5 * a.slots * nsteps,
-                           a.slots, moments_out);
-    hipLaunchKernelGGL(hk_run_guard_kernel, dim3(1), dim3(64), 0, s, slots_out, nsteps, elog);
-    return sc_check_launch("sc_hk_run (reduction)");
-}
-#endif  // SC_RUN_MOMENTS_TU
+#endif

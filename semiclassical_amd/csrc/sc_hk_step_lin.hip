@@ -311,16 +311,7 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
             {
                 double one = 1.0;
                 asm volatile("" : "+v"(one));
-                double s5[5];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) s5[i] = 0.0;
-                dpp_guard(red5);
-                sfor<0, D>([&](auto kc) {             // sums over the lanes k < D: fused broadcast multiply-adds with 1.0
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) fmac_bc<decltype(kc)::value>(s5[i], red5[i], one);
-                });
-#pragma unroll
-                for (int i = 0; i < 5; ++i) red5[i] = s5[i];
+                sum_rows<D>(red5, one);               // over the lanes k < D: fused broadcast multiply-adds with 1.0
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s) red5[s] -= A.pot.scalar0;

@@ -81,6 +81,7 @@ __global__ __launch_bounds__(256, 2) void hk_step_sep16_kernel(StepArgs A) {
                 double one = 1.0, s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
                 asm volatile("" : "+v"(one));
                 dpp_guard(red5);
+                // sum_rows (sc_row16.h) written out: with the call hk_step_sep16_kernel<12, true, HARMONIC_SEP> gets other registers
                 sfor<0, DP>([&](auto kc) {            // sums over the lanes k < DP (lanes beyond D hold zeros)
 #pragma unroll
                     for (int i = 0; i < 5; ++i) fmac_bc<decltype(kc)::value>(s5[i], red5[i], one);
@@ -152,22 +153,11 @@ int sc_launch_step_sep16(const StepArgs &a, int grid_entries, hipStream_t s) {
     const bool step = (a.mode & 0xff) == 0;
     if (grid_entries != (int)(a.st.n < 4096 ? a.st.n : 4096))
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_step: %d energy partials, the kernel zeroes min(n, 4096)", grid_entries);
-#define SC_SEP16_K(DP_, KIND_)                                                                                      \
-    do {                                                                                                            \
-        if (step) hipLaunchKernelGGL((hk_step_sep16_kernel<DP_, true, KIND_>), dim3(wg), dim3(256), 0, s, a);       \
-        else hipLaunchKernelGGL((hk_step_sep16_kernel<DP_, false, SC_POT_HARMONIC_SEP>), dim3(wg), dim3(256), 0, s, a); \
-    } while (0)
-#define SC_SEP16(DP_)                                                                                               \
-    do {                                                                                                            \
-        if (a.pot.kind == SC_POT_MORSE) SC_SEP16_K(DP_, SC_POT_MORSE);                                              \
-        else if (a.pot.kind == SC_POT_HARMONIC_SEP) SC_SEP16_K(DP_, SC_POT_HARMONIC_SEP);                           \
-        else SC_SEP16_K(DP_, SC_POT_EPS_MORSE);                                                                     \
-    } while (0)
-    if (D <= 4) SC_SEP16(4);
-    else if (D <= 8) SC_SEP16(8);
-    else SC_SEP16(12);
-#undef SC_SEP16_K
-#undef SC_SEP16
+    sc_sep16_dispatch(a.pot.kind, D, [&](auto dp, auto kind) {
+        constexpr int DP = decltype(dp)::value, KIND = decltype(kind)::value;
+        if (step) hipLaunchKernelGGL((hk_step_sep16_kernel<DP, true, KIND>), dim3(wg), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((hk_step_sep16_kernel<DP, false, SC_POT_HARMONIC_SEP>), dim3(wg), dim3(256), 0, s, a);
+    });
     const int rc = sc_check_launch("sc_hk_step (four trajectories per wavefront)");
     return rc == SC_OK ? 1 : rc;
 }

@@ -4,8 +4,6 @@
 #pragma once
 #include "sc_common.h"
 
-#include <type_traits>
-
 namespace {
 
 typedef const __attribute__((address_space(4))) double *kptr;   // uniform read-only data: scalar loads
@@ -79,6 +77,33 @@ template <int K>
 __device__ __forceinline__ void fnmac_bc(double &acc, const double &b, const double &a) {     // acc -= b[K] * a
     asm volatile("v_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(b), "v"(a), "n"(K));
 }
+// sum over the lanes k < N of the 16-lane row of every element of t (result in all lanes): t_m <- sum_k t_m[k], as broadcast
+// multiply-adds with `one` (1.0 in a register the compiler cannot fold).  `n` < N stops at a run-time number of lanes.
+template <int N, int M>
+__device__ __forceinline__ void sum_rows(double (&t)[M], const double &one, int n = N) {
+    double s[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) s[m] = 0.0;
+    dpp_guard(t);
+    sfor<0, N>([&](auto kc) {
+        if (decltype(kc)::value < n) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) fmac_bc<decltype(kc)::value>(s[m], t[m], one);
+        }
+    });
+#pragma unroll
+    for (int m = 0; m < M; ++m) t[m] = s[m];
+}
+template <int N, int M>
+__device__ __forceinline__ void sum_rows(cplx (&t)[M], const double &one) {
+    double s[2 * M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) { s[2 * m] = t[m].x; s[2 * m + 1] = t[m].y; }
+    sum_rows<N>(s, one);
+#pragma unroll
+    for (int m = 0; m < M; ++m) t[m] = c_make(s[2 * m], s[2 * m + 1]);
+}
+
 // c += w * x[K] and c -= w * x[K] (complex; x is taken from lane K, w is this lane's).  c and x must be DIFFERENT
 // registers (an in-place update would read x as DPP operand right behind its own write: cfnma_inplace below).
 template <int K>

@@ -61,31 +61,6 @@ struct WmSmallLayout {
 #define SC_WM_FORCE_WEAK 0     // 1: variant library that flags EVERY trajectory (tests of the pivoted fallback)
 #endif
 
-// sum over the lanes k < N of the 16-lane row of every element of t (result in all lanes): t_m <- sum_k t_m[k]
-template <int N, int M>
-__device__ __forceinline__ void sum_rows(double (&t)[M], const double &one) {
-    double s[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) s[m] = 0.0;
-    dpp_guard(t);
-    sfor<0, N>([&](auto kc) {
-#pragma unroll
-        for (int m = 0; m < M; ++m) fmac_bc<decltype(kc)::value>(s[m], t[m], one);
-    });
-#pragma unroll
-    for (int m = 0; m < M; ++m) t[m] = s[m];
-}
-template <int N, int M>
-__device__ __forceinline__ void sum_rows(cplx (&t)[M], const double &one) {
-    double s[2 * M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) { s[2 * m] = t[m].x; s[2 * m + 1] = t[m].y; }
-    sum_rows<N>(s, one);
-#pragma unroll
-    for (int m = 0; m < M; ++m) t[m] = c_make(s[2 * m], s[2 * m + 1]);
-}
-
-
 template <int D, int DP>
 __global__ __launch_bounds__(256, SC_WM_SMALL_OCC) void wm_small_kernel(WmArgs A) {
     typedef WmSmallLayout<D, DP> L;

@@ -240,6 +240,23 @@ def test_step_physics_is_defined_once_in_the_source():
         assert holders == ["sc_common.h"], (needle, holders)
 
 
+def test_correlation_terms_are_defined_once_in_the_source():
+    """the term of C_auto (conj(vt) vi f w), the trajectory factor f (signed root times action phase) and nacQ of the term of
+    k_ic are written out in csrc/sc_common.h alone: every HK route calls corr_c_term / trajectory_factor / corr_k_term.
+    nac_initial_kernel (sc_hk_correlate.hip) keeps nacq with its own sign convention: the second holder of `p0n1 +`.  The WM
+    kernels form a different nacQ from other constants and contain none of the needles."""
+    import glob
+    csrc = os.path.join(ROOT, "semiclassical_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) > 20
+    expected = {"c_conj(vt": ["sc_common.h"], "c_sqrt(c2": ["sc_common.h"], "p0n1 +": ["sc_common.h", "sc_hk_correlate.hip"]}
+    for needle, want in expected.items():
+        holders = [os.path.basename(f) for f in files if needle in open(f).read()]
+        assert holders == want, (needle, holders)
+    corr = open(os.path.join(csrc, "sc_hk_correlate.hip")).read()
+    assert corr.count("p0n1 +") == 1 and "nac_initial_kernel" in corr.split("p0n1 +")[0].rsplit("__global__", 1)[1]
+
+
 def test_normal_mode_step_matrices_reproduce_the_full_step_matrix():
     """MolecularHarmonicPotential._normal_modes (sc_hk_run_modal): T blockdiag-by-mode(phi) T^-1 with T = diag(A, B) is the RK4 step
     matrix Phi(dt) of _step_matrix, including zero-frequency modes (free motion) and a wide mass ratio"""
