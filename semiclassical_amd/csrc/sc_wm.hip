@@ -30,15 +30,30 @@ namespace {
 
 // Gauss-Jordan inversion of the n x n complex matrix in the left half of aug (n x 2n, row-major); the right half must
 // hold the identity on entry and holds the inverse on exit.  Returns det(left) to every thread.  colbuf: n complex.
+// WIDE = false: n <= 64 and 2n <= blockDim.x rounded to a power of two -- one pivot candidate per lane, one column per thread;
+// WIDE = true: any n -- the search walks down the whole column, and with more columns than threads every thread strides over them.
+template <bool WIDE>
 __device__ __forceinline__ cplx lds_gauss_jordan(cplx *aug, int n, cplx *colbuf, int *ipiv) {
     const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, w2 = 2 * n;
     cplx det = c_make(1.0, 0.0);
     for (int k = 0; k < n; ++k) {
         if (tid < 64) {
-            // one candidate row per lane (n <= 64): |a_ik|^2 of row i = k + lane
-            const int i = k + lane;
+            // candidate rows k + lane, k + lane + 64, ... up to n - 1, i.e. the whole column below the diagonal: the largest
+            // one per lane (strictly larger, so a lane's lower row wins a tie), then a DPP maximum over the lanes
+            int i = k + lane;
             const bool valid = i < n;
-            int bi = wave_pivot_row(valid ? c_abs2(aug[i * w2 + k]) : 0.0, i, valid);
+            double mag = valid ? c_abs2(aug[i * w2 + k]) : 0.0;
+            if (WIDE) {
+                if (i + 64 < n) {
+                    const double m2 = c_abs2(aug[(i + 64) * w2 + k]);
+                    if (m2 > mag) { mag = m2; i += 64; }
+                }
+                for (int r = k + lane + 128; r < n; r += 64) {        // n > 128 (d' >= 65) only
+                    const double m2 = c_abs2(aug[r * w2 + k]);
+                    if (m2 > mag) { mag = m2; i = r; }
+                }
+            }
+            int bi = wave_pivot_row(mag, i, valid);
             if (bi < 0) bi = k;
             if (bi != k) {
                 for (int j = lane; j < w2; j += 64) {
@@ -59,14 +74,23 @@ __device__ __forceinline__ cplx lds_gauss_jordan(cplx *aug, int n, cplx *colbuf,
         __syncthreads();
         for (int j = tid; j < w2; j += nth) aug[k * w2 + j] = c_mul(aug[k * w2 + j], inv);
         __syncthreads();
-        {   // rows strided over groups of `wp` threads (wp = w2 rounded up to a power of two): no integer division
+        {   // rows strided over groups of `wp` threads (wp = w2 rounded up to a power of two): no integer division.
+            // More columns than threads (w2 > 256, d' >= 65): every thread strides over the columns and takes all rows
             int wp = 1;
             while (wp < w2) wp <<= 1;
-            const int j = tid & (wp - 1), rstep = nth > wp ? nth / wp : 1, r0 = nth > wp ? tid / wp : 0;
-            if (j < w2 && (nth >= wp || tid < wp)) {
-                const cplx rk = aug[k * w2 + j];
-                for (int i = r0; i < n; i += rstep)
-                    if (i != k) aug[i * w2 + j] = c_fnma(colbuf[i], rk, aug[i * w2 + j]);
+            if (WIDE && wp > nth) {
+                for (int j = tid; j < w2; j += nth) {
+                    const cplx rk = aug[k * w2 + j];
+                    for (int i = 0; i < n; ++i)
+                        if (i != k) aug[i * w2 + j] = c_fnma(colbuf[i], rk, aug[i * w2 + j]);
+                }
+            } else {
+                const int j = tid & (wp - 1), rstep = nth > wp ? nth / wp : 1, r0 = nth > wp ? tid / wp : 0;
+                if (j < w2) {
+                    const cplx rk = aug[k * w2 + j];
+                    for (int i = r0; i < n; i += rstep)
+                        if (i != k) aug[i * w2 + j] = c_fnma(colbuf[i], rk, aug[i * w2 + j]);
+                }
             }
         }
         __syncthreads();
@@ -200,7 +224,9 @@ __global__ __launch_bounds__(256) void wm_kernel(WmArgs A) {
         }
         for (int e = tid; e < D * E; e += nth) BQ[e] = c_make(Tq[e], ihb * Mp[e]);
         __syncthreads();
-        const cplx detA = lds_gauss_jordan(aug, E, colbuf, &ipiv);
+        // orders beyond 64 exist on global scratch only: with this carve-up (D >= d') the 160 KB of LDS end at E = 50, so the LDS
+        // kernel holds the narrow instantiation alone, the code it always ran
+        const cplx detA = GLOBAL_SCRATCH && E > 64 ? lds_gauss_jordan<true>(aug, E, colbuf, &ipiv) : lds_gauss_jordan<false>(aug, E, colbuf, &ipiv);
         // Wm = BQ' iA' (iA' = inverse(A'/s)/s)
         for (int e = tid; e < D * E; e += nth) {
             const int a = e / E, j = e - a * E;
@@ -284,7 +310,7 @@ __global__ __launch_bounds__(256) void wm_kernel(WmArgs A) {
             hat[e] = s;
         }
         __syncthreads();
-        const cplx detM = lds_gauss_jordan(augM, dp, colbuf, &ipiv);
+        const cplx detM = GLOBAL_SCRATCH && dp > 64 ? lds_gauss_jordan<true>(augM, dp, colbuf, &ipiv) : lds_gauss_jordan<false>(augM, dp, colbuf, &ipiv);
         // rho_v = iM' hat_v,  iM' = inverse(M'/(2 pi)) / (2 pi)
         for (int e = tid; e < 5 * dp; e += nth) {
             const int v = e / dp, i = e - v * dp;

@@ -111,6 +111,41 @@ def test_more_than_64_dimensions_through_the_dense_path(D, dense_gamma):
     assert cases.rel_err(c, rc) < 1e-8 and cases.rel_err(k, rk) < 1e-8
 
 
+def test_walton_manolopoulos_beyond_64_dimensions_through_step():
+    """The route a user takes with WM on a model of more than 64 modes: step() on the dense path, then sc_wm_correlate on global
+    scratch with an augmented Filinov matrix of 4 d' = 280 columns (more than one per thread) and 2 d' = 140 rows (more than
+    one pivot candidate per lane).  The Morse model of test_more_than_64_dimensions_through_the_dense_path at D = d' = 70,
+    diagonal widths, against WMOracle: C(t), k_ic(t) and the three branch trackers."""
+    from oracle import sc_oracle as orc
+    from semiclassical_amd import potentials as P, propagators as PR
+    D, n, nt, dt, alpha = 70, 10, 3, 2.0, 200.0
+    rng = np.random.default_rng(D)
+    omega = torch.from_numpy(np.sort(rng.uniform(400, 3200, D)) / 219474.63)
+    S = torch.from_numpy(rng.uniform(0.01, 0.1, D) * rng.choice([-1, 1], D))
+    nac = torch.from_numpy(rng.normal(0, 1e-4, D))
+    chi = torch.full((D,), 0.02)
+    q0 = torch.sqrt(2 * abs(S) / omega) * torch.sign(S)
+    p0 = 0.0 * q0
+    G = torch.diag(omega)
+    E0 = float(0.5 * omega.sum())
+    ref = orc.WMOracle(G, G, alpha, alpha)
+    torch.manual_seed(2)
+    ref.initial_conditions(q0, p0, G, ntraj=n)
+    rc, rk = orc.run_loop(ref, orc.MorseOracle(omega, chi.clone(), nac), dt, nt, E0)
+    prop = PR.WaltonManolopoulosPropagator(G, G, alpha, alpha, device="cuda")
+    prop.set_initial_conditions(q0, p0, G, ref.zi, ref.probi)
+    assert prop._wm_host.dprime == D and prop._wm_scratch is not None
+    pot = P.MorsePotential(omega, chi.clone(), nac)
+    c, k = np.zeros(nt, dtype=complex), np.zeros(nt, dtype=complex)
+    for t in range(nt):
+        c[t], k[t] = prop.autocorrelation(E0), prop.ic_correlation(pot, E0)
+        prop.step(pot, dt)
+    prop.synchronize()
+    assert cases.rel_err(c, rc) < 1e-8 and cases.rel_err(k, rk) < 1e-8, (c, rc, k, rk)
+    for key, sgn in (("detA", prop._sgnA), ("detM", prop._sgnM), ("prefactorC", prop._sgn)):
+        assert np.array_equal(sgn.cpu().numpy(), ref.tracker.signs(key).real.numpy()), key
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # position-dependent derivative couplings (reference propagators.py:880-903, 1685-1714: the couplings are evaluated at
 # the initial AND the current points of every trajectory; the reference's own potentials return constants)
