@@ -555,6 +555,35 @@ int sc_hk_cross(const sc_state *st, const double *La, const double *Lb, const do
                 const double *targets, int32_t K, const double *vi, const double *probi, double mc_norm,
                 const uint8_t *kept, double *operands, double *partials, double *out, const int64_t *cursor, void *stream);
 
+/* Operator correlation functions X_a(t) = <phi_0| A_a e^(-iHt) B_a |phi_0> of the Herman-Kluk wavepacket for M pairs of LINEAR
+ * operators A_a = cA_a + mA_a.x, B_a = cB_a + mB_a.x, behind HermanKlukPropagator.operator_correlation() and
+ * run(operators=...) (not in the reference, whose ic_correlation, propagators.py:845-911, has the structure: a bra-side and a
+ * ket-side factor on every trajectory's C_auto term).  The caller folds the Gaussian matrix elements
+ *   <a|x|b> / <a|b> = (Gamma_a + Gamma_b)^+ (Gamma_a q_a + Gamma_b q_b + i (p_b - p_a) / hbar)
+ * into one affine form per operator and side (diagonal and dense widths alike, no operand pre-pass):
+ *   g_ia = ket_k[a] + ket_u[a].q_i + i ket_w[a].p_i      sc_hk_opcorr_initial, from the INITIAL points zi [n][2 D] = [q_i | p_i]:
+ *                                                        once per ensemble and set of operators, into g [n][M] complex;
+ *   f_ia = bra_k[a] + bra_u[a].Q_i + i bra_w[a].P_i      from the current (Q_i, P_i) of `st`;
+ *   x_ia = f_ia g_ia cq_i                                cq [n] complex: the per-trajectory C_auto terms sc_hk_correlate(_m)
+ *                                                        exports for the same state (the Monte-Carlo weight is inside);
+ *   out[a] = sum_i (Re x_ia, Im x_ia, (Re x_ia)^2, (Im x_ia)^2, Re x_ia Im x_ia)    -- the row of sc_hk_cross, no phase.
+ *   *_u, *_w [M][D] real, *_k [M] complex (re, im).  With S = (Gamma_0 + Gamma_t)^+ the bra side of A = c + m.x is
+ *   u = Gamma_t S m, w = S m / hbar, k = c + m.S (Gamma_0 q0 - i p0 / hbar); the ket side has S = (Gamma_i + Gamma_0)^+,
+ *   u = Gamma_i S m, w = -S m / hbar, k = c + m.S (Gamma_0 q0 + i p0 / hbar).
+ *   kept: uint8 [n] or NULL; a trajectory with kept == 0 adds zero to all five sums: its state, cq and g are not read.
+ *   partials: scratch of sc_hk_opcorr_rows(n, M) * M * 5 doubles, free again when the call's work on `stream` has run.
+ *   out [M][5]; with `cursor` (device resident) the row goes to out + 5 M *cursor, and the cursor is NOT advanced (the
+ *             reduction of the correlate launch that shares the cursor advances it: launch this one first).
+ * `st` may be a view of an intermediate state (sc_hk_step_multi, sc_hk_step_visit): only n, dim and qp are read.
+ * sc_hk_opcorr: two launches; no atomics, the order of every sum is a function of (n, M) alone: the same bits in every call.
+ * D <= 512, 1 <= M <= 65535, n <= 64 * 65535; beyond: SC_ERR_UNSUPPORTED.  A null pointer or M < 1: SC_ERR_BAD_ARGUMENT. */
+int64_t sc_hk_opcorr_rows(int64_t n, int64_t M);
+int sc_hk_opcorr_initial(const double *zi, int64_t n, int32_t D, const double *ket_u, const double *ket_w, const double *ket_k,
+                         int32_t M, double *g, void *stream);
+int sc_hk_opcorr(const sc_state *st, const double *cq, const double *bra_u, const double *bra_w, const double *bra_k,
+                 const double *g, int32_t M, const uint8_t *kept, double *partials, double *out, const int64_t *cursor,
+                 void *stream);
+
 /* Frozen-Gaussian wavefunction on a spatial grid behind HermanKlukPropagator.wavefunction() (propagators.py:252-292,
  * 688-732):  phi[k] = fac sum_n v_n exp(-1/2 |Lx_k - Lq_n|^2 + i (p_n.x_k - pq_n)),  L = Gamma_t^(1/2).
  * LqT, PT [D][n] (trajectory index fastest), pq [n], v [n] complex, Lx, X [nx][D], phi [nx] complex. */

@@ -116,9 +116,10 @@ class CorrelationStore(object):
     def __init__(self, path):
         self.path = path
 
-    def start(self, task, propagator_name, times, setup, cross_targets=None):
+    def start(self, task, propagator_name, times, setup, cross_targets=None, operators=None):
         """``cross_targets``: (q, p) of the task's "cross_correlation_targets", or None: a file that is added to has to hold
-        exactly these (ConfigurationError otherwise, before any trajectory runs)"""
+        exactly these (ConfigurationError otherwise, before any trajectory runs).  ``operators``: (bra_c, bra_m, ket_c, ket_m) of
+        the task's "operator_correlation", or None: the same rule."""
         fresh = task['results'].get('overwrite', True) is True or not os.path.exists(self.path)
         if fresh:
             nt = len(times)
@@ -135,6 +136,7 @@ class CorrelationStore(object):
         assert previous['propagator'] == propagator_name, "Data produced with different propagators cannot be added."
         if previous['trajectories'] > 0:
             self._check_cross_targets(previous, cross_targets)
+            self._check_operators(previous, operators)
 
     CROSS_KEYS = ('cross_targets_q', 'cross_targets_p', 'cross_correlation')
 
@@ -152,6 +154,23 @@ class CorrelationStore(object):
                 f"{self.path} holds cross-correlation functions with other targets than this task's "
                 "(\"cross_correlation_targets\"): they are different estimators and cannot be pooled")
 
+    OPERATOR_KEYS = ('operator_bra_c', 'operator_bra_m', 'operator_ket_c', 'operator_ket_m', 'operator_correlation')
+
+    OPERATOR_ERROR_KEYS = ('operator_correlation_second_moment', 'operator_correlation_error')
+
+    def _check_operators(self, stored, operators):
+        """the stored operator correlation functions belong to exactly the operators (bra_c, bra_m, ket_c, ket_m) of the task
+        (None: the task has none)"""
+        have = 'operator_bra_c' in stored
+        if have != (operators is not None):
+            raise ConfigurationError(
+                f"{self.path} holds {'operator correlation functions' if have else 'no operator correlation functions'}, this task "
+                f"{'has no' if have else 'has'} \"operator_correlation\": they cannot be pooled")
+        if have and not all(np.array_equal(stored[key], new) for key, new in zip(self.OPERATOR_KEYS[:4], operators)):
+            raise ConfigurationError(
+                f"{self.path} holds operator correlation functions with other operators than this task's "
+                "(\"operator_correlation\"): they are different estimators and cannot be pooled")
+
     ERROR_KEYS = ('autocorrelation_error', 'ic_correlation_error', 'autocorrelation_second_moment', 'ic_correlation_second_moment')
 
     BLOCK_KEYS = ('autocorrelation_blocks', 'ic_correlation_blocks', 'block_trajectories')
@@ -159,7 +178,8 @@ class CorrelationStore(object):
     SYMPLECTICITY_KEYS = ('symplecticity_steps', 'symplecticity_max', 'symplecticity_mean', 'symplecticity_exceeding',
                           'symplecticity_tolerance', 'symplecticity_kept', 'symplecticity_discard')
 
-    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None, cross=None):
+    def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None, cross=None,
+                  operators=None):
         """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
         per-sample second moments (rows (S_rr, S_ii, S_ri) times the batch size, phase applied) of the batch, folded the same
         way; the standard errors of the pooled means follow from them.  Files and batches that do not both carry them lose
@@ -181,12 +201,18 @@ class CorrelationStore(object):
         'correlation' (nt, K) and, with standard errors, 'second_moment' (nt, K, 3) as for the autocorrelation.  The file then holds
         ``cross_targets_q``, ``cross_targets_p``, ``cross_correlation`` (pooled with the weights of ``autocorrelation``) and, by the
         keep-or-drop rule of the second moments, ``cross_correlation_second_moment`` and ``cross_correlation_error``.  Stored
-        targets that differ from the batch's (or exist on one side only) are refused (ConfigurationError)."""
+        targets that differ from the batch's (or exist on one side only) are refused (ConfigurationError).
+        ``operators``: the record of the batch's operator correlation functions: 'bra_c', 'ket_c' (M,),
+        'bra_m', 'ket_m' (M, D), 'correlation' (nt, M) and, with standard errors, 'second_moment' (nt, M, 3).  The file then holds
+        ``operator_bra_c``, ``operator_bra_m``, ``operator_ket_c``, ``operator_ket_m``, ``operator_correlation`` and, by the same
+        keep-or-drop rule, ``operator_correlation_second_moment`` and ``operator_correlation_error``; everything as for ``cross``."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
         if done > 0:
             self._check_cross_targets(stored, None if cross is None else (cross['q'], cross['p']))
+            self._check_operators(stored, None if operators is None else
+                                  tuple(operators[key] for key in ('bra_c', 'bra_m', 'ket_c', 'ket_m')))
         discarding = symplecticity is not None and bool(symplecticity.get('discard', False))
         if done > 0:
             was_discarding = bool(stored.get('symplecticity_discard', False))
@@ -271,6 +297,26 @@ class CorrelationStore(object):
                                "this task does not compute them (\"standard_errors\": true)")
                 for key in self.CROSS_ERROR_KEYS:
                     stored.pop(key, None)
+        if operators is not None:
+            pool = done > 0
+            new = np.asarray(operators['correlation'], dtype=complex)
+            for key in ('bra_c', 'bra_m', 'ket_c', 'ket_m'):
+                stored['operator_' + key] = np.asarray(operators[key], dtype=np.float64)
+            stored['operator_correlation'] = (ntraj * new + done * stored['operator_correlation']) / total if pool else new
+            moment = operators.get('second_moment', None)
+            key = 'operator_correlation_second_moment'
+            have_moment = key in stored
+            if moment is not None and (have_moment or not pool):
+                stored[key] = (ntraj * moment + done * stored[key]) / total if pool else np.asarray(moment, dtype=np.float64)
+                stored['operator_correlation_error'] = hostmath.standard_errors(stored['operator_correlation'], stored[key] / total, total)
+            elif have_moment or moment is not None:
+                logger.warning("standard errors of the operator correlation functions dropped from %s: %s", self.path,
+                               "the stored trajectories have no second moments" if moment is not None else
+                               "this task does not compute them (\"standard_errors\": true)")
+                for key in self.OPERATOR_ERROR_KEYS:
+                    stored.pop(key, None)
+            for key in ('operator_lineshape', 'radiative_rate'):      # computed from the old correlation functions: stale now
+                stored.pop(key, None)
         stored.pop('ic_rate', None)          # a rate computed from the old correlation function is stale now
         stored.pop('ic_rate_error', None)
         logger.info(f"<phi(0)|phi(0)>= {stored['autocorrelation'][0]}")
@@ -329,7 +375,8 @@ def _check_symplecticity(propagator, step, time, tolerance, log, discard=False):
 
 
 def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False,
-                    error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None, discard_nonsymplectic=False, targets=None):
+                    error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None, discard_nonsymplectic=False, targets=None,
+                    operators=None):
     """C_auto(t), k_ic(t) of one batch of trajectories: the device loop leaves the raw per-step sums in a device buffer,
     ``flush`` (None on a single rank) adds the buffers of all ranks -- ONE all-reduce per batch, SURVEY 8e -- and the host
     applies the dynamical phase.  ``norm_every`` > 0 logs the wavefunction norm (the O(n^2) convergence diagnostic of
@@ -348,14 +395,24 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     kept before the check, and the record gains 'kept' (the number kept after every check) and 'discard' = True.
     ``targets`` = (Q, P), arrays (K, D): the cross-correlation functions with these target coherent states (propagator.run(targets=...));
     the result then ends with one more element still, the record {'q', 'p', 'correlation' (nt, K)} and, with ``errors``,
-    'second_moment' (nt, K, 3), the per-sample second moments as (M_C, M_k).  Single rank only: the flush does not carry them."""
+    'second_moment' (nt, K, 3), the per-sample second moments as (M_C, M_k).  Single rank only: the flush does not carry them.
+    ``operators`` = (bra_c, bra_m, ket_c, ket_m): the operator correlation functions (propagator.run(operators=...)); the result then
+    ends with yet another element, the record {'bra_c', 'bra_m', 'ket_c', 'ket_m', 'correlation' (nt, M)} and, with ``errors``,
+    'second_moment' (nt, M, 3).  Single rank only, for the same reason."""
+    if operators is not None and flush is not None:
+        raise ValueError("operators are not available with more than one rank: the flush buffer does not carry the operator-correlation rows")
     if targets is not None and flush is not None:
         raise ValueError("targets are not available with more than one rank: the flush buffer does not carry the cross-correlation rows")
     if discard_nonsymplectic and not (symplecticity_every > 0 and symplecticity_tolerance is not None):
         raise ValueError("discard_nonsymplectic needs symplecticity_every > 0 and a symplecticity_tolerance")
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
     moments = torch.zeros((nt, 6), dtype=torch.float64, device=propagator.device) if errors else None
-    blocks = counts = cross = None
+    blocks = counts = cross = opcorr = None
+    if operators is not None:
+        bra_c, bra_m, ket_c, ket_m = (np.asarray(a, dtype=np.float64) for a in operators)
+        if bra_c.ndim != 1 or bra_c.shape[0] == 0:
+            raise ValueError(f"operators: c of shape (M,) with M > 0 is expected, got {bra_c.shape}")
+        opcorr = torch.zeros((nt, bra_c.shape[0], 5), dtype=torch.float64, device=propagator.device)
     if targets is not None:
         Q, P = (np.asarray(a, dtype=np.float64) for a in targets)
         if Q.ndim != 2 or Q.shape[0] == 0:
@@ -380,7 +437,8 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
                        moments=None if moments is None else moments[first:first + count],
                        blocks=None if blocks is None else blocks[first:first + count],
-                       **({} if cross is None else dict(targets=(Q, P), cross=cross[first:first + count])))
+                       **({} if cross is None else dict(targets=(Q, P), cross=cross[first:first + count])),
+                       **({} if opcorr is None else dict(operators=((bra_c, bra_m), (ket_c, ket_m)), opcorr=opcorr[first:first + count])))
     if symplecticity_every > 0 and pieces:
         # The clock of a piece is t0 + (dt + dt + ...), which differs from the uncut loop's 0 + dt + dt + ... in the last bits, and
         # with it the dynamical phase.  The check must leave every bit of the correlation functions as it is: the phase is taken
@@ -413,6 +471,13 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         if errors:
             record['second_moment'] = propagator._ntraj_norm * m3
         tail = tail + (record,)
+    if opcorr is not None:
+        parts = [propagator.phased_cross(opcorr[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
+        X, m3 = (np.concatenate(part) for part in zip(*parts))
+        record = {'bra_c': bra_c, 'bra_m': bra_m, 'ket_c': ket_c, 'ket_m': ket_m, 'correlation': X}
+        if errors:
+            record['second_moment'] = propagator._ntraj_norm * m3
+        tail = tail + (record,)
     if moments is None:
         parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
                  for first, count, t0 in pieces]
@@ -437,6 +502,28 @@ def _load_targets(path, dim):
     if not (np.isfinite(q).all() and np.isfinite(p).all()):
         raise ConfigurationError(f"'cross_correlation_targets': non-finite entry in {path}")
     return q, p
+
+
+def _load_operators(path, dim):
+    """(bra_c, bra_m, ket_c, ket_m), float64 (M,) and (M, D), of an "operator_correlation" file; without ket_c and ket_m the ket's
+    operators are the bra's"""
+    try:
+        with np.load(path, allow_pickle=False) as handle:
+            bra_c, bra_m = (np.array(handle[key], dtype=np.float64) for key in ('bra_c', 'bra_m'))
+            if ('ket_c' in handle) != ('ket_m' in handle):
+                raise KeyError("ket_c and ket_m come together")
+            ket_c, ket_m = ((np.array(handle[key], dtype=np.float64) for key in ('ket_c', 'ket_m')) if 'ket_c' in handle else
+                            (bra_c.copy(), bra_m.copy()))
+    except (OSError, KeyError, ValueError) as err:
+        raise ConfigurationError(f"'operator_correlation': {path} should be an npz file with arrays bra_c and bra_m (and ket_c, "
+                                 f"ket_m) ({err})")
+    for side, c, m in (("bra", bra_c, bra_m), ("ket", ket_c, ket_m)):
+        if c.ndim != 1 or c.shape[0] == 0 or m.shape != (c.shape[0], dim) or c.shape != bra_c.shape:
+            raise ConfigurationError(f"'operator_correlation': {side}_c of shape (M,) and {side}_m of shape (M, {dim}) with M > 0 are "
+                                     f"expected in {path}, got {c.shape} and {m.shape}")
+        if not (np.isfinite(c).all() and np.isfinite(m).all()):
+            raise ConfigurationError(f"'operator_correlation': non-finite entry in {path}")
+    return bra_c, bra_m, ket_c, ket_m
 
 
 def run_semiclassical_dynamics(task, device='cuda', comm=None):
@@ -484,8 +571,18 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     if targets_file is not None and world > 1:
         raise ConfigurationError("'cross_correlation_targets' is not available with more than one rank: the flush buffer does not "
                                  "carry the cross-correlation rows")
+    # correlation functions with linear operators on both sides (a key the reference does not have): an npz file
+    # with arrays bra_c (M,), bra_m (M, D) and optionally ket_c, ket_m, atomic units, in the coordinates of q0
+    operators_file = task.get('operator_correlation', None)
+    if operators_file is not None and task.get('propagator', 'HK') == "WM":
+        raise ConfigurationError("'operator_correlation' is not available with the WM propagator: its Gaussians have "
+                                 "per-trajectory widths and another prefactor")
+    if operators_file is not None and world > 1:
+        raise ConfigurationError("'operator_correlation' is not available with more than one rank: the flush buffer does not "
+                                 "carry the operator-correlation rows")
     setup = build_problem(task)
     targets = None if targets_file is None else _load_targets(targets_file, int(setup.q0.shape[0]))
+    operators = None if operators_file is None else _load_operators(operators_file, int(setup.q0.shape[0]))
 
     dt = task['time_step_fs'] / units.autime_to_fs
     nt = task['num_steps']
@@ -502,7 +599,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
 
     store = CorrelationStore(task['results'].get('correlations', 'correlations.npz'))
     if writer:
-        store.start(task, task.get('propagator', 'HK'), times, setup, cross_targets=targets)
+        store.start(task, task.get('propagator', 'HK'), times, setup, cross_targets=targets, operators=operators)
 
     seed = task.get('manual_seed', None)
     if seed is not None:
@@ -550,7 +647,10 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         out = propagate_batch(propagator, setup, dt, nt, times, norm_every=task.get('calc_norm_every', 0), flush=flush,
                               across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks,
                               symplecticity_every=check_every, symplecticity_tolerance=tolerance, discard_nonsymplectic=discard,
-                              targets=targets)
+                              targets=targets, operators=operators)
+        oprecord = None
+        if operators is not None:
+            out, oprecord = out[:-1], out[-1]
         cross = None
         if targets is not None:
             out, cross = out[:-1], out[-1]
@@ -562,7 +662,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         assert not np.isnan(ic_correlation).any(), f"encountered NaN's in IC correlation : {ic_correlation}"
         if writer:
             store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:4] if errors else None,
-                            blocks=out[-1] if error_blocks else None, symplecticity=checks, cross=cross)
+                            blocks=out[-1] if error_blocks else None, symplecticity=checks, cross=cross, operators=oprecord)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -597,6 +697,18 @@ def calculate_rates(task):
         # Monte-Carlo standard error of the rate at every energy from the spread of the blocks' own rates (batch means)
         _, sigma = rates.rate_standard_error(stored['times'], stored['ic_correlation_blocks'], stored['block_trajectories'], lineshape)
         stored['ic_rate_error'] = (2.0 * np.pi * sigma)[keep]
+    for key in ('operator_lineshape', 'radiative_rate'):
+        stored.pop(key, None)
+    if 'operator_correlation' in stored:
+        # emission lineshapes G_a(E) of the operator correlation functions on the same energies; their sum is the lineshape of the
+        # dipole correlation function when the operators are the components of a transition dipole
+        X = stored['operator_correlation']
+        shapes = np.stack([rates.lineshape_from_correlation(stored['times'], X[:, a], lineshape)[1] for a in range(X.shape[1])], axis=1)
+        stored['operator_lineshape'] = shapes[keep].real
+        gap_ev = task.get('adiabatic_gap_ev', None)
+        if gap_ev is not None:
+            stored['radiative_rate'] = rates.radiative_rate(stored['energies'], stored['operator_lineshape'].sum(axis=1),
+                                                            gap_ev / units.hartree_to_ev)
     np.savez(task.get('rates', 'correlations.npz'), **stored)
 
 

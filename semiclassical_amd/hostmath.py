@@ -138,6 +138,28 @@ class NacConstants(object):
         self.n2 = float(-hbar ** 2 * 0.5 * tau2_sum)
 
 
+def fold_linear_operators(c, m, G_traj, G_0, q0, p0, ket):
+    """(u, w, kappa): the Gaussian matrix element of the linear operators c_a + m_a.x between phi_0 = |q0, p0, G_0> and a
+    trajectory's Gaussian |q, p, G_traj>, divided by their overlap, as one affine form  kappa_a + u_a.q + i w_a.p  per operator
+    (DESIGN.md section 4.14).  From  <a|x|b> / <a|b> = (G_a + G_b)^+ (G_a q_a + G_b q_b + i (p_b - p_a) / hbar)  with
+    S = (G_traj + G_0)^+:  u = G_traj S m,  kappa = c + m.S (G_0 q0 -+ i p0 / hbar),  w = +- S m / hbar -- the upper signs for
+    ``ket`` False (phi_0 is the bra: <phi_0|A|q, p>), the lower ones for ``ket`` True (<q, p|B|phi_0>).
+    c (M,), m (M, D) real; returns real (M, D), real (M, D), complex (M,).  Singular widths: the pseudo-inverse of
+    OverlapConstants; every m_a has to lie in the range of G_traj + G_0 (relative 1e-8, the test of reduced_density), else
+    ValueError."""
+    e, V = _eigh(G_traj + G_0)
+    keep = abs(e) > ZERO
+    S = torch.einsum('ij,j,kj->ik', V[:, keep], 1.0 / e[keep], V[:, keep])
+    outside = torch.linalg.norm(m - (m @ V[:, keep]) @ V[:, keep].T, dim=1) > 1.0e-8 * torch.linalg.norm(m, dim=1)
+    if bool(outside.any()):
+        raise ValueError(f"operators: the vector(s) m of operator(s) {torch.nonzero(outside).flatten().tolist()} lie outside the "
+                         "range of the sum of the widths: the matrix element along a null direction does not exist")
+    Sm = m @ S                                              # rows S m_a (S is symmetric)
+    sign = 1.0 if ket else -1.0
+    kappa = torch.complex(c + Sm @ (G_0 @ q0), sign / hbar * (Sm @ p0))
+    return (Sm @ G_traj).contiguous(), (-sign / hbar * Sm).contiguous(), kappa.contiguous()
+
+
 def time_grid(nt, dt):
     """t_k of the propagator: t accumulates `t += dt` (propagators.py:655), not k*dt"""
     t, out = 0.0, np.empty(nt)

@@ -77,8 +77,8 @@ def _resolve_device(device):
 
 # One step's row of run()'s output buffers as the launches take it: the addresses of its slot, of its moments, blocks = (address, B)
 # and of its cross rows, None where there is no such buffer.  slots[k] is the slot as a tensor, formed only where torch adds the k_ic
-# sum to it (position-dependent couplings).
-_Row = collections.namedtuple("_Row", "slot moments blocks cross slots k")
+# sum to it (position-dependent couplings).  opcorr: the address of its operator-correlation rows (section 4.14), or None.
+_Row = collections.namedtuple("_Row", "slot moments blocks cross slots k opcorr", defaults=(None,))
 
 
 class _StepRows(object):
@@ -89,9 +89,10 @@ class _StepRows(object):
     #   moments    MOMENT = 6             48
     #   blocks     (B, BLOCK = 4)         32 B
     #   cross      (K, CROSS = 5)         40 K
-    SLOT, MOMENT, BLOCK, CROSS = 5, 6, 4, 5
+    #   opcorr     (M, OPCORR = 5)        40 M
+    SLOT, MOMENT, BLOCK, CROSS, OPCORR = 5, 6, 4, 5, 5
 
-    def __init__(self, device, nt, slots, moments=None, blocks=None, cross=None, K=None):
+    def __init__(self, device, nt, slots, moments=None, blocks=None, cross=None, K=None, *, opcorr=None, M=None):
         device = torch.device(device)
         self._check("slots", slots, nt, (self.SLOT,), device)
         if moments is not None:
@@ -102,9 +103,12 @@ class _StepRows(object):
                 raise ValueError(f"the number of blocks has to be a power of two in 2 ... 64, got {int(blocks.shape[1])}")
         if cross is not None:
             self._check("cross", cross, nt, (K, self.CROSS), device)
+        if opcorr is not None:
+            self._check("opcorr", opcorr, nt, (M, self.OPCORR), device)
         self.slots, self.moments = slots, moments
-        self.B, self.K = (None if t is None else int(t.shape[1]) for t in (blocks, cross))
+        self.B, self.K, self.M = (None if t is None else int(t.shape[1]) for t in (blocks, cross, opcorr))
         self._base = tuple(None if t is None else t.data_ptr() for t in (slots, moments, blocks, cross))
+        self._opcorr = None if opcorr is None else opcorr.data_ptr()
 
     @staticmethod
     def _check(name, t, nt, row, device):           # row: the trailing shape ("B": any size)
@@ -118,13 +122,14 @@ class _StepRows(object):
         slot, mom, blk, cross = self._base
         return _Row(slot + 8 * self.SLOT * k, None if mom is None else mom + 8 * self.MOMENT * k,
                     None if blk is None else (blk + 8 * self.BLOCK * self.B * k, self.B),
-                    None if cross is None else cross + 8 * self.CROSS * self.K * k, self.slots, k)
+                    None if cross is None else cross + 8 * self.CROSS * self.K * k, self.slots, k,
+                    None if self._opcorr is None else self._opcorr + 8 * self.OPCORR * self.M * k)
 
     @staticmethod
-    def single(slot=None, moments=None, cross=None):
+    def single(slot=None, moments=None, cross=None, opcorr=None):
         """the row of buffers that hold one row each: scratch of the caller's own, of any shape, not validated"""
         at = lambda t: None if t is None else t.data_ptr()
-        return _Row(at(slot), at(moments), None, at(cross), None if slot is None else slot.view(1, -1), 0)
+        return _Row(at(slot), at(moments), None, at(cross), None if slot is None else slot.view(1, -1), 0, at(opcorr))
 
 
 class HermanKlukPropagator(object):
@@ -287,6 +292,7 @@ class HermanKlukPropagator(object):
         # discard mask (discard_nonsymplectic): None until the first mark -- every route then runs the launches it always ran
         self._kept, self._discarded_at, self._kept_count, self._masked_scratch = None, None, None, None
         self._cross = None            # constants and scratch of cross_correlation(): depend on Gamma_0 and n
+        self._opcorr = None           # folded operators, g and scratch of operator_correlation(): depend on (zi, Gamma_0, q0, p0) and n
 
         self._prepare()
         self.t = 0.0
@@ -653,13 +659,14 @@ class HermanKlukPropagator(object):
                                       ptr(self._masked_scratch), C_void(row.slot), None if row.moments is None else C_void(row.moments),
                                       None if out is None else C_void(out), self._stream()))
 
-    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None):
+    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None, operators=None):
         """per-trajectory terms + their sums for the current state into `row` (_StepRows): the 5-double slot; the six second-moment
         sums, formed inside the correlate kernel; the block sums -- the terms are exported and sc_term_blocks follows the correlate
         kernel.  `state`: another view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi.  Under a
         discard mask the correlate kernel only exports the terms; sc_term_masked_sums forms every sum from them.  `targets`
         (_cross_targets): the (K, 5) sums of the cross-correlation of the same state with them go to the row's cross rows,
-        sc_hk_cross after the correlate kernel."""
+        sc_hk_cross after the correlate kernel.  `operators` (_operators): the (M, 5) sums of the operator correlation functions
+        of the same state go to the row's opcorr rows, sc_hk_opcorr on the terms the correlate kernel has just exported."""
         s = self._stream()
         nac = self._nac
         mom_ptr, blk = row.moments, row.blocks
@@ -668,7 +675,7 @@ class HermanKlukPropagator(object):
         if masked and generic:
             raise NotImplementedError("position-dependent derivative couplings are not available once trajectories have been "
                                       "discarded (discard_nonsymplectic)")
-        per_trajectory = per_trajectory or generic or blk is not None or masked
+        per_trajectory = per_trajectory or generic or blk is not None or masked or operators is not None
         in_kernel = mom_ptr is not None and not generic and not masked
         with self._timed("hk_correlate"):
             check(lib.sc_hk_correlate_m(self._state if state is None else state, self._ovl_t0, nac, ptr(self._vi), ptr(self.probi),
@@ -678,6 +685,8 @@ class HermanKlukPropagator(object):
                                         ptr(self._mpart) if in_kernel else None, s))
         if targets is not None:
             self._launch_cross(targets, row.cross, state=state, cursor=cursor)
+        if operators is not None:
+            self._launch_opcorr(operators, row.opcorr, state=state, cursor=cursor)
         if masked:
             assert cursor is None
             self._masked_sums(nac is not None, row)
@@ -806,8 +815,90 @@ class HermanKlukPropagator(object):
         C, m3 = HermanKlukPropagator.phased_cross(cross, t0, dt, energy0_es)
         return C, hostmath.standard_errors(C, m3, ntraj_norm)
 
+    # ---- correlation functions with linear operators (not in the reference) ----
+    @staticmethod
+    def _is_operator_set(x):
+        """(c, m) with c one-dimensional and m two-dimensional"""
+        try:
+            return len(x) == 2 and np.ndim(x[0]) == 1 and np.ndim(x[1]) == 2
+        except (TypeError, ValueError):
+            return False
+
+    def _operator_set(self, name, ops):
+        """validated (c (M,), m (M, D)) of one side as fp64 host tensors"""
+        if not self._is_operator_set(ops):
+            raise ValueError(f"operators: {name} = (c, m) with c of shape (M,) and m of shape (M, {self.dim}) is expected")
+        try:
+            c, m = np.asarray(ops[0], dtype=np.float64), np.asarray(ops[1], dtype=np.float64)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"operators: real arrays are expected for {name} ({err})")
+        if m.shape != (c.shape[0], self.dim):
+            raise ValueError(f"operators: {name} = (c, m) with c of shape (M,) and m of shape (M, {self.dim}) is expected, got "
+                             f"{c.shape} and {m.shape}")
+        if c.shape[0] == 0:
+            raise ValueError("operators: at least one operator is expected (M = 0)")
+        if not (np.isfinite(c).all() and np.isfinite(m).all()):
+            raise ValueError(f"operators: non-finite entry in {name}")
+        return torch.from_numpy(c.copy()), torch.from_numpy(m.copy())
+
+    def _operators(self, bra, ket=None):
+        """validated operators A_a = cA_a + mA_a.x (``bra``) and B_a (``ket``; None: the bra's), their folded vectors
+        (hostmath.fold_linear_operators) and the ket-side factors g [n][M] of the initial points (sc_hk_opcorr_initial) on the device.
+        Cached per set of operators until the initial conditions change (_finish_state)."""
+        if not self._opcorr_ok:
+            raise NotImplementedError(f"{type(self).__name__} has no operator correlation functions: its Gaussians have "
+                                      "per-trajectory widths and another prefactor")
+        cA, mA = self._operator_set("bra", bra)
+        cB, mB = (cA, mA) if ket is None else self._operator_set("ket", ket)
+        if cB.shape != cA.shape:
+            raise ValueError(f"operators: bra and ket have to hold the same number of operators, got {cA.shape[0]} and {cB.shape[0]}")
+        key = tuple(t.numpy().tobytes() for t in (cA, mA, cB, mB))
+        hit = self._opcorr
+        if hit is not None and hit["key"] == key:
+            return hit
+        M, dev = int(cA.shape[0]), self.device
+        uA, wA, kA = hostmath.fold_linear_operators(cA, mA, self._Gt, self._G0h, self._q0h, self._p0h, ket=False)
+        uB, wB, kB = hostmath.fold_linear_operators(cB, mB, self._Gi, self._G0h, self._q0h, self._p0h, ket=True)
+        bufs = [t.to(dev) for t in (uA, wA, kA, uB, wB, kB)]
+        g = torch.empty((self.ntraj, M), dtype=C128, device=dev)
+        check(lib.sc_hk_opcorr_initial(ptr(self._zi_t), self.ntraj, self.dim, ptr(bufs[3]), ptr(bufs[4]), ptr(bufs[5]), M, ptr(g),
+                                       self._stream()))
+        partials = torch.empty(max(int(lib.sc_hk_opcorr_rows(self.ntraj, M)) * M * 5, 1), dtype=F64, device=dev)
+        self._opcorr = {"key": key, "M": M, "bra": (cA.numpy(), mA.numpy()), "ket": (cB.numpy(), mB.numpy()), "bufs": bufs, "g": g,
+                        "partials": partials}
+        return self._opcorr
+
+    def _launch_opcorr(self, operators, out_ptr, state=None, cursor=None):
+        """the (M, 5) operator-correlation sums of `state` (default: the current one) from the terms _cq the correlate kernel has
+        exported for it, into the doubles at `out_ptr`, or into row *cursor of the (., M, 5) buffer there (the cursor is read, not
+        advanced); honours the discard mask"""
+        b = operators["bufs"]
+        with self._timed("hk_opcorr"):
+            check(lib.sc_hk_opcorr(self._state if state is None else state, ptr(self._cq), ptr(b[0]), ptr(b[1]), ptr(b[2]),
+                                   ptr(operators["g"]), operators["M"], ptr(self._kept), ptr(operators["partials"]), C_void(out_ptr),
+                                   None if cursor is None else ptr(cursor), self._stream()))
+
+    def operator_correlation(self, bra, ket=None, energy0_es=0.0, standard_errors=False):
+        """X_a(t) = e^{i t E0/hbar} <phi_0| A_a e^{-iHt/hbar} B_a |phi_0> for the current step with M pairs of LINEAR operators
+        A_a = cA_a + mA_a.x, B_a = cB_a + mB_a.x (not in the reference): a complex ndarray (M,).
+        ``bra`` = (c, m), real arrays (M,) and (M, D) in the coordinates of q0; ``ket`` likewise, None = the operators of the bra.
+        Every trajectory's C_auto term is multiplied by the closed-form Gaussian matrix elements of A at its current and of B at its
+        initial phase-space point, the way ``ic_correlation`` treats the non-adiabatic coupling: linear in the ensemble like
+        ``autocorrelation()``, which it equals for c = 1, m = 0.  With ``standard_errors`` the result is ``(X, sigma)``, sigma =
+        sigma_Re + i sigma_Im per pair (``hostmath.standard_errors``).  Trajectories discarded by ``discard_nonsymplectic`` count as
+        samples of value zero, N unchanged.  Synchronises; the state is not touched: the steps that follow give the bits they would
+        have given without the call.  ``ValueError`` for operators of the wrong shape, with non-finite entries, M = 0, or a vector
+        m outside the range of Gamma_0 + Gamma_t (bra) or Gamma_i + Gamma_0 (ket)."""
+        operators = self._operators(bra, ket)
+        out = torch.zeros((1, operators["M"], 5), dtype=F64, device=self.device)
+        slot = torch.zeros(8, dtype=F64, device=self.device)
+        self._launch_correlate(self._rows.single(slot, opcorr=out), operators=operators)
+        self.synchronize()
+        X, sigma = self.finalize_cross(out, self.t, 0.0, energy0_es, self._ntraj_norm)
+        return (X[0], sigma[0]) if standard_errors else X[0]
+
     def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
-            targets=None, cross=None):
+            targets=None, cross=None, operators=None, opcorr=None):
         """The caller loop of cli.py:401-436 on the device: ``nt`` times (C_auto, k_ic, step), no host sync.
 
         Returns ``(autocorrelation[nt], ic_correlation[nt])`` as complex NumPy arrays.  With ``slots`` (a
@@ -853,6 +944,14 @@ class HermanKlukPropagator(object):
         for ``finalize_cross``.  With targets the loop never runs as the one-launch kernel (it exports no per-step state): on those
         shapes C and k are the step-at-a-time loop's; everywhere else C, k, moments, blocks and the final state are the same bit for
         bit with or without targets.  ``use_graph=True`` with targets raises ``ValueError``.
+
+        Operator correlation functions: ``operators`` = (bra, ket) or bra alone, each a pair (c (M,), m (M, D)) of linear operators
+        c_a + m_a.x (``operator_correlation``): a ``sc_hk_opcorr`` launch follows every correlate launch, which then exports its
+        per-trajectory terms as it does for blocks, the intermediate states of pairs and visits included.  With ``slots=None`` the
+        returned tuple gains ``X`` (nt, M) complex at its end (after the cross outputs), and ``sigma_X`` after it with
+        ``standard_errors=True``.  With ``slots`` given ``opcorr`` is required: a contiguous float64 device tensor (>= nt, M, 5) for the
+        raw rows, which ``finalize_cross`` takes as they are.  The rules of targets hold: never the one-launch kernel, everything
+        else the same bit for bit with or without operators, ``use_graph=True`` raises ``ValueError``.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
         if use_graph and self._kept is not None:
@@ -873,6 +972,23 @@ class HermanKlukPropagator(object):
             targets = self._cross_targets(q_targets, p_targets)
             if cross is None:
                 cross = torch.zeros((nt, targets["K"], 5), dtype=F64, device=self.device)
+        if operators is None and opcorr is not None:
+            raise ValueError("opcorr= receives the sums of run(operators=...): pass the operators as well")
+        if operators is not None:
+            if use_graph:
+                raise ValueError("use_graph=True is not available with operators: the graph replay has no operator-correlation launch")
+            if slots is not None and opcorr is None:
+                raise ValueError("run(slots=..., operators=...) leaves the raw sums on the device: pass opcorr=, a float64 device "
+                                 "tensor (>= nt, M, 5), to receive those of the operators")
+            if self._is_operator_set(operators):
+                operators = (operators, None)
+            try:
+                bra, ket = operators
+            except (TypeError, ValueError):
+                raise ValueError("operators: (bra, ket) or bra, each a pair (c, m) of arrays (M,) and (M, D), is expected")
+            operators = self._operators(bra, ket)
+            if opcorr is None:
+                opcorr = torch.zeros((nt, operators["M"], 5), dtype=F64, device=self.device)
         dt = float(dt)
         self._remember_nac(potential)
         own = slots is None
@@ -882,14 +998,15 @@ class HermanKlukPropagator(object):
             slots = torch.zeros((nt, 5), dtype=F64, device=self.device)
             if standard_errors and moments is None:
                 moments = torch.zeros((nt, 6), dtype=F64, device=self.device)
-        rows = self._rows(self.device, nt, slots, moments, blocks, cross, None if targets is None else targets["K"])
+        rows = self._rows(self.device, nt, slots, moments, blocks, cross, None if targets is None else targets["K"],
+                          opcorr=opcorr, M=None if operators is None else operators["M"])
         t0 = self.t
         fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model") and self.dim <= 64
                  and self._nac_generic is None)
         desc = self._potential_descriptor(potential, dt) if fused else None
-        if fused and targets is None and self._whole_loop_applies(desc):
+        if fused and targets is None and operators is None and self._whole_loop_applies(desc):
             # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run; it exports no per-step state
-            # for the targets of a cross-correlation)
+            # for the targets of a cross-correlation or for operators)
             self._run_whole_loop(desc, dt, nt, rows, potential)
         elif (use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing
               and self._modal_step_constants(potential, desc, dt) is None):
@@ -900,13 +1017,14 @@ class HermanKlukPropagator(object):
             kmax = self._visit_steps_for(desc) if pairs else 1
             k = 0
             while k < nt:
-                self._launch_correlate(rows.row(k), per_trajectory=False, targets=targets)
+                self._launch_correlate(rows.row(k), per_trajectory=False, targets=targets, operators=operators)
                 ks = min(kmax, nt - k) if pairs else 1       # never a visit longer than the steps left
                 if ks == 2:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
-                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, targets=targets)
+                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, targets=targets,
+                                           operators=operators)
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -915,7 +1033,8 @@ class HermanKlukPropagator(object):
                     # and blocks comes from the j-th intermediate state
                     self._launch_step_visit(desc, dt, ks)
                     for j in range(1, ks):
-                        self._launch_correlate(rows.row(k + j), self._multi["states_mid"][j - 1], per_trajectory=False, targets=targets)
+                        self._launch_correlate(rows.row(k + j), self._multi["states_mid"][j - 1], per_trajectory=False, targets=targets,
+                                               operators=operators)
                     for _ in range(ks):
                         self.t += dt
                     k += ks
@@ -931,6 +1050,9 @@ class HermanKlukPropagator(object):
         if targets is not None:
             X, sigma_X = self.finalize_cross(cross[:nt], t0, dt, energy0_es, self._ntraj_norm)
             tail = (X, sigma_X) if standard_errors else (X,)
+        if operators is not None:
+            X, sigma_X = self.finalize_cross(opcorr[:nt], t0, dt, energy0_es, self._ntraj_norm)
+            tail = tail + ((X, sigma_X) if standard_errors else (X,))
         if standard_errors:
             return (self.finalize_slots(slots, t0, dt, energy0_es)
                     + self.finalize_moments(slots, moments, t0, dt, energy0_es, self._ntraj_norm) + tail)
@@ -950,6 +1072,7 @@ class HermanKlukPropagator(object):
     _rows = _StepRows               # widths, strides and validation of the output buffers of run()
     _whole_loop_ok = True           # WM needs its own per-step kernel between the steps
     _cross_ok = True                # WM has per-trajectory widths and another prefactor: no cross-correlation
+    _opcorr_ok = True               # ... and no operator correlation functions
 
     def _whole_loop_applies(self, desc):
         # (under a discard mask the sums come from the exported terms, which the whole-loop kernels do not write)
@@ -1638,6 +1761,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
     _whole_loop_ok = False          # ... by its own kernel, between the steps
     _multi_ok = False
     _cross_ok = False               # cross_correlation() and run(targets=...) raise NotImplementedError
+    _opcorr_ok = False              # operator_correlation() and run(operators=...) raise NotImplementedError
 
     def __init__(self, Gamma_i, Gamma_t, alpha, beta, device='cuda'):
         super().__init__(Gamma_i, Gamma_t, device=device)      # the Filinov matrix needs the dense monodromy blocks
@@ -1800,8 +1924,9 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
-    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None):
-        assert state is None and targets is None          # no pairs or visits; run(targets=...) is refused before the loop starts
+    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None, operators=None):
+        # no pairs or visits; run(targets=...) and run(operators=...) are refused before the loop starts
+        assert state is None and targets is None and operators is None
         # the per-trajectory terms were produced together with the prefactor; recompute (with the stored branch
         # signs, no tracking) only if the coupling vector was not known at that time
         knows_nac = self._wm_nac_bufs is not None or self._wm_nac_traj is not None

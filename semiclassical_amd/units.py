@@ -10,3 +10,6 @@ hartree_to_ev = 27.211396132
 bohr_to_angs = 0.529177249
 autime_to_fs = 0.02418884326505
 amu_to_aumass = 1822.888486192
+
+# not in the reference: the speed of light in atomic units, 1 / alpha (CODATA 2018), for the radiative rate (rates.radiative_rate)
+speed_of_light = 137.035999084
