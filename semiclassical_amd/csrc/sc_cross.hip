@@ -14,28 +14,21 @@
 //
 // cross_operands_kernel (dense widths only): the trajectory rows into caller-owned scratch, three D x D mat-vecs per trajectory,
 //   one trajectory per wavefront pass.  Diagonal widths need no pre-pass: the tile kernel scales q and p while it stages them.
-// cross_tile_kernel: one workgroup of 256 threads owns 64 trajectories (blockIdx.y, a "band") x 64 targets (blockIdx.x); thread
-//   (ti, tj) owns the 4 x 4 pairs of trajectories 4 ti + a and targets 4 tj + b (the mapping of pair_sum_kernel, phase A).  The
-//   d-loop is staged through LDS in chunks of CK; then one c_exp per pair, the product with v_i (formed once per trajectory by
-//   the first 64 threads exactly as hk_correlate_kernel forms it) and the three moment products.  The thread adds its 4
-//   trajectories in registers, the 16 threads of a target column add through LDS in a fixed order: one store of 5 doubles per
-//   target into partials[band][K][5].
-// cross_reduce_kernel: adds the bands in a fixed order (16 contiguous slices, then the slices) into the output row.
-// No atomics; the order of every sum is a function of (n, K) alone: the same bits in every call.  Discarded trajectories
-// (`kept`) and the rows beyond n are staged as zero operands with v = 0: they add exact zeros and never meet a non-finite value.
-#include "sc_common.h"
+// cross_tile_kernel: the tile mapping, the column reduction and the reduction over the bands of sc_rows5.h, the columns being the
+//   targets.  Per pair and d two FMAs for Re E and one for Im E; then one c_exp per pair and the product with v_i (formed once per
+//   trajectory by the first 64 threads exactly as hk_correlate_kernel forms it).
+// Discarded trajectories (`kept`) and the rows beyond n are staged as zero operands with v = 0: they add exact zeros and never
+// meet a non-finite value.
+#include "sc_rows5.h"
 
 namespace {
 
-#define CT 64      // tile edge
-#define CK 16      // d chunk
-#define CROW (CT + 2)   // row stride: 16-byte aligned, so that a thread's four values are two 16-byte LDS reads (with CT + 1 they are
-                        // two-address 8-byte reads at half the LDS rate: 0.33 instead of 0.22 ms at n = 1e5, K = 64, D = 60)
 
 // the LDS of the tile kernel: the d-chunk of both operand sets, reused for the column reduction
 struct alignas(16) CrossStage {
-    double ta[CK][CROW], tb[CK][CROW], tq[CK][CROW], tc[CK][CROW];      // trajectories: La q, Lb p, q, C p
-    double ka[CK][CROW], kb[CK][CROW], kq[CK][CROW], kg[CK][CROW];      // targets: La q_k, Lb p_k, q_k, C p_k - p_k
+    typedef double chunk[R5_CHUNK][R5_ROW];
+    chunk ta, tb, tq, tc;      // trajectories: La q, Lb p, q, C p
+    chunk ka, kb, kq, kg;      // targets: La q_k, Lb p_k, q_k, C p_k - p_k
 };
 
 struct CrossArgs {
@@ -50,24 +43,18 @@ struct CrossArgs {
     double *partials;               // [bands][K][5]
 };
 
-// four consecutive doubles of a staged row, from a 16-byte aligned address
-__device__ __forceinline__ void load4(const double *p, double (&o)[4]) {
-    const double2 lo = ((const double2 *)p)[0], hi = ((const double2 *)p)[1];
-    o[0] = lo.x; o[1] = lo.y; o[2] = hi.x; o[3] = hi.y;
-}
-
 template <bool DIAG>
 __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
     __shared__ CrossStage S;
-    __shared__ double2 vs[CT];      // v_i of the band's trajectories (0: beyond n, or discarded)
-    __shared__ int live[CT];
-    static_assert(sizeof(CrossStage) >= sizeof(double) * 16 * 5 * CT, "the column reduction reuses the staging buffers");
+    __shared__ double2 vs[R5_TILE]; // v_i of the band's trajectories (0: beyond n, or discarded)
+    __shared__ int live[R5_TILE];
+    static_assert(sizeof(CrossStage) >= sizeof(double) * R5_REDUCE_DOUBLES, "the column reduction reuses the staging buffers");
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
     const int D = A.st.dim;
-    const int64_t n = A.st.n, i0 = (int64_t)blockIdx.y * CT;
-    const int k0 = blockIdx.x * CT;
-    const int iv = (int)min((int64_t)CT, n - i0), kv = min(CT, A.K - k0);      // valid trajectories / targets of the tile
-    if (tid < CT) {
+    const int64_t n = A.st.n, i0 = (int64_t)blockIdx.y * R5_TILE;
+    const int k0 = blockIdx.x * R5_TILE;
+    const int iv = (int)min((int64_t)R5_TILE, n - i0), kv = min(R5_TILE, A.K - k0);      // valid rows / targets of the tile
+    if (tid < R5_TILE) {
         cplx v = c_make(0.0, 0.0);
         const int64_t tr = i0 + tid;
         const bool in = tid < iv && (!A.kept || A.kept[tr]);
@@ -86,10 +73,10 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) { re[a][b] = 0.0; im[a][b] = 0.0; }
-    for (int d0 = 0; d0 < D; d0 += CK) {
+    for (int d0 = 0; d0 < D; d0 += R5_CHUNK) {
         __syncthreads();                                   // live[] is written; the last readers of the chunk before are done
-        for (int e = tid; e < CK * CT; e += 256) {
-            const int r = e / CK, k = e - r * CK, d = d0 + k;      // row r of the tile, column k of the chunk
+        for (int e = tid; e < R5_CHUNK * R5_TILE; e += 256) {
+            const int r = e / R5_CHUNK, k = e - r * R5_CHUNK, d = d0 + k;      // row r of the tile, column k of the chunk
             double a = 0.0, b = 0.0, q = 0.0, c = 0.0;
             if (d < D && live[r]) {
                 if (DIAG) {
@@ -112,7 +99,7 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
         }
         __syncthreads();
 #pragma unroll 4
-        for (int k = 0; k < CK; ++k) {
+        for (int k = 0; k < R5_CHUNK; ++k) {
             double xa[4], xb[4], xq[4], xc[4], ya[4], yb[4], yq[4], yg[4];
             load4(&S.ta[k][4 * ti], xa); load4(&S.tb[k][4 * ti], xb); load4(&S.tq[k][4 * ti], xq); load4(&S.tc[k][4 * ti], xc);
             load4(&S.ka[k][4 * tj], ya); load4(&S.kb[k][4 * tj], yb); load4(&S.kq[k][4 * tj], yq); load4(&S.kg[k][4 * tj], yg);
@@ -137,23 +124,10 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
         for (int a = 0; a < 4; ++a) {
             const cplx o = c_scale(c_exp(c_make(-0.5 * re[a][b], -im[a][b] * (1.0 / SC_HBAR))), A.fac);
             const cplx x = c_mul(o, vs[4 * ti + a]);
-            sum[b][0] += x.x; sum[b][1] += x.y;
-            sum[b][2] = fma(x.x, x.x, sum[b][2]); sum[b][3] = fma(x.y, x.y, sum[b][3]); sum[b][4] = fma(x.x, x.y, sum[b][4]);
+            rows5_add(sum[b], x);
         }
     }
-    __syncthreads();                                       // the staging buffers are free
-    double (*red)[5][CT] = (double (*)[5][CT])&S;          // [ti][column][target]
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int c = 0; c < 5; ++c) red[ti][c][4 * tj + b] = sum[b][c];
-    __syncthreads();
-    for (int e = tid; e < 5 * kv; e += 256) {
-        const int t = e / 5, c = e - 5 * t;
-        double s = 0.0;
-        for (int g = 0; g < 16; ++g) s += red[g][c][t];
-        A.partials[((size_t)blockIdx.y * A.K + k0) * 5 + e] = s;
-    }
+    rows5_store_partials(sum, &S, tid, ti, tj, kv, k0, A.K, A.partials);
 }
 
 // dense widths: operands[i] = [La q_i | Lb p_i | q_i | C p_i].  La and Lb are symmetric, Ct is the TRANSPOSE of C: element (a, b)
@@ -181,33 +155,9 @@ __global__ __launch_bounds__(256) void cross_operands_kernel(sc_state st, const 
     }
 }
 
-// out[e] = sum over the bands of partials[band][e], e < total = 5 K: the bands in 16 contiguous slices, each added in order by
-// one thread, then the slices in order
-__global__ __launch_bounds__(256) void cross_reduce_kernel(const double *partials, int64_t bands, int64_t total, double *out,
-                                                           const long long *cursor) {
-    __shared__ double red[16][16];
-    const int sl = threadIdx.x >> 4, el = threadIdx.x & 15;
-    const int64_t e = (int64_t)blockIdx.x * 16 + el;
-    const int64_t per = (bands + 15) / 16, b0 = sl * per, b1 = min(b0 + per, bands);
-    double s = 0.0;
-    if (e < total)
-        for (int64_t b = b0; b < b1; ++b) s += partials[b * total + e];
-    red[sl][el] = s;
-    __syncthreads();
-    if (sl == 0 && e < total) {
-        double t = 0.0;
-        for (int g = 0; g < 16; ++g) t += red[g][el];
-        if (cursor) out += total * *cursor;
-        out[e] = t;
-    }
-}
-
 }  // namespace
 
-extern "C" int64_t sc_hk_cross_rows(int64_t n, int64_t K) {
-    if (n <= 0 || K <= 0) return 0;
-    return (n + CT - 1) / CT;
-}
+extern "C" int64_t sc_hk_cross_rows(int64_t n, int64_t K) { return sc_rows5_bands(n, K); }
 
 extern "C" int sc_hk_cross(const sc_state *st, const double *La, const double *Lb, const double *Ct, int32_t diag, double fac,
                            const double *targets, int32_t K, const double *vi, const double *probi, double mc_norm,
@@ -215,32 +165,25 @@ extern "C" int sc_hk_cross(const sc_state *st, const double *La, const double *L
                            void *stream) {
     if (!st || !La || !Lb || !Ct || !targets || !vi || !probi || !partials || !out)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_cross: null argument");
-    if (K < 1 || st->dim < 1 || st->n < 0)
-        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_cross: K=%d, D=%d, n=%lld", K, st->dim, (long long)st->n);
-    if (!diag && !operands) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_cross: dense widths need the operand scratch [n][4 D]");
-    if (st->dim > 512) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_cross: D=%d outside D <= 512", st->dim);
-    if (K > 65535) return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_cross: K=%d targets outside K <= 65535", K);
-    const int64_t bands = (st->n + CT - 1) / CT;
-    if (bands > 65535)
-        return sc_fail(SC_ERR_UNSUPPORTED, "sc_hk_cross: n=%lld trajectories outside n <= %d", (long long)st->n, CT * 65535);
+    int rc = sc_rows5_limits("sc_hk_cross", "K", "targets", st->n, st->dim, K,
+                             !diag && !operands ? "dense widths need the operand scratch [n][4 D]" : nullptr);
+    if (rc != SC_OK) return rc;
+    const int64_t bands = sc_rows5_bands(st->n, K);
     hipStream_t s = (hipStream_t)stream;
     if (bands > 0) {
         if (!diag) {
             const int64_t blocks = (st->n + 3) / 4;
             hipLaunchKernelGGL(cross_operands_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256),
                                (size_t)4 * 2 * st->dim * sizeof(double), s, *st, La, Lb, Ct, operands);
-            const int rc = sc_check_launch("sc_hk_cross (operands)");
+            rc = sc_check_launch("sc_hk_cross (operands)");
             if (rc != SC_OK) return rc;
         }
         CrossArgs a{*st, La, Lb, Ct, operands, targets, K, fac, mc_norm, vi, probi, kept, partials};
-        const dim3 grid((unsigned)((K + CT - 1) / CT), (unsigned)bands);
+        const dim3 grid((unsigned)((K + R5_TILE - 1) / R5_TILE), (unsigned)bands);
         if (diag) hipLaunchKernelGGL(cross_tile_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(cross_tile_kernel<false>, grid, dim3(256), 0, s, a);
-        const int rc = sc_check_launch("sc_hk_cross");
+        rc = sc_check_launch("sc_hk_cross");
         if (rc != SC_OK) return rc;
     }
-    const int64_t total = (int64_t)5 * K;
-    hipLaunchKernelGGL(cross_reduce_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, s, partials, bands, total, out,
-                       (const long long *)cursor);
-    return sc_check_launch("sc_hk_cross (reduction)");
+    return sc_rows5_reduce("sc_hk_cross (reduction)", partials, bands, K, out, cursor, s);
 }

@@ -108,6 +108,24 @@ def build_problem(task):
 # correlations.npz
 # ---------------------------------------------------------------------------------------------------------------------
 
+# The two families of five-sum rows as the driver carries them from the task to the result file.
+#   task_key  the task's key, an npz file (_load_targets / _load_operators)
+#   noun      the propagate_batch argument and the run() argument, and the noun of the messages; buffer: run()'s buffer argument
+#   idents    the arrays that say which estimator it is: the keys of the record, stored as prefix + key; as_run: the same arrays as
+#             run() takes them
+#   stored    the key of the pooled correlation functions; + "_second_moment" and + "_error" by the keep-or-drop rule
+#   what, rows  the nouns of the messages; ndim, expected: the shape check of the first array
+#   stale     derived keys that go stale when the correlation functions change
+RowFamily = namedtuple("RowFamily", "task_key noun buffer idents prefix as_run stored what rows ndim expected stale")
+ROW_FAMILIES = (
+    RowFamily("cross_correlation_targets", "targets", "cross", ("q", "p"), "cross_targets_", tuple, "cross_correlation",
+              "cross-correlation functions", "cross-correlation", 2, "arrays of shape (K, D) with K > 0 are", ()),
+    RowFamily("operator_correlation", "operators", "opcorr", ("bra_c", "bra_m", "ket_c", "ket_m"), "operator_",
+              lambda a: (tuple(a[:2]), tuple(a[2:])), "operator_correlation", "operator correlation functions",
+              "operator-correlation", 1, "c of shape (M,) with M > 0 is", ("operator_lineshape", "radiative_rate")),
+)
+
+
 class CorrelationStore(object):
     """The result file: ``propagator, times, autocorrelation, ic_correlation, adiabatic_gap, zero_point_energy,
     trajectories`` (cli.py:346-353), re-read and re-written after every batch so that an interrupted run keeps what it
@@ -135,41 +153,25 @@ class CorrelationStore(object):
             f"Time steps in {self.path} differ. Delete the old file or change the grid for time propagation."
         assert previous['propagator'] == propagator_name, "Data produced with different propagators cannot be added."
         if previous['trajectories'] > 0:
-            self._check_cross_targets(previous, cross_targets)
-            self._check_operators(previous, operators)
+            for fam, idents in zip(ROW_FAMILIES, (cross_targets, operators)):
+                self._check_family(fam, previous, idents)
 
-    CROSS_KEYS = ('cross_targets_q', 'cross_targets_p', 'cross_correlation')
+    CROSS_KEYS, OPERATOR_KEYS = (tuple(fam.prefix + key for key in fam.idents) + (fam.stored,) for fam in ROW_FAMILIES)
 
-    CROSS_ERROR_KEYS = ('cross_correlation_second_moment', 'cross_correlation_error')
+    CROSS_ERROR_KEYS, OPERATOR_ERROR_KEYS = ((fam.stored + '_second_moment', fam.stored + '_error') for fam in ROW_FAMILIES)
 
-    def _check_cross_targets(self, stored, targets):
-        """the stored cross-correlation functions belong to exactly the targets (q, p) of the task (None: the task has none)"""
-        have = 'cross_targets_q' in stored
-        if have != (targets is not None):
+    def _check_family(self, fam, stored, idents):
+        """the stored correlation functions of the family belong to exactly the identifying arrays of the task or batch (the targets
+        (q, p), the operators (bra_c, bra_m, ket_c, ket_m); None: it has none)"""
+        have = fam.prefix + fam.idents[0] in stored
+        if have != (idents is not None):
             raise ConfigurationError(
-                f"{self.path} holds {'cross-correlation functions' if have else 'no cross-correlation functions'}, this task "
-                f"{'has no' if have else 'has'} \"cross_correlation_targets\": they cannot be pooled")
-        if have and not (np.array_equal(stored['cross_targets_q'], targets[0]) and np.array_equal(stored['cross_targets_p'], targets[1])):
+                f"{self.path} holds {fam.what if have else 'no ' + fam.what}, this task "
+                f"{'has no' if have else 'has'} \"{fam.task_key}\": they cannot be pooled")
+        if have and not all(np.array_equal(stored[fam.prefix + key], new) for key, new in zip(fam.idents, idents)):
             raise ConfigurationError(
-                f"{self.path} holds cross-correlation functions with other targets than this task's "
-                "(\"cross_correlation_targets\"): they are different estimators and cannot be pooled")
-
-    OPERATOR_KEYS = ('operator_bra_c', 'operator_bra_m', 'operator_ket_c', 'operator_ket_m', 'operator_correlation')
-
-    OPERATOR_ERROR_KEYS = ('operator_correlation_second_moment', 'operator_correlation_error')
-
-    def _check_operators(self, stored, operators):
-        """the stored operator correlation functions belong to exactly the operators (bra_c, bra_m, ket_c, ket_m) of the task
-        (None: the task has none)"""
-        have = 'operator_bra_c' in stored
-        if have != (operators is not None):
-            raise ConfigurationError(
-                f"{self.path} holds {'operator correlation functions' if have else 'no operator correlation functions'}, this task "
-                f"{'has no' if have else 'has'} \"operator_correlation\": they cannot be pooled")
-        if have and not all(np.array_equal(stored[key], new) for key, new in zip(self.OPERATOR_KEYS[:4], operators)):
-            raise ConfigurationError(
-                f"{self.path} holds operator correlation functions with other operators than this task's "
-                "(\"operator_correlation\"): they are different estimators and cannot be pooled")
+                f"{self.path} holds {fam.what} with other {fam.noun} than this task's "
+                f"(\"{fam.task_key}\"): they are different estimators and cannot be pooled")
 
     ERROR_KEYS = ('autocorrelation_error', 'ic_correlation_error', 'autocorrelation_second_moment', 'ic_correlation_second_moment')
 
@@ -209,10 +211,10 @@ class CorrelationStore(object):
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
+        records = list(zip(ROW_FAMILIES, (cross, operators)))
         if done > 0:
-            self._check_cross_targets(stored, None if cross is None else (cross['q'], cross['p']))
-            self._check_operators(stored, None if operators is None else
-                                  tuple(operators[key] for key in ('bra_c', 'bra_m', 'ket_c', 'ket_m')))
+            for fam, record in records:
+                self._check_family(fam, stored, None if record is None else tuple(record[key] for key in fam.idents))
         discarding = symplecticity is not None and bool(symplecticity.get('discard', False))
         if done > 0:
             was_discarding = bool(stored.get('symplecticity_discard', False))
@@ -280,42 +282,27 @@ class CorrelationStore(object):
                            "the stored trajectories have none, or were checked at other steps or against another tolerance")
             for key in self.SYMPLECTICITY_KEYS:
                 stored.pop(key, None)
-        if cross is not None:
+        for fam, record in records:
+            if record is None:
+                continue
             pool = done > 0
-            new = np.asarray(cross['correlation'], dtype=complex)
-            stored['cross_targets_q'], stored['cross_targets_p'] = (np.asarray(cross[key], dtype=np.float64) for key in ('q', 'p'))
-            stored['cross_correlation'] = (ntraj * new + done * stored['cross_correlation']) / total if pool else new
-            moment = cross.get('second_moment', None)
-            have_moment = 'cross_correlation_second_moment' in stored
-            if moment is not None and (have_moment or not pool):
-                key = 'cross_correlation_second_moment'
-                stored[key] = (ntraj * moment + done * stored[key]) / total if pool else np.asarray(moment, dtype=np.float64)
-                stored['cross_correlation_error'] = hostmath.standard_errors(stored['cross_correlation'], stored[key] / total, total)
-            elif have_moment or moment is not None:
-                logger.warning("standard errors of the cross-correlation functions dropped from %s: %s", self.path,
-                               "the stored trajectories have no second moments" if moment is not None else
-                               "this task does not compute them (\"standard_errors\": true)")
-                for key in self.CROSS_ERROR_KEYS:
-                    stored.pop(key, None)
-        if operators is not None:
-            pool = done > 0
-            new = np.asarray(operators['correlation'], dtype=complex)
-            for key in ('bra_c', 'bra_m', 'ket_c', 'ket_m'):
-                stored['operator_' + key] = np.asarray(operators[key], dtype=np.float64)
-            stored['operator_correlation'] = (ntraj * new + done * stored['operator_correlation']) / total if pool else new
-            moment = operators.get('second_moment', None)
-            key = 'operator_correlation_second_moment'
+            new = np.asarray(record['correlation'], dtype=complex)
+            for key in fam.idents:
+                stored[fam.prefix + key] = np.asarray(record[key], dtype=np.float64)
+            stored[fam.stored] = (ntraj * new + done * stored[fam.stored]) / total if pool else new
+            moment = record.get('second_moment', None)
+            key = fam.stored + '_second_moment'
             have_moment = key in stored
             if moment is not None and (have_moment or not pool):
                 stored[key] = (ntraj * moment + done * stored[key]) / total if pool else np.asarray(moment, dtype=np.float64)
-                stored['operator_correlation_error'] = hostmath.standard_errors(stored['operator_correlation'], stored[key] / total, total)
+                stored[fam.stored + '_error'] = hostmath.standard_errors(stored[fam.stored], stored[key] / total, total)
             elif have_moment or moment is not None:
-                logger.warning("standard errors of the operator correlation functions dropped from %s: %s", self.path,
+                logger.warning(f"standard errors of the {fam.what} dropped from %s: %s", self.path,
                                "the stored trajectories have no second moments" if moment is not None else
                                "this task does not compute them (\"standard_errors\": true)")
-                for key in self.OPERATOR_ERROR_KEYS:
-                    stored.pop(key, None)
-            for key in ('operator_lineshape', 'radiative_rate'):      # computed from the old correlation functions: stale now
+                for drop in (key, fam.stored + '_error'):
+                    stored.pop(drop, None)
+            for key in fam.stale:            # computed from the old correlation functions: stale now
                 stored.pop(key, None)
         stored.pop('ic_rate', None)          # a rate computed from the old correlation function is stale now
         stored.pop('ic_rate_error', None)
@@ -399,25 +386,21 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     ``operators`` = (bra_c, bra_m, ket_c, ket_m): the operator correlation functions (propagator.run(operators=...)); the result then
     ends with yet another element, the record {'bra_c', 'bra_m', 'ket_c', 'ket_m', 'correlation' (nt, M)} and, with ``errors``,
     'second_moment' (nt, M, 3).  Single rank only, for the same reason."""
-    if operators is not None and flush is not None:
-        raise ValueError("operators are not available with more than one rank: the flush buffer does not carry the operator-correlation rows")
-    if targets is not None and flush is not None:
-        raise ValueError("targets are not available with more than one rank: the flush buffer does not carry the cross-correlation rows")
+    given = [(fam, idents) for fam, idents in zip(ROW_FAMILIES, (targets, operators)) if idents is not None]
+    for fam, _ in given:
+        if flush is not None:
+            raise ValueError(f"{fam.noun} are not available with more than one rank: the flush buffer does not carry the {fam.rows} rows")
     if discard_nonsymplectic and not (symplecticity_every > 0 and symplecticity_tolerance is not None):
         raise ValueError("discard_nonsymplectic needs symplecticity_every > 0 and a symplecticity_tolerance")
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
     moments = torch.zeros((nt, 6), dtype=torch.float64, device=propagator.device) if errors else None
-    blocks = counts = cross = opcorr = None
-    if operators is not None:
-        bra_c, bra_m, ket_c, ket_m = (np.asarray(a, dtype=np.float64) for a in operators)
-        if bra_c.ndim != 1 or bra_c.shape[0] == 0:
-            raise ValueError(f"operators: c of shape (M,) with M > 0 is expected, got {bra_c.shape}")
-        opcorr = torch.zeros((nt, bra_c.shape[0], 5), dtype=torch.float64, device=propagator.device)
-    if targets is not None:
-        Q, P = (np.asarray(a, dtype=np.float64) for a in targets)
-        if Q.ndim != 2 or Q.shape[0] == 0:
-            raise ValueError(f"targets: arrays of shape (K, D) with K > 0 are expected, got {Q.shape}")
-        cross = torch.zeros((nt, Q.shape[0], 5), dtype=torch.float64, device=propagator.device)
+    blocks = counts = None
+    rows5 = []                                    # per family given: (family, its identifying arrays, the buffer of raw rows)
+    for fam, idents in given:
+        idents = tuple(np.asarray(a, dtype=np.float64) for a in idents)
+        if idents[0].ndim != fam.ndim or idents[0].shape[0] == 0:
+            raise ValueError(f"{fam.noun}: {fam.expected} expected, got {idents[0].shape}")
+        rows5.append((fam, idents, torch.zeros((nt, idents[0].shape[0], 5), dtype=torch.float64, device=propagator.device)))
     if error_blocks:
         blocks = torch.zeros((nt, error_blocks, 4), dtype=torch.float64, device=propagator.device)
         counts = torch.from_numpy(propagator.block_counts(propagator.ntraj, error_blocks)).to(torch.float64)
@@ -434,11 +417,12 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
                                                discard=discard_nonsymplectic))
         count = stop - first
         pieces.append((first, count, propagator.t))
+        extra = {}
+        for fam, idents, buf in rows5:
+            extra.update({fam.noun: fam.as_run(idents), fam.buffer: buf[first:first + count]})
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
                        moments=None if moments is None else moments[first:first + count],
-                       blocks=None if blocks is None else blocks[first:first + count],
-                       **({} if cross is None else dict(targets=(Q, P), cross=cross[first:first + count])),
-                       **({} if opcorr is None else dict(operators=((bra_c, bra_m), (ket_c, ket_m)), opcorr=opcorr[first:first + count])))
+                       blocks=None if blocks is None else blocks[first:first + count], **extra)
     if symplecticity_every > 0 and pieces:
         # The clock of a piece is t0 + (dt + dt + ...), which differs from the uncut loop's 0 + dt + dt + ... in the last bits, and
         # with it the dynamical phase.  The check must leave every bit of the correlation functions as it is: the phase is taken
@@ -464,17 +448,10 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         if discard_nonsymplectic:
             record.update(kept=np.asarray(kept, dtype=np.int64), discard=True)
         tail = tail + (record,)
-    if cross is not None:
-        parts = [propagator.phased_cross(cross[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
+    for fam, idents, buf in rows5:
+        parts = [propagator.phased_cross(buf[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
         X, m3 = (np.concatenate(part) for part in zip(*parts))
-        record = {'q': Q, 'p': P, 'correlation': X}
-        if errors:
-            record['second_moment'] = propagator._ntraj_norm * m3
-        tail = tail + (record,)
-    if opcorr is not None:
-        parts = [propagator.phased_cross(opcorr[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
-        X, m3 = (np.concatenate(part) for part in zip(*parts))
-        record = {'bra_c': bra_c, 'bra_m': bra_m, 'ket_c': ket_c, 'ket_m': ket_m, 'correlation': X}
+        record = dict(zip(fam.idents, idents), correlation=X)
         if errors:
             record['second_moment'] = propagator._ntraj_norm * m3
         tail = tail + (record,)
@@ -562,24 +539,18 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     if check_every and world > 1:
         raise ConfigurationError("'check_symplecticity_every' is not available with more than one rank: the maximum over the "
                                  "trajectories does not fit the one sum all-reduce per batch")
-    # cross-correlation functions with target coherent states (a key the reference does not have): an npz file with
-    # arrays q and p (K, D), atomic units, in the coordinates of q0
-    targets_file = task.get('cross_correlation_targets', None)
-    if targets_file is not None and task.get('propagator', 'HK') == "WM":
-        raise ConfigurationError("'cross_correlation_targets' is not available with the WM propagator: its Gaussians have "
-                                 "per-trajectory widths and another prefactor")
-    if targets_file is not None and world > 1:
-        raise ConfigurationError("'cross_correlation_targets' is not available with more than one rank: the flush buffer does not "
-                                 "carry the cross-correlation rows")
-    # correlation functions with linear operators on both sides (a key the reference does not have): an npz file
-    # with arrays bra_c (M,), bra_m (M, D) and optionally ket_c, ket_m, atomic units, in the coordinates of q0
-    operators_file = task.get('operator_correlation', None)
-    if operators_file is not None and task.get('propagator', 'HK') == "WM":
-        raise ConfigurationError("'operator_correlation' is not available with the WM propagator: its Gaussians have "
-                                 "per-trajectory widths and another prefactor")
-    if operators_file is not None and world > 1:
-        raise ConfigurationError("'operator_correlation' is not available with more than one rank: the flush buffer does not "
-                                 "carry the operator-correlation rows")
+    # Two keys the reference does not have, an npz file each, atomic units, in the coordinates of q0.  "cross_correlation_targets":
+    # cross-correlation functions with target coherent states, arrays q and p (K, D).  "operator_correlation":
+    # correlation functions with linear operators on both sides, arrays bra_c (M,), bra_m (M, D) and optionally
+    # ket_c, ket_m.
+    targets_file, operators_file = (task.get(fam.task_key, None) for fam in ROW_FAMILIES)
+    for fam, file in zip(ROW_FAMILIES, (targets_file, operators_file)):
+        if file is not None and task.get('propagator', 'HK') == "WM":
+            raise ConfigurationError(f"'{fam.task_key}' is not available with the WM propagator: its Gaussians have "
+                                     "per-trajectory widths and another prefactor")
+        if file is not None and world > 1:
+            raise ConfigurationError(f"'{fam.task_key}' is not available with more than one rank: the flush buffer does not "
+                                     f"carry the {fam.rows} rows")
     setup = build_problem(task)
     targets = None if targets_file is None else _load_targets(targets_file, int(setup.q0.shape[0]))
     operators = None if operators_file is None else _load_operators(operators_file, int(setup.q0.shape[0]))
@@ -648,12 +619,10 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
                               across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks,
                               symplecticity_every=check_every, symplecticity_tolerance=tolerance, discard_nonsymplectic=discard,
                               targets=targets, operators=operators)
-        oprecord = None
-        if operators is not None:
-            out, oprecord = out[:-1], out[-1]
-        cross = None
-        if targets is not None:
-            out, cross = out[:-1], out[-1]
+        records = {}
+        for fam, idents in reversed(list(zip(ROW_FAMILIES, (targets, operators)))):
+            if idents is not None:
+                out, records[fam.noun] = out[:-1], out[-1]
         checks = None
         if check_every:
             out, checks = out[:-1], out[-1]
@@ -662,7 +631,8 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         assert not np.isnan(ic_correlation).any(), f"encountered NaN's in IC correlation : {ic_correlation}"
         if writer:
             store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:4] if errors else None,
-                            blocks=out[-1] if error_blocks else None, symplecticity=checks, cross=cross, operators=oprecord)
+                            blocks=out[-1] if error_blocks else None, symplecticity=checks, cross=records.get('targets'),
+                            operators=records.get('operators'))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

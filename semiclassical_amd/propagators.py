@@ -76,9 +76,20 @@ def _resolve_device(device):
 
 
 # One step's row of run()'s output buffers as the launches take it: the addresses of its slot, of its moments, blocks = (address, B)
-# and of its cross rows, None where there is no such buffer.  slots[k] is the slot as a tensor, formed only where torch adds the k_ic
-# sum to it (position-dependent couplings).  opcorr: the address of its operator-correlation rows (section 4.14), or None.
+# and of its five-sum rows cross and opcorr, None where there is no such buffer.  slots[k] is the slot as a
+# tensor, formed only where torch adds the k_ic sum to it (position-dependent couplings).
 _Row = collections.namedtuple("_Row", "slot moments blocks cross slots k opcorr", defaults=(None,))
+
+# The two families of five-sum rows as run() and _launch_correlate treat them.  arg: the argument of run(); field: its buffer
+# argument and the field of _Row; letter: the count and its key in the prepared dict; what: the launch in messages; prepare: the
+# method that validates the caller's argument into the prepared dict; launch: the method that fills a row from it; needs_terms:
+# the launch reads the per-trajectory terms, which the correlate kernel then has to export.
+_RowFamily = collections.namedtuple("_RowFamily", "arg field letter what prepare launch needs_terms")
+_ROW_FAMILIES = (
+    _RowFamily("targets", "cross", "K", "cross-correlation", "_prepare_targets", "_launch_cross", False),
+    _RowFamily("operators", "opcorr", "M", "operator-correlation", "_prepare_operators", "_launch_opcorr", True),
+)
+_OPERATOR_ROWS = _ROW_FAMILIES[1]
 
 
 class _StepRows(object):
@@ -101,14 +112,15 @@ class _StepRows(object):
             self._check("blocks", blocks, nt, ("B", self.BLOCK), device)
             if not hostmath.valid_error_blocks(int(blocks.shape[1])):
                 raise ValueError(f"the number of blocks has to be a power of two in 2 ... 64, got {int(blocks.shape[1])}")
-        if cross is not None:
-            self._check("cross", cross, nt, (K, self.CROSS), device)
-        if opcorr is not None:
-            self._check("opcorr", opcorr, nt, (M, self.OPCORR), device)
+        for name, t, count, width in (("cross", cross, K, self.CROSS), ("opcorr", opcorr, M, self.OPCORR)):
+            if t is not None:
+                self._check(name, t, nt, (count, width), device)
         self.slots, self.moments = slots, moments
         self.B, self.K, self.M = (None if t is None else int(t.shape[1]) for t in (blocks, cross, opcorr))
-        self._base = tuple(None if t is None else t.data_ptr() for t in (slots, moments, blocks, cross))
-        self._opcorr = None if opcorr is None else opcorr.data_ptr()
+        # per buffer: (address of row 0, bytes from row to row), None where there is none
+        given = (("slot", slots, self.SLOT, 1), ("moments", moments, self.MOMENT, 1), ("blocks", blocks, self.BLOCK, self.B),
+                 ("cross", cross, self.CROSS, self.K), ("opcorr", opcorr, self.OPCORR, self.M))
+        self._base = {name: None if t is None else (t.data_ptr(), 8 * width * count) for name, t, width, count in given}
 
     @staticmethod
     def _check(name, t, nt, row, device):           # row: the trailing shape ("B": any size)
@@ -119,11 +131,9 @@ class _StepRows(object):
 
     def row(self, k):
         """row k.  Row 0 is also the base the cursor routes take, row k0 the start of the piece a whole-loop launch fills from k0 on"""
-        slot, mom, blk, cross = self._base
-        return _Row(slot + 8 * self.SLOT * k, None if mom is None else mom + 8 * self.MOMENT * k,
-                    None if blk is None else (blk + 8 * self.BLOCK * self.B * k, self.B),
-                    None if cross is None else cross + 8 * self.CROSS * self.K * k, self.slots, k,
-                    None if self._opcorr is None else self._opcorr + 8 * self.OPCORR * self.M * k)
+        at = {name: None if base is None else base[0] + base[1] * k for name, base in self._base.items()}
+        return _Row(at["slot"], at["moments"], None if at["blocks"] is None else (at["blocks"], self.B), at["cross"], self.slots, k,
+                    at["opcorr"])
 
     @staticmethod
     def single(slot=None, moments=None, cross=None, opcorr=None):
@@ -659,14 +669,13 @@ class HermanKlukPropagator(object):
                                       ptr(self._masked_scratch), C_void(row.slot), None if row.moments is None else C_void(row.moments),
                                       None if out is None else C_void(out), self._stream()))
 
-    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None, operators=None):
+    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=()):
         """per-trajectory terms + their sums for the current state into `row` (_StepRows): the 5-double slot; the six second-moment
         sums, formed inside the correlate kernel; the block sums -- the terms are exported and sc_term_blocks follows the correlate
         kernel.  `state`: another view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi.  Under a
-        discard mask the correlate kernel only exports the terms; sc_term_masked_sums forms every sum from them.  `targets`
-        (_cross_targets): the (K, 5) sums of the cross-correlation of the same state with them go to the row's cross rows,
-        sc_hk_cross after the correlate kernel.  `operators` (_operators): the (M, 5) sums of the operator correlation functions
-        of the same state go to the row's opcorr rows, sc_hk_opcorr on the terms the correlate kernel has just exported."""
+        discard mask the correlate kernel only exports the terms; sc_term_masked_sums forms every sum from them.  `families`:
+        (family of _ROW_FAMILIES, its prepared dict) of the five-sum rows wanted: the (count, 5) sums of the same state go to the
+        family's field of the row, one launch each after the correlate kernel, which exports its terms where a launch reads them."""
         s = self._stream()
         nac = self._nac
         mom_ptr, blk = row.moments, row.blocks
@@ -675,7 +684,7 @@ class HermanKlukPropagator(object):
         if masked and generic:
             raise NotImplementedError("position-dependent derivative couplings are not available once trajectories have been "
                                       "discarded (discard_nonsymplectic)")
-        per_trajectory = per_trajectory or generic or blk is not None or masked or operators is not None
+        per_trajectory = per_trajectory or generic or blk is not None or masked or any(fam.needs_terms for fam, _ in families)
         in_kernel = mom_ptr is not None and not generic and not masked
         with self._timed("hk_correlate"):
             check(lib.sc_hk_correlate_m(self._state if state is None else state, self._ovl_t0, nac, ptr(self._vi), ptr(self.probi),
@@ -683,10 +692,8 @@ class HermanKlukPropagator(object):
                                         ptr(self._cq) if per_trajectory else None,
                                         ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
                                         ptr(self._mpart) if in_kernel else None, s))
-        if targets is not None:
-            self._launch_cross(targets, row.cross, state=state, cursor=cursor)
-        if operators is not None:
-            self._launch_opcorr(operators, row.opcorr, state=state, cursor=cursor)
+        for fam, prepared in families:
+            getattr(self, fam.launch)(prepared, getattr(row, fam.field), state=state, cursor=cursor)
         if masked:
             assert cursor is None
             self._masked_sums(nac is not None, row)
@@ -771,6 +778,14 @@ class HermanKlukPropagator(object):
             cc["partials"] = torch.empty(need, dtype=F64, device=self.device)
         return {"K": K, "rows": rows, "q": Q, "p": P}
 
+    def _prepare_targets(self, targets):
+        """run(targets=...): the caller's pair into the prepared dict of _cross_targets"""
+        try:
+            q_targets, p_targets = targets
+        except (TypeError, ValueError):
+            raise ValueError("targets: a pair (q_targets, p_targets) of arrays (K, D) is expected")
+        return self._cross_targets(q_targets, p_targets)
+
     def _launch_cross(self, targets, out_ptr, state=None, cursor=None):
         """the (K, 5) cross-correlation sums of `state` (default: the current one) into the doubles at `out_ptr`, or into row *cursor
         of the (., K, 5) buffer there (the cursor is read, not advanced); honours the discard mask"""
@@ -793,9 +808,13 @@ class HermanKlukPropagator(object):
         targets = self._cross_targets(q_targets, p_targets)
         out = torch.zeros((1, targets["K"], 5), dtype=F64, device=self.device)
         self._launch_cross(targets, self._rows.single(cross=out).cross)
+        return self._current_five_sums(out, energy0_es, standard_errors)
+
+    def _current_five_sums(self, out, energy0_es, standard_errors):
+        """X, or (X, sigma), of the current step from the one raw row (1, count, 5) a launch has just filled.  Synchronises."""
         self.synchronize()
-        C, sigma = self.finalize_cross(out, self.t, 0.0, energy0_es, self._ntraj_norm)
-        return (C[0], sigma[0]) if standard_errors else C[0]
+        X, sigma = self.finalize_cross(out, self.t, 0.0, energy0_es, self._ntraj_norm)
+        return (X[0], sigma[0]) if standard_errors else X[0]
 
     @staticmethod
     def phased_cross(cross, t0, dt, energy0_es):
@@ -868,6 +887,16 @@ class HermanKlukPropagator(object):
                         "partials": partials}
         return self._opcorr
 
+    def _prepare_operators(self, operators):
+        """run(operators=...): the caller's (bra, ket), or bra alone, into the prepared dict of _operators"""
+        if self._is_operator_set(operators):
+            operators = (operators, None)
+        try:
+            bra, ket = operators
+        except (TypeError, ValueError):
+            raise ValueError("operators: (bra, ket) or bra, each a pair (c, m) of arrays (M,) and (M, D), is expected")
+        return self._operators(bra, ket)
+
     def _launch_opcorr(self, operators, out_ptr, state=None, cursor=None):
         """the (M, 5) operator-correlation sums of `state` (default: the current one) from the terms _cq the correlate kernel has
         exported for it, into the doubles at `out_ptr`, or into row *cursor of the (., M, 5) buffer there (the cursor is read, not
@@ -892,10 +921,8 @@ class HermanKlukPropagator(object):
         operators = self._operators(bra, ket)
         out = torch.zeros((1, operators["M"], 5), dtype=F64, device=self.device)
         slot = torch.zeros(8, dtype=F64, device=self.device)
-        self._launch_correlate(self._rows.single(slot, opcorr=out), operators=operators)
-        self.synchronize()
-        X, sigma = self.finalize_cross(out, self.t, 0.0, energy0_es, self._ntraj_norm)
-        return (X[0], sigma[0]) if standard_errors else X[0]
+        self._launch_correlate(self._rows.single(slot, opcorr=out), families=((_OPERATOR_ROWS, operators),))
+        return self._current_five_sums(out, energy0_es, standard_errors)
 
     def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
             targets=None, cross=None, operators=None, opcorr=None):
@@ -947,48 +974,30 @@ class HermanKlukPropagator(object):
 
         Operator correlation functions: ``operators`` = (bra, ket) or bra alone, each a pair (c (M,), m (M, D)) of linear operators
         c_a + m_a.x (``operator_correlation``): a ``sc_hk_opcorr`` launch follows every correlate launch, which then exports its
-        per-trajectory terms as it does for blocks, the intermediate states of pairs and visits included.  With ``slots=None`` the
-        returned tuple gains ``X`` (nt, M) complex at its end (after the cross outputs), and ``sigma_X`` after it with
-        ``standard_errors=True``.  With ``slots`` given ``opcorr`` is required: a contiguous float64 device tensor (>= nt, M, 5) for the
-        raw rows, which ``finalize_cross`` takes as they are.  The rules of targets hold: never the one-launch kernel, everything
-        else the same bit for bit with or without operators, ``use_graph=True`` raises ``ValueError``.
+        per-trajectory terms as it does for blocks.  Everything said of targets holds with ``opcorr`` (>= nt, M, 5) in the place of
+        ``cross``; ``X`` (nt, M) and ``sigma_X`` come after the cross outputs.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
         if use_graph and self._kept is not None:
             raise ValueError("use_graph=True is not available once trajectories have been discarded (discard_nonsymplectic): the "
                              "graph replay has no masked reduction")
-        if targets is None and cross is not None:
-            raise ValueError("cross= receives the sums of run(targets=...): pass the targets as well")
-        if targets is not None:
+        given = {"targets": targets, "cross": cross, "operators": operators, "opcorr": opcorr}
+        families, bufs, counts = [], {}, {}
+        for fam in _ROW_FAMILIES:
+            arg, buf = given[fam.arg], given[fam.field]
+            if arg is None:
+                if buf is not None:
+                    raise ValueError(f"{fam.field}= receives the sums of run({fam.arg}=...): pass the {fam.arg} as well")
+                continue
             if use_graph:
-                raise ValueError("use_graph=True is not available with targets: the graph replay has no cross-correlation launch")
-            if slots is not None and cross is None:
-                raise ValueError("run(slots=..., targets=...) leaves the raw sums on the device: pass cross=, a float64 device tensor "
-                                 "(>= nt, K, 5), to receive those of the targets")
-            try:
-                q_targets, p_targets = targets
-            except (TypeError, ValueError):
-                raise ValueError("targets: a pair (q_targets, p_targets) of arrays (K, D) is expected")
-            targets = self._cross_targets(q_targets, p_targets)
-            if cross is None:
-                cross = torch.zeros((nt, targets["K"], 5), dtype=F64, device=self.device)
-        if operators is None and opcorr is not None:
-            raise ValueError("opcorr= receives the sums of run(operators=...): pass the operators as well")
-        if operators is not None:
-            if use_graph:
-                raise ValueError("use_graph=True is not available with operators: the graph replay has no operator-correlation launch")
-            if slots is not None and opcorr is None:
-                raise ValueError("run(slots=..., operators=...) leaves the raw sums on the device: pass opcorr=, a float64 device "
-                                 "tensor (>= nt, M, 5), to receive those of the operators")
-            if self._is_operator_set(operators):
-                operators = (operators, None)
-            try:
-                bra, ket = operators
-            except (TypeError, ValueError):
-                raise ValueError("operators: (bra, ket) or bra, each a pair (c, m) of arrays (M,) and (M, D), is expected")
-            operators = self._operators(bra, ket)
-            if opcorr is None:
-                opcorr = torch.zeros((nt, operators["M"], 5), dtype=F64, device=self.device)
+                raise ValueError(f"use_graph=True is not available with {fam.arg}: the graph replay has no {fam.what} launch")
+            if slots is not None and buf is None:
+                raise ValueError(f"run(slots=..., {fam.arg}=...) leaves the raw sums on the device: pass {fam.field}=, a float64 device "
+                                 f"tensor (>= nt, {fam.letter}, 5), to receive those of the {fam.arg}")
+            prepared = getattr(self, fam.prepare)(arg)
+            counts[fam.letter] = prepared[fam.letter]
+            bufs[fam.field] = torch.zeros((nt, counts[fam.letter], 5), dtype=F64, device=self.device) if buf is None else buf
+            families.append((fam, prepared))
         dt = float(dt)
         self._remember_nac(potential)
         own = slots is None
@@ -998,13 +1007,12 @@ class HermanKlukPropagator(object):
             slots = torch.zeros((nt, 5), dtype=F64, device=self.device)
             if standard_errors and moments is None:
                 moments = torch.zeros((nt, 6), dtype=F64, device=self.device)
-        rows = self._rows(self.device, nt, slots, moments, blocks, cross, None if targets is None else targets["K"],
-                          opcorr=opcorr, M=None if operators is None else operators["M"])
+        rows = self._rows(self.device, nt, slots, moments, blocks, **bufs, **counts)
         t0 = self.t
         fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model") and self.dim <= 64
                  and self._nac_generic is None)
         desc = self._potential_descriptor(potential, dt) if fused else None
-        if fused and targets is None and operators is None and self._whole_loop_applies(desc):
+        if fused and not families and self._whole_loop_applies(desc):
             # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run; it exports no per-step state
             # for the targets of a cross-correlation or for operators)
             self._run_whole_loop(desc, dt, nt, rows, potential)
@@ -1017,14 +1025,13 @@ class HermanKlukPropagator(object):
             kmax = self._visit_steps_for(desc) if pairs else 1
             k = 0
             while k < nt:
-                self._launch_correlate(rows.row(k), per_trajectory=False, targets=targets, operators=operators)
+                self._launch_correlate(rows.row(k), per_trajectory=False, families=families)
                 ks = min(kmax, nt - k) if pairs else 1       # never a visit longer than the steps left
                 if ks == 2:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
-                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, targets=targets,
-                                           operators=operators)
+                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, families=families)
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -1033,8 +1040,8 @@ class HermanKlukPropagator(object):
                     # and blocks comes from the j-th intermediate state
                     self._launch_step_visit(desc, dt, ks)
                     for j in range(1, ks):
-                        self._launch_correlate(rows.row(k + j), self._multi["states_mid"][j - 1], per_trajectory=False, targets=targets,
-                                               operators=operators)
+                        self._launch_correlate(rows.row(k + j), self._multi["states_mid"][j - 1], per_trajectory=False,
+                                               families=families)
                     for _ in range(ks):
                         self.t += dt
                     k += ks
@@ -1047,11 +1054,8 @@ class HermanKlukPropagator(object):
             return None
         self.synchronize()
         tail = ()
-        if targets is not None:
-            X, sigma_X = self.finalize_cross(cross[:nt], t0, dt, energy0_es, self._ntraj_norm)
-            tail = (X, sigma_X) if standard_errors else (X,)
-        if operators is not None:
-            X, sigma_X = self.finalize_cross(opcorr[:nt], t0, dt, energy0_es, self._ntraj_norm)
+        for fam, _ in families:
+            X, sigma_X = self.finalize_cross(bufs[fam.field][:nt], t0, dt, energy0_es, self._ntraj_norm)
             tail = tail + ((X, sigma_X) if standard_errors else (X,))
         if standard_errors:
             return (self.finalize_slots(slots, t0, dt, energy0_es)
@@ -1924,9 +1928,9 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
-    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, targets=None, operators=None):
+    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=()):
         # no pairs or visits; run(targets=...) and run(operators=...) are refused before the loop starts
-        assert state is None and targets is None and operators is None
+        assert state is None and not families
         # the per-trajectory terms were produced together with the prefactor; recompute (with the stored branch
         # signs, no tracking) only if the coupling vector was not known at that time
         knows_nac = self._wm_nac_bufs is not None or self._wm_nac_traj is not None
