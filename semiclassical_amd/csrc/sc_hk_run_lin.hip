@@ -10,7 +10,7 @@
 // kernel and its launcher; the entry points, the checks and the reductions are in sc_hk_run.hip.
 //
 // Per step and trajectory, in the order of the caller loop, with the arithmetic (and operation order) of the step-at-a-time
-// kernels, so that both paths agree to rounding:
+// kernels, so that both paths agree to rounding -- what it shares with hk_step_lin_kernel is written once, in sc_lin16.h:
 //   terms of C_auto, k_ic from the CURRENT state    hk_correlate_rows16_kernel: y = A dq, B dp, C dp as fused broadcast
 //                                                   multiply-adds, sums over the modes (sum_rows, sc_row16.h), then the scalar
 //                                                   tail every route calls (sc_common.h: overlap_value ... corr_k_term)   (:784-911)
@@ -20,17 +20,13 @@
 //                                                   pivot repeats the elimination with the pivot searched among the lanes
 //                                                   (the rows are still in registers)                  (:969-1052)
 #include "sc_hk_run.h"
-#include "sc_row16.h"
+#include "sc_lin16.h"
 
 namespace {
 
-template <int D, int DP, bool DIAG>
-struct RunLinLayout {
-    // per-lane rows of the constants, zero padded to 16 lanes; odd pitches spread the lanes over the LDS banks
-    static constexpr int PH = D + 1, PP = 4 * D + 1, PL = D + 1, PR = DP + 1, PD = D + 1;
-    static constexpr int n_doubles = 16 * PH + 16 * PP + 12 * 16 + (DIAG ? 0 : 2 * 16 * PL + 2 * 16 * PR) + 3 * 16 * PD;
-    static constexpr size_t bytes = (size_t)n_doubles * 8;
-};
+// LDS: the constants of both constant-Hessian kernels (sc_lin16.h) with this kernel's per-lane vectors among them (qk, pk, nq0, np0,
+// nrn, ngn, -), then the overlap rows A, B, C at the odd pitch D + 1
+template <int D, int DP, bool DIAG> using RunLinConsts = Lin16Consts<D, DP, DIAG, 12>;
 
 #ifndef SC_RUNLIN_OCC
 #define SC_RUNLIN_OCC 2
@@ -43,23 +39,19 @@ struct RunLinLayout {
 // phi_pp)_a -- 8 D plain multiply-adds per lane and step instead of the 8 D^2 broadcast multiply-adds of the product with Phi.
 template <int D, int DP, bool DIAG, bool MODAL, bool MOM>
 __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) void hk_run_lin_kernel(RunArgs R) {
-    typedef RunLinLayout<D, DP, DIAG> L;
-    constexpr int W = 2 * D, DD = D * D, N = DIAG ? D : DP;
-    constexpr int PH = L::PH, PP = L::PP, PL = L::PL, PR = L::PR, PD = L::PD;
+    typedef RunLinConsts<D, DP, DIAG> L;
+    constexpr int DD = D * D, N = DIAG ? D : DP, PD = D + 1;
     extern __shared__ double2 smem2[];
     const StepArgs &A = R.step;
     const int tid = threadIdx.x, lane = tid & 63, r = tid & 15, grp = tid >> 4, wave = tid >> 6, rowbase = tid & 48;
     const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
     const bool nac = R.has_nac != 0;
 
-    double *ls = (double *)smem2;
-    double *sH = ls;    ls += 16 * PH;
-    double *sPhi = ls;  ls += 16 * PP;             // row a: Phi_qq[a][:], Phi_qp[a][:], Phi_pq[a][:], Phi_pp[a][:]
-    double *svec = ls;  ls += 12 * 16;             // x0, g0, 1/m, st, 1/st, qk, pk, nq0, np0, nrn, ngn, -
-    double *sL1 = ls, *sL2 = sL1 + (DIAG ? 0 : 16 * PL), *sR1 = sL2 + (DIAG ? 0 : 16 * PL), *sR2 = sR1 + (DIAG ? 0 : 16 * PR);
-    ls = sR2 + (DIAG ? 0 : 16 * PR);
-    double *sOA = ls, *sOB = sOA + 16 * PD, *sOC = sOB + 16 * PD;
-
+    const L C((double *)smem2);
+    constexpr int W = 2 * D, PH = L::PH, PP = L::PP, PL = L::PL, PR = L::PR;
+    double *sH = C.sH, *sPhi = C.sPhi, *svec = C.svec, *sL1 = C.sL1, *sL2 = C.sL2, *sR1 = C.sR1, *sR2 = C.sR2;
+    double *sOA = (double *)smem2 + L::n_doubles, *sOB = sOA + 16 * PD, *sOC = sOB + 16 * PD;
+    // (Lin16Consts::stage written out, fused with the own rows: as a call <12, 7, false, false> spills 93 VGPRs; 62 before sc_lin16.h, 41 as built)
     for (int e = tid; e < 16 * D; e += 256) {
         const int i = e / D, b = e - i * D;
         const bool in = i < D;
@@ -128,6 +120,7 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
         double *M = A.st.mono + tr * 4 * (int64_t)DD, *qp = A.st.qp + tr * 2 * D;
         // ---- the trajectory: rows of the four blocks as [half][q | p block][column]: half 0 = (Mqq, Mpq), half 1 = (Mqp, Mpp)
         double cur[2][2][D];
+        // (load and write-back written out: through lin_load_half / lin_store_half <12, 7, false, false> spills 93 VGPRs; 62 before, 41 as built)
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -145,7 +138,7 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
         for (int k = 0; k < R.nsteps; ++k) {
             int lofs = 0;
             asm volatile("" : "+v"(lofs));         // the per-lane constants are re-read from LDS every step, never kept across steps
-            const double *cH = sH + lofs, *cPhi = sPhi + lofs, *cv = svec + lofs;
+            const double *cH = sH + lofs + r * PH, *cPhi = sPhi + lofs + r * PP, *cv = svec + lofs;     // the lane's rows of the constants
             double v5[5];
             // ---- terms of the correlation functions from the current state (hk_correlate_rows16_kernel) ----
             {
@@ -173,43 +166,17 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
                     v5[2] = kq.x; v5[3] = kq.y;
                 }
             }
-            // ---- (q, p, S): the explicit RK4 stages (V = E0 + g.dr + 1/2 dr.H.dr - origin, grad = g + H.dr), hk_step_lin_kernel ----
+            // ---- (q, p, S): the explicit RK4 stages (lin_rk4_row) ----
             {
-                double qs = q, ps = p, kqs = 0.0, kps = 0.0, qn = 0.0, pn = 0.0, red5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-                double hrow[D];
-#pragma unroll
-                for (int b = 0; b < D; ++b) hrow[b] = cH[r * PH + b];
-                sfor<0, 4>([&](auto sc_) {
-                    constexpr int s = decltype(sc_)::value;
-                    if (s > 0) { const double c = (s == 3) ? dt : hh; qs = q + c * kqs; ps = p + c * kps; }
-                    double dr = r < D ? qs - x0 : 0.0;
-                    double hd = 0.0, hd2 = 0.0;
-                    dpp_guard(dr);
-                    sfor<0, D>([&](auto bc_) {
-                        constexpr int b = decltype(bc_)::value;
-                        if (b & 1) fmac_bc<b>(hd2, dr, hrow[b]); else fmac_bc<b>(hd, dr, hrow[b]);
-                    });
-                    hd += hd2;
-                    const double v = dr * g0 + 0.5 * dr * hd;
-                    const double kq = ps * im, kp = -(g0 + hd), t = 0.5 * ps * ps * im;
-                    red5[s] = t - v;
-                    if (s == 3) red5[4] = t + v;
-                    const double w = (s == 0 || s == 3) ? 1.0 : 2.0;
-                    qn += w * kq; pn += w * kp;
-                    kqs = kq; kps = kp;
-                });
-                sum_rows<D>(red5, one);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) red5[s] -= A.pot.scalar0;
-                red5[4] += A.pot.scalar0;
-                if (r < D) { q = q + h6 * qn; p = p + h6 * pn; }
+                double red5[5];
+                lin_rk4_row<D>(cH, r, x0, g0, im, dt, hh, h6, q, p, red5);
+                lin_rk4_sums<D>(red5, one, A.pot.scalar0);
                 S = S + h6 * (red5[0] + 2.0 * red5[1] + 2.0 * red5[2] + red5[3]);
                 v5[4] = red5[4];
             }
-            // ---- [X; Y] <- Phi [X; Y], one half (Mqq, Mpq | Mqp, Mpp) at a time: row g of the old blocks comes from lane g
-            //      inside the multiply-add, Phi[r][g] from LDS ----
+            // ---- [X; Y] <- Phi [X; Y], one half (Mqq, Mpq | Mqp, Mpp) at a time (lin_phi_half); MODAL: 2 x 2 per mode ----
             if constexpr (MODAL) {
-                const double fqq = cPhi[r * PP], fqp = cPhi[r * PP + 1], fpq = cPhi[r * PP + 2], fpp = cPhi[r * PP + 3];
+                const double fqq = cPhi[0], fqp = cPhi[1], fpq = cPhi[2], fpp = cPhi[3];
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -223,66 +190,28 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
                 constexpr int h = decltype(hc)::value;
                 double (&Tq)[D] = cur[h][0], (&Tp)[D] = cur[h][1];
                 double Xq[D], Xp[D];
-#pragma unroll
-                for (int b = 0; b < D; ++b) { Xq[b] = 0.0; Xp[b] = 0.0; }
-                dpp_guard(Tq, Tp);
-                sfor<0, D>([&](auto gc) {
-                    constexpr int g = decltype(gc)::value;
-                    const double fqq = cPhi[r * PP + g], fqp = cPhi[r * PP + D + g];
-                    const double fpq = cPhi[r * PP + 2 * D + g], fpp = cPhi[r * PP + 3 * D + g];
-#pragma unroll
-                    for (int b = 0; b < D; ++b) { fmac_bc<g>(Xq[b], Tq[b], fqq); fmac_bc<g>(Xp[b], Tq[b], fpq); }
-#pragma unroll
-                    for (int b = 0; b < D; ++b) { fmac_bc<g>(Xq[b], Tp[b], fqp); fmac_bc<g>(Xp[b], Tp[b], fpp); }
-                });
+                lin_phi_half<D>(cPhi, Tq, Tp, Xq, Xp);
 #pragma unroll
                 for (int b = 0; b < D; ++b) { Tq[b] = Xq[b]; Tp[b] = Xp[b]; }
             });
-            // ---- prefactor matrix from the new rows (the formulas and the order of hk_step_lin_kernel) ----
+            // ---- prefactor matrix from the new rows (lin_prefactor_half, lin_sandwich) ----
             cplx mat[N];
             auto build_mat = [&]() {
                 if constexpr (DIAG) {
+                    // (both halves of an element together: in two passes of lin_prefactor_half <12, 12, true> takes 324 B of scratch; 232 before, 200 as built)
 #pragma unroll
                     for (int b = 0; b < D; ++b) {
-                        const double sib = ksi[b], isib = 1.0 / sib;
-                        mat[b] = r < D ? c_make(0.5 * (sta * isib * cur[0][0][b]), 0.5 * ((1.0 / SC_HBAR) * ista * isib * cur[0][1][b]))
-                                       : c_make(0.0, 0.0);
-                        mat[b] = r < D ? c_make(mat[b].x + 0.5 * (ista * sib * cur[1][1][b]), mat[b].y + 0.5 * (-SC_HBAR * sta * sib * cur[1][0][b]))
-                                       : c_make(0.0, 0.0);
+                        const double sib = ksi[b];
+                        lin_diag_element<0>(mat[b], r < D, sib, sta, ista, cur[0][0][b], cur[0][1][b]);
+                        lin_diag_element<1>(mat[b], r < D, sib, sta, ista, cur[1][0][b], cur[1][1][b]);
                     }
                 } else {
-                    double s1[DP], s2[DP], t1[DP], t2[DP];     // Mqq R1, Mqp R2, Mpp R2, Mpq R1
+                    Lin16Sums<DP, DIAG> sums;
                     sfor<0, 2>([&](auto hc) {
                         constexpr int h = decltype(hc)::value;
-                        double rr[DP];
-                        double (&uq)[DP] = h ? s2 : s1, (&up)[DP] = h ? t1 : t2;
-#pragma unroll
-                        for (int j = 0; j < DP; ++j) { rr[j] = ((h ? sR2 : sR1) + lofs)[r * PR + j]; uq[j] = 0.0; up[j] = 0.0; }
-                        dpp_guard(rr);
-                        sfor<0, D>([&](auto bcn) {
-                            constexpr int b = decltype(bcn)::value;
-#pragma unroll
-                            for (int j = 0; j < DP; ++j) { fmac_bc<b>(uq[j], rr[j], cur[h][0][b]); fmac_bc<b>(up[j], rr[j], cur[h][1][b]); }
-                        });
+                        lin_prefactor_half<D, DP, DIAG, h>(mat, sums, (h ? sR2 : sR1) + lofs + r * PR, ksi, sta, ista, r, cur[h][0], cur[h][1]);
                     });
-                    cplx X1[DP], X2[DP];
-#pragma unroll
-                    for (int j = 0; j < DP; ++j) {
-                        X1[j] = c_make(s1[j], -SC_HBAR * s2[j]);                 // Mqq R1 - i hbar Mqp R2
-                        X2[j] = c_make(t1[j], (1.0 / SC_HBAR) * t2[j]);          // Mpp R2 + i/hbar Mpq R1
-                        mat[j] = c_make(0.0, 0.0);
-                    }
-                    dpp_guard(X1, X2);
-                    sfor<0, D>([&](auto ac) {
-                        constexpr int a = decltype(ac)::value;
-                        const double l1 = (sL1 + lofs)[r * PL + a], l2 = (sL2 + lofs)[r * PL + a];
-#pragma unroll
-                        for (int j = 0; j < DP; ++j) { fmac_bc<a>(mat[j].x, X1[j].x, l1); fmac_bc<a>(mat[j].y, X1[j].y, l1); }
-#pragma unroll
-                        for (int j = 0; j < DP; ++j) { fmac_bc<a>(mat[j].x, X2[j].x, l2); fmac_bc<a>(mat[j].y, X2[j].y, l2); }
-                    });
-#pragma unroll
-                    for (int j = 0; j < DP; ++j) mat[j] = c_scale(mat[j], 0.5);
+                    lin_sandwich<D, DP>(mat, sums, sL1 + lofs + r * PL, sL2 + lofs + r * PL);
                 }
             };
             build_mat();
@@ -332,7 +261,7 @@ __global__ __launch_bounds__(256, MODAL ? SC_RUNLIN_MODAL_OCC : SC_RUNLIN_OCC) v
 
 template <int D, int DP, bool DIAG, bool MODAL, bool MOM>
 int launch_one(const RunArgs &a, int grid, hipStream_t s) {
-    const size_t lds = RunLinLayout<D, DP, DIAG>::bytes;
+    const size_t lds = (size_t)(RunLinConsts<D, DP, DIAG>::n_doubles + 3 * 16 * (D + 1)) * 8;
     if (hipFuncSetAttribute((const void *)hk_run_lin_kernel<D, DP, DIAG, MODAL, MOM>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds) != hipSuccess)
         return sc_check_launch("sc_hk_run (LDS attribute)");
@@ -363,15 +292,9 @@ int launch(const RunArgs &a, int grid, hipStream_t s, int do_launch) {
 }  // namespace
 
 int SC_RUNLIN_ENTRY(const RunArgs &a, int grid, hipStream_t s, int do_launch) {
-    const int D = a.step.st.dim, dp = a.step.hk.dprime;
-    const bool diag = a.step.hk.diag != 0;
-    if (!diag && !a.step.hk.real_lr) return 0;
-#define SC_RUNLIN_CASE(D_, DP_, DIAG_) if (D == D_ && dp == DP_ && diag == DIAG_) return launch<D_, DP_, DIAG_>(a, grid, s, do_launch);
-    SC_RUNLIN_CASE(12, 6, false) SC_RUNLIN_CASE(12, 12, true) SC_RUNLIN_CASE(9, 3, false) SC_RUNLIN_CASE(9, 9, true)
-    SC_RUNLIN_CASE(6, 6, true) SC_RUNLIN_CASE(6, 6, false) SC_RUNLIN_CASE(3, 3, true)
-    SC_RUNLIN_CASE(6, 1, false) SC_RUNLIN_CASE(9, 4, false) SC_RUNLIN_CASE(12, 7, false)
-#undef SC_RUNLIN_CASE
-    return 0;
+    return lin16_dispatch<true>(a.step.hk, a.step.st.dim, [&](auto d, auto dp, auto diag) {
+        return launch<decltype(d)::value, decltype(dp)::value, decltype(diag)::value>(a, grid, s, do_launch);
+    });
 }
 
 #ifndef SC_RUN_MOMENTS_TU

@@ -15,8 +15,7 @@
 // per-row constants sit in LDS (staged once per workgroup), uniform constants come from scalar registers.
 // Replaces hk_step_kernel<true> (every matrix in LDS, one 64-thread workgroup per trajectory) for the instantiated
 // shapes: config 3 (methylium, D = 12, d' = 6, n = 1e5) 1.78 -> 0.20 ms (docs/NOTEBOOK.md section 4.2).
-#include "sc_common.h"
-#include "sc_row16.h"
+#include "sc_lin16.h"
 
 #ifndef SC_LIN_OCC
 #define SC_LIN_OCC 2      // waves per SIMD the kernel is compiled for
@@ -48,8 +47,6 @@ struct LinDma {
     static constexpr int units = on ? 4 * wave_units + zero_units : 1;
 };
 
-// complex constant from LDS, read as two doubles
-__device__ __forceinline__ cplx lds_cplx(const cplx *p) { const double *d = (const double *)p; return c_make(d[0], d[1]); }
 __device__ __forceinline__ void lin_opaque(kptr &p) { asm volatile("" : "+s"(p)); }
 __device__ __forceinline__ void lin_opaque(int &v) { asm volatile("" : "+v"(v)); }
 
@@ -79,23 +76,6 @@ __device__ __forceinline__ void lin_lds_units(unsigned addr, lin_d2v (&v)[NJ]) {
     for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(v[j]));
 }
 
-template <int D, int DP, bool DIAG>
-struct LinLayout {
-    // doubles: H rows [16][D], Phi rows [16][4 D], per-lane vectors [8][16]; complex rows L1, L2 [16][D] and R1, R2 [16][d']
-    // (dense widths)
-    // Row pitches: every lane of a 16-lane row reads ITS row of a constant, so the pitch decides the LDS banks the lanes
-    // meet on.  Unpadded, Phi's rows (4 D doubles = 96 dwords at D = 12) put all lanes on one bank: a 12-way conflict on
-    // every read of the product loop, 87 % of the kernel's LDS cycles (SQ_LDS_BANK_CONFLICT).  One double (one complex
-    // number) more per row spreads the lanes over the banks.
-    // L1, L2, R1, R2 are REAL here (round 4): they are products of U and real symmetric square roots of the positive
-    // semi-definite width matrices; the reference carries them as complex128 with imaginary parts that are zero or rounding
-    // dust (1e-24 for methylium).  sc_hk_consts.real_lr says so; widths with genuinely complex roots take the LDS kernel.
-    static constexpr int PH = D + 1, PP = 4 * D + 1, PL = D + 1, PR = DP + 1;
-    static constexpr int n_real = 16 * PH + 16 * PP + 8 * 16;
-    static constexpr int n_lr = DIAG ? 0 : 2 * 16 * PL + 2 * 16 * PR;
-    static constexpr size_t bytes = (size_t)n_real * 8 + (size_t)n_lr * 8 + 16 * 8;
-};
-
 // Waves per SIMD: two for every shape (256 registers per lane).  The loop of the prefetching shapes must not spill: a scratch
 // reload is a vector-memory operation, and its vmcnt wait would also wait for every row request in flight (measured with
 // the prefactor accumulated from whole rows: 115 spilled registers at two waves, 0.40 ms with one wave and accumulator
@@ -104,52 +84,18 @@ template <int D> constexpr int lin_occ() { return SC_LIN_OCC; }
 
 template <int D, int DP, bool DIAG>
 __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs A) {
-    typedef LinLayout<D, DP, DIAG> L;
-    constexpr int W = 2 * D, DD = D * D, N = DIAG ? D : DP;
+    typedef Lin16Consts<D, DP, DIAG> L;
+    constexpr int DD = D * D, N = DIAG ? D : DP;
     extern __shared__ double2 smem2[];
     const int tid = threadIdx.x, r = tid & 15, grp = tid >> 4;
     const bool do_step = (A.mode & 0xff) == 0;
     const double dt = A.dt, hh = 0.5 * dt, h6 = dt / 6.0;
 
-    double *ls = (double *)smem2;
-    constexpr int PH = L::PH, PP = L::PP, PL = L::PL, PR = L::PR;
-    double *sH = ls;    ls += 16 * PH;
-    double *sPhi = ls;  ls += 16 * PP;             // row a: Phi_qq[a][:], Phi_qp[a][:], Phi_pq[a][:], Phi_pp[a][:]
-    double *svec = ls;  ls += 8 * 16;              // x0, g0, 1/m, st, 1/st
-    double *sL1 = ls, *sL2 = sL1 + 16 * PL;        // rows i < d' of Re L1, Re L2 (dense widths)
-    double *sR1 = sL2 + 16 * PL, *sR2 = sR1 + 16 * PR; // rows b < D of Re R1, Re R2
-    double *red = sL1 + L::n_lr;
-
-    for (int e = tid; e < 16 * D; e += 256) {
-        const int i = e / D, b = e - i * D;
-        sH[i * PH + b] = i < D ? A.pot.par2[i * D + b] : 0.0;
-        if (!DIAG) {
-            sL1[i * PL + b] = i < DP ? A.hk.L1[2 * (i * D + b)] : 0.0;          // real parts of the interleaved complex arrays
-            sL2[i * PL + b] = i < DP ? A.hk.L2[2 * (i * D + b)] : 0.0;
-        }
-    }
-    if (!DIAG) {
-        for (int e = tid; e < 16 * DP; e += 256) {
-            const int i = e / DP, j = e - i * DP;
-            sR1[i * PR + j] = i < D ? A.hk.R1[2 * (i * DP + j)] : 0.0;
-            sR2[i * PR + j] = i < D ? A.hk.R2[2 * (i * DP + j)] : 0.0;
-        }
-    }
-    for (int e = tid; e < 16 * 4 * D; e += 256) {
-        const int i = e / (4 * D), k = e - i * 4 * D, blk = k / D, g = k - blk * D;      // blk: qq, qp, pq, pp
-        const int row = (blk >> 1) * D + i, col = (blk & 1) * D + g;
-        sPhi[i * PP + k] = (i < D && A.pot.lin_prop) ? A.pot.lin_prop[row * W + col] : 0.0;
-    }
-    if (tid < 16) {
-        const bool in = tid < D;
-        svec[tid] = in ? A.pot.par0[tid] : 0.0;
-        svec[16 + tid] = in ? A.pot.par1[tid] : 0.0;
-        svec[32 + tid] = in ? A.pot.inv_mass[tid] : 0.0;
-        const double st = (DIAG && in) ? A.hk.st[tid] : 1.0;
-        svec[48 + tid] = st; svec[64 + tid] = 1.0 / st;
-    }
+    const L C((double *)smem2);
+    double *red = (double *)smem2 + L::n_doubles;
+    C.stage(A, tid);           // (a prefactor-only launch has no Phi: zeros)
     __syncthreads();
-    const double x0 = svec[r], g0 = svec[16 + r], im = svec[32 + r], sta = svec[48 + r], ista = svec[64 + r];
+    const double x0 = C.svec[r], g0 = C.svec[16 + r], im = C.svec[32 + r], sta = C.svec[48 + r], ista = C.svec[64 + r];
     kptr ksi = (kptr)A.hk.si;
 
     // ---- row prefetch (LinDma) ----
@@ -226,7 +172,7 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
         lin_opaque(ksi);
         int lofs = 0;
         lin_opaque(lofs);
-        const double *cH = sH + lofs, *cPhi = sPhi + lofs;
+        const double *cH = C.sH + lofs + r * L::PH, *cPhi = C.sPhi + lofs + r * L::PP;        // the lane's rows of the constants
 
         double q = 0.0, p = 0.0;
         // the read-modify-write operands of the row's first lane (action, previous determinant and branch sign) come with
@@ -247,83 +193,30 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
             }
         }
 
-        // ---- prefactor, accumulated HALF by half of the monodromy rows (columns of [Mqq; Mpq], then of [Mqp; Mpp]): a half
-        // is consumed as soon as its product is there and never lives next to the other one ----
-        // diagonal widths: mat_ab = 1/2 [st_a/si_b Mqq + si_b/st_a Mpp - i hbar st_a si_b Mqp + i/hbar Mpq/(st_a si_b)]  (:969-986)
-        // dense widths:    X1 = Mqq R1 - i hbar Mqp R2, X2 = Mpp R2 + i/hbar Mpq R1 (row r; rows b of R1, R2 come from lane b);
-        //                  mat' = 1/2 (L1 X1 + L2 X2): rows of X1, X2 from lane a, L1[i][a], L2[i][a] from LDS        (:969-994)
+        // ---- prefactor, accumulated HALF by half of the monodromy rows (lin_prefactor_half): a half is consumed as soon as its
+        // product is there and never lives next to the other one ----
         cplx mat[N];
-        constexpr int NS = DIAG ? 1 : DP;
-        double s1[NS], s2[NS], t1[NS], t2[NS];     // Mqq R1, Mqp R2, Mpp R2, Mpq R1 (real: R1, R2 are)
+        Lin16Sums<DP, DIAG> sums;
         auto accum_half = [&](auto hc, const double (&Xhq)[D], const double (&Xhp)[D]) {
             constexpr int h = decltype(hc)::value;
-            if constexpr (DIAG) {
-                WM_BLOCK {
-#pragma unroll
-                    for (int b = 0; b < D; ++b) {
-                        const double sib = ksi[b], isib = 1.0 / sib;
-                        if (h == 0) mat[b] = r < D ? c_make(0.5 * (sta * isib * Xhq[b]), 0.5 * ((1.0 / SC_HBAR) * ista * isib * Xhp[b])) : c_make(0.0, 0.0);
-                        else mat[b] = r < D ? c_make(mat[b].x + 0.5 * (ista * sib * Xhp[b]), mat[b].y + 0.5 * (-SC_HBAR * sta * sib * Xhq[b])) : c_make(0.0, 0.0);
-                    }
-                }
-            } else {
-                double rr[DP];
-                double (&uq)[NS] = h ? s2 : s1, (&up)[NS] = h ? t1 : t2;
-#pragma unroll
-                for (int j = 0; j < DP; ++j) {
-                    rr[j] = ((h ? sR2 : sR1) + lofs)[r * PR + j];
-                    uq[j] = 0.0; up[j] = 0.0;
-                }
-                dpp_guard(rr);
-                sfor<0, D>([&](auto bcn) {
-                    constexpr int b = decltype(bcn)::value;
-#pragma unroll
-                    for (int j = 0; j < DP; ++j) { fmac_bc<b>(uq[j], rr[j], Xhq[b]); fmac_bc<b>(up[j], rr[j], Xhp[b]); }
-                });
-            }
+            lin_prefactor_half<D, DP, DIAG, h>(mat, sums, (h ? C.sR2 : C.sR1) + lofs + r * L::PR, ksi, sta, ista, r, Xhq, Xhp);
         };
 
         if (FETCHED || do_step) {
-            // ---- (q, p, S): the explicit RK4 stages (V = E0 + g.dr + 1/2 dr.H.dr - origin, grad = g + H.dr) ----
-            double qs = q, ps = p, kqs = 0.0, kps = 0.0, qn = 0.0, pn = 0.0, red5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            double hrow[D];
-#pragma unroll
-            for (int b = 0; b < D; ++b) hrow[b] = cH[r * PH + b];
-            sfor<0, 4>([&](auto sc_) {
-                constexpr int s = decltype(sc_)::value;
-                if (s > 0) { const double c = (s == 3) ? dt : hh; qs = q + c * kqs; ps = p + c * kps; }
-                double dr = r < D ? qs - x0 : 0.0;
-                double hd = 0.0, hd2 = 0.0;         // two chains: consecutive multiply-adds do not wait for each other
-                dpp_guard(dr);
-                sfor<0, D>([&](auto bc_) {
-                    constexpr int b = decltype(bc_)::value;
-                    if (b & 1) fmac_bc<b>(hd2, dr, hrow[b]); else fmac_bc<b>(hd, dr, hrow[b]);
-                });
-                hd += hd2;
-                const double v = dr * g0 + 0.5 * dr * hd;           // + scalar0 after the reduction
-                const double kq = ps * im, kp = -(g0 + hd), t = 0.5 * ps * ps * im;
-                red5[s] = t - v;
-                if (s == 3) red5[4] = t + v;
-                const double w = (s == 0 || s == 3) ? 1.0 : 2.0;
-                qn += w * kq; pn += w * kp;
-                kqs = kq; kps = kp;
-            });
+            double red5[5];
+            lin_rk4_row<D>(cH, r, x0, g0, im, dt, hh, h6, q, p, red5);
             {
                 double one = 1.0;
                 asm volatile("" : "+v"(one));
-                sum_rows<D>(red5, one);               // over the lanes k < D: fused broadcast multiply-adds with 1.0
+                lin_rk4_sums<D>(red5, one, A.pot.scalar0);
             }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) red5[s] -= A.pot.scalar0;
-            red5[4] += A.pot.scalar0;
-            if (active && r < D) { qp[r] = q + h6 * qn; qp[D + r] = p + h6 * pn; }
+            if (active && r < D) { qp[r] = q; qp[D + r] = p; }
             if (active && r == 0) {
                 A.st.act[tr] = act_old + h6 * (red5[0] + 2.0 * red5[1] + 2.0 * red5[2] + red5[3]);
                 esum += red5[4];
             }
 
-            // ---- [X; Y] <- Phi [X; Y]: row g of the old blocks from lane g, Phi[r][g] from LDS.  Column c of the
-            // result needs column c of the old blocks only: one half (Mqq, Mpq | Mqp, Mpp) at a time ----
+            // ---- [X; Y] <- Phi [X; Y], one half (Mqq, Mpq | Mqp, Mpp) at a time (lin_phi_half) ----
             double Told[2][2][D], Xn[2][2][D];          // old and new rows: [half][q | p][column]
             if constexpr (FETCHED) {
                 lin_lds_rows<D>(rowaddr, Told[0][0], Told[0][1]);
@@ -331,29 +224,11 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
             } else {
                 // BOTH halves requested together: one HBM round trip per trajectory instead of one per half of the product
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int b = 0; b < D; ++b) {
-                        Told[h][0][b] = r < D ? M[(h ? DD : 0) + r * D + b] : 0.0;
-                        Told[h][1][b] = r < D ? M[(h ? DD : 0) + 2 * DD + r * D + b] : 0.0;
-                    }
+                for (int h = 0; h < 2; ++h) lin_load_half<D>(M, r, h, Told[h][0], Told[h][1]);
             }
             auto product = [&](auto hc) {
                 constexpr int h = decltype(hc)::value;
-                double (&Tq)[D] = Told[h][0], (&Tp)[D] = Told[h][1], (&Xq)[D] = Xn[h][0], (&Xp)[D] = Xn[h][1];
-#pragma unroll
-                for (int b = 0; b < D; ++b) { Xq[b] = 0.0; Xp[b] = 0.0; }
-                dpp_guard(Tq, Tp);
-                sfor<0, D>([&](auto gc) {
-                    constexpr int g = decltype(gc)::value;
-                    const double fqq = cPhi[r * PP + g], fqp = cPhi[r * PP + D + g];
-                    const double fpq = cPhi[r * PP + 2 * D + g], fpp = cPhi[r * PP + 3 * D + g];
-                    // X[r][b] += Phi[r][g] * old[g][b]: the old row g comes from lane g inside the multiply-add
-#pragma unroll
-                    for (int b = 0; b < D; ++b) { fmac_bc<g>(Xq[b], Tq[b], fqq); fmac_bc<g>(Xp[b], Tq[b], fpq); }
-#pragma unroll
-                    for (int b = 0; b < D; ++b) { fmac_bc<g>(Xq[b], Tp[b], fqp); fmac_bc<g>(Xp[b], Tp[b], fpp); }
-                });
+                lin_phi_half<D>(cPhi, Told[h][0], Told[h][1], Xn[h][0], Xn[h][1]);
             };
             auto store_half = [&](int h) {
                 if constexpr (FETCHED) {
@@ -370,11 +245,7 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
                         if (soff(j) >= 0) *(lin_d2v *)(dst + soff(j)) = v[j];
                     return;
                 }
-                if (active && r < D) {
-                    double *Oq = M + (h ? DD : 0), *Op = Oq + 2 * DD;
-#pragma unroll
-                    for (int b = 0; b < D; ++b) { Oq[r * D + b] = Xn[h][0][b]; Op[r * D + b] = Xn[h][1][b]; }
-                }
+                if (active && r < D) lin_store_half<D>(M, r, h, Xn[h][0], Xn[h][1]);
             };
             product(std::integral_constant<int, 0>{});
             accum_half(std::integral_constant<int, 0>{}, Xn[0][0], Xn[0][1]);
@@ -395,37 +266,11 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
             sfor<0, 2>([&](auto hc) {
                 constexpr int h = decltype(hc)::value;
                 double Xq[D], Xp[D];
-                WM_BLOCK {
-#pragma unroll
-                    for (int b = 0; b < D; ++b) {
-                        Xq[b] = r < D ? M[(h ? DD : 0) + r * D + b] : 0.0;
-                        Xp[b] = r < D ? M[(h ? DD : 0) + 2 * DD + r * D + b] : 0.0;
-                    }
-                }
+                WM_BLOCK { lin_load_half<D>(M, r, h, Xq, Xp); }
                 accum_half(hc, Xq, Xp);
             });
         }
-        if constexpr (!DIAG) {
-            cplx X1[DP], X2[DP];
-#pragma unroll
-            for (int j = 0; j < DP; ++j) {
-                X1[j] = c_make(s1[j], -SC_HBAR * s2[j]);                 // Mqq R1 - i hbar Mqp R2
-                X2[j] = c_make(t1[j], (1.0 / SC_HBAR) * t2[j]);          // Mpp R2 + i/hbar Mpq R1
-            }
-#pragma unroll
-            for (int j = 0; j < DP; ++j) mat[j] = c_make(0.0, 0.0);
-            dpp_guard(X1, X2);
-            sfor<0, D>([&](auto ac) {
-                constexpr int a = decltype(ac)::value;
-                const double l1 = (sL1 + lofs)[r * PL + a], l2 = (sL2 + lofs)[r * PL + a];
-#pragma unroll
-                for (int j = 0; j < DP; ++j) { fmac_bc<a>(mat[j].x, X1[j].x, l1); fmac_bc<a>(mat[j].y, X1[j].y, l1); }
-#pragma unroll
-                for (int j = 0; j < DP; ++j) { fmac_bc<a>(mat[j].x, X2[j].x, l2); fmac_bc<a>(mat[j].y, X2[j].y, l2); }
-            });
-#pragma unroll
-            for (int j = 0; j < DP; ++j) mat[j] = c_scale(mat[j], 0.5);
-        }
+        if constexpr (!DIAG) lin_sandwich<D, DP>(mat, sums, C.sL1 + lofs + r * L::PL, C.sL2 + lofs + r * L::PL);
         // determinant in the fixed pivot order (sc_row16.h); a weak pivot hands the trajectory to the fully pivoted
         // elimination of hk_step_kernel (fix-up launch of sc_hk_step, as on the separable fast path)
         int weak = SC_LIN_FORCE_FIXUP;
@@ -460,7 +305,7 @@ __global__ __launch_bounds__(256, lin_occ<D>()) void hk_step_lin_kernel(StepArgs
 
 template <int D, int DP, bool DIAG>
 int launch(const StepArgs &a, int grid, hipStream_t s) {
-    const size_t lds = LinLayout<D, DP, DIAG>::bytes;
+    const size_t lds = (size_t)(Lin16Consts<D, DP, DIAG>::n_doubles + 16) * 8;       // + the energy partials of the 16 rows
     if (hipFuncSetAttribute((const void *)hk_step_lin_kernel<D, DP, DIAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
         hipSuccess)
         return sc_check_launch("sc_hk_step (LDS attribute)");
@@ -481,15 +326,7 @@ int launch(const StepArgs &a, int grid, hipStream_t s) {
 // returns 1 and launches if the shape (D, d', diagonal widths) is instantiated, 0 if not, < 0 on error.  The caller
 // guarantees: SC_POT_HARMONIC_DENSE, pot.lin_prop built for this dt (mode 0), row-major monodromy blocks.
 int sc_launch_step_lin(const StepArgs &a, int grid, hipStream_t s) {
-    const int D = a.st.dim, dp = a.hk.dprime;
-    const bool diag = a.hk.diag != 0;
-    if (!diag && !a.hk.real_lr) return 0;       // genuinely complex L, R (indefinite rounding in the widths): the LDS kernel
-#define SC_LIN_CASE(D_, DP_, DIAG_) if (D == D_ && dp == DP_ && diag == DIAG_) return launch<D_, DP_, DIAG_>(a, grid, s);
-    SC_LIN_CASE(12, 6, false) SC_LIN_CASE(12, 12, true) SC_LIN_CASE(9, 3, false) SC_LIN_CASE(9, 9, true)
-    SC_LIN_CASE(6, 6, true) SC_LIN_CASE(6, 6, false) SC_LIN_CASE(3, 3, true)
-    // further molecular shapes (D = 3 N Cartesian coordinates, d' = D - 6, or D - 5 for a linear molecule)
-    SC_LIN_CASE(6, 1, false) SC_LIN_CASE(9, 4, false) SC_LIN_CASE(12, 7, false) SC_LIN_CASE(15, 9, false)
-    SC_LIN_CASE(15, 15, true)
-#undef SC_LIN_CASE
-    return 0;
+    return lin16_dispatch<false>(a.hk, a.st.dim, [&](auto d, auto dp, auto diag) {
+        return launch<decltype(d)::value, decltype(dp)::value, decltype(diag)::value>(a, grid, s);
+    });
 }

@@ -240,6 +240,27 @@ def test_step_physics_is_defined_once_in_the_source():
         assert holders == ["sc_common.h"], (needle, holders)
 
 
+def test_constant_hessian_pieces_are_defined_once_in_the_source():
+    """csrc/sc_lin16.h holds what hk_step_lin_kernel and hk_run_lin_kernel share: the two files read Phi and the prefactor constants
+    through it, and there is one list of instantiated shapes.  Exempt by name: the staging loop that hk_run_lin_kernel keeps written
+    out (fused with its own rows; the comment there names the instantiation whose spills rise otherwise) -- one read of each constant,
+    from the head of that loop to the barrier."""
+    csrc = os.path.join(ROOT, "semiclassical_amd", "csrc")
+    needles = ("pot.lin_prop", "hk.R1", "hk.R2", "hk.L1", "hk.L2")
+    code = lambda name: "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, name)))          # without comments
+    step, run, header = code("sc_hk_step_lin.hip"), code("sc_hk_run_lin.hip"), code("sc_lin16.h")
+    assert not [n for n in needles if n in step], "sc_hk_step_lin.hip reads a shared constant directly"
+    assert open(os.path.join(csrc, "sc_hk_run_lin.hip")).read().count("(Lin16Consts::stage written out") == 1
+    head, rest = run.split("for (int e = tid; e < 16 * D; e += 256)", 1)
+    staging, tail = rest.split("__syncthreads();", 1)
+    assert not [n for n in needles if n in head + tail], "sc_hk_run_lin.hip reads a shared constant outside its staging loop"
+    assert [staging.count(n) for n in needles] == [1, 1, 1, 1, 1]
+    for text in (step, run):
+        assert "_CASE(" not in text and "(12, 6, false" not in text and "{12, 6, false" not in text
+        assert text.count("lin16_dispatch<") == 1 and "real_lr" not in text.split("namespace {", 1)[1]
+    assert header.count("lin16_shapes[] =") == 1 and header.count("{12, 6, false, true}") == 1 and header.count("hk.real_lr") == 1
+
+
 def test_correlation_terms_are_defined_once_in_the_source():
     """the term of C_auto (conj(vt) vi f w), the trajectory factor f (signed root times action phase) and nacQ of the term of
     k_ic are written out in csrc/sc_common.h alone: every HK route calls corr_c_term / trajectory_factor / corr_k_term.
