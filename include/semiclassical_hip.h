@@ -584,6 +584,32 @@ int sc_hk_opcorr(const sc_state *st, const double *cq, const double *bra_u, cons
                  const double *g, int32_t M, const uint8_t *kept, double *partials, double *out, const int64_t *cursor,
                  void *stream);
 
+/* The same correlation functions for QUADRATIC operators A_a = c_a + m_a.x + 1/2 x^T K_a x (K_a real symmetric), B_a likewise
+ * (DESIGN.md section 4.16).  With every width fixed the matrix element is a quadratic form in the complex mean of the linear case,
+ *   <a|A|b> / <a|b> = c + m.x + 1/2 x^T K x + 1/2 tr(K S),   S = (Gamma_a + Gamma_b)^+,
+ *   x = S (Gamma_a q_a + Gamma_b q_b + i (p_b - p_a) / hbar),
+ * and the caller writes K = sum_r lambda_r v_r v_r^T (R eigenpairs kept): one side of one operator is 1 + R COLUMNS, each an affine
+ * form of sc_hk_opcorr.  All operators of a side are padded to the same R with columns of zeros.
+ *   z_col = k[col] + u[col].Q_i + i w[col].P_i            col = a (1 + R) + j, j = 0 ... R
+ *   f_ia  = l[a][0] z_(a,0) + sum_{j >= 1} l[a][j] z_(a,j)^2       column 0 enters to the first power, the others squared; added in
+ *                                                        column order.  From the current (Q_i, P_i) of `st` with bra_*, RA;
+ *   g_ia  = the same from the INITIAL points zi [n][2 D] = [q_i | p_i] with ket_*, RB: sc_hk_opquad_initial, once per ensemble
+ *           and set of operators, into g [n][M] complex;
+ *   x_ia  = f_ia g_ia cq_i,  out[a] = the five sums of sc_hk_opcorr.
+ *   *_u, *_w [M][1 + R][D] real, *_k [M][1 + R] complex (re, im), *_l [M][1 + R] real.  Column 0: (u, w, k) of sc_hk_opcorr for
+ *   (c, m) with 1/2 tr(K S) added to k, l = 1; column j >= 1: (u, w, k) of sc_hk_opcorr for (0, v_j), l = lambda_j / 2.
+ *   RA and RB are independent and either may be 0; with both 0 and l = 1 the rows are those of sc_hk_opcorr.
+ *   kept, partials (sc_hk_opquad_rows(n, M) * M * 5 doubles), out, cursor, `st`: as for sc_hk_opcorr.
+ * sc_hk_opquad: two launches; no atomics, the order of every sum is a function of (n, M, R) alone: the same bits in every call.
+ * D <= 512, 1 <= M <= 65535, n <= 64 * 65535, 0 <= R <= 512, M (1 + R) < 2^24; beyond: SC_ERR_UNSUPPORTED.  A null pointer, M < 1
+ * or R < 0: SC_ERR_BAD_ARGUMENT. */
+int64_t sc_hk_opquad_rows(int64_t n, int64_t M);
+int sc_hk_opquad_initial(const double *zi, int64_t n, int32_t D, const double *ket_u, const double *ket_w, const double *ket_k,
+                         const double *ket_l, int32_t M, int32_t RB, double *g, void *stream);
+int sc_hk_opquad(const sc_state *st, const double *cq, const double *bra_u, const double *bra_w, const double *bra_k,
+                 const double *bra_l, const double *g, int32_t M, int32_t RA, const uint8_t *kept, double *partials, double *out,
+                 const int64_t *cursor, void *stream);
+
 /* Frozen-Gaussian wavefunction on a spatial grid behind HermanKlukPropagator.wavefunction() (propagators.py:252-292,
  * 688-732):  phi[k] = fac sum_n v_n exp(-1/2 |Lx_k - Lq_n|^2 + i (p_n.x_k - pq_n)),  L = Gamma_t^(1/2).
  * LqT, PT [D][n] (trajectory index fastest), pq [n], v [n] complex, Lx, X [nx][D], phi [nx] complex. */

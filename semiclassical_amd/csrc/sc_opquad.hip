@@ -1,0 +1,268 @@
+// Operator correlation functions <phi_0| A_a e^(-iHt) B_a |phi_0> of the Herman-Kluk wavepacket for M pairs of QUADRATIC operators
+// A_a = c_a + m_a.x + 1/2 x^T K_a x (not in the reference) -- the kernels behind
+// HermanKlukPropagator.operator_correlation() and run(operators=...) once a K is given.  The structure is that of sc_opcorr.hip: a
+// bra-side factor at the current (Q_i, P_i), a ket-side factor at the initial (q_i, p_i), both on the C_auto term cq_i.  With every
+// width fixed, the Gaussian matrix element of a quadratic operator is a quadratic form in the complex mean x of section 4.14 plus a
+// constant, and the host writes K = sum_r lambda_r v_r v_r^T: one side of one operator is a list of 1 + R COLUMNS, each an affine
+// form of section 4.14,
+//
+//   z_col = k_col + u_col.Q_i + i w_col.P_i
+//   f_ia  = l_0 z_0 + sum_{col >= 1} l_col z_col^2          (column 0: the linear part, to the first power; the others squared)
+//   x_ia  = f_ia g_ia cq_i,  row a of the output: the five sums of x_ia over i (sc_rows5.h).
+//
+// opquad_tile_kernel: the tile mapping and the staged d-loop of sc_rows5.h / opcorr_tile_kernel, the tile columns being the COLUMNS
+//   of the operators, all of them in one array [M (1 + R)][D].  With 1 + R <= 64 a workgroup owns one tile of floor(64 / (1 + R))
+//   whole operators (their columns are contiguous, so the tile is a contiguous range of columns; the rest of the 64 is staged as
+//   zeros); with 1 + R > 64 a workgroup owns ONE operator and loops over its ceil((1 + R) / 64) tiles, f carried in registers.
+//   After the d-loop of a tile every thread forms t = l z^p of its 4 x 4 pairs; the t go through the staging LDS one plane (real,
+//   then imaginary) at a time, and the thread that owns (trajectory r, operator o) -- r = tid & 63, o = (tid >> 6) + 4 s -- adds
+//   the operator's columns in column order.  Then x = f g cq, x through the same LDS, and thread (operator, quarter of the band)
+//   adds its 16 trajectories in order; the four quarters are added in order: partials[band][M][5] for sc_rows5_reduce.
+//   The order of every sum is a function of (n, M, R) alone.
+// Discarded trajectories (`kept`) and the rows beyond n are staged as zero operands, and their cq and g are never loaded (x = 0 by
+// selection, not by a product): a non-finite value of a discarded trajectory cannot reach a sum.
+#include "sc_rows5.h"
+
+namespace {
+
+constexpr int STAGE_DOUBLES = 4 * R5_CHUNK * R5_ROW;       // the d-chunk of Q, P (trajectories) and u, w (columns)
+constexpr int PLANE_ROW = R5_TILE + 1;                     // row stride of a plane of t or x: lane = row reads without conflicts
+static_assert(R5_TILE * PLANE_ROW <= STAGE_DOUBLES, "a plane of t fits the staging buffers");
+static_assert(4 * 5 * R5_TILE <= STAGE_DOUBLES, "the four quarters of the five sums fit the staging buffers");
+
+struct OpquadArgs {
+    const double *qp;               // [n][2 D]
+    int64_t n;
+    int D, M, C1;                   // C1 = 1 + R columns per operator
+    const double *cq;               // [n] complex
+    const double *u, *w;            // [M C1][D]
+    const double *kap;              // [M C1] complex
+    const double *lam;              // [M C1]
+    const double *g;                // [n][M] complex
+    const uint8_t *kept;            // may be NULL
+    double *partials;               // [bands][M][5]
+};
+
+__global__ __launch_bounds__(256) void opquad_tile_kernel(OpquadArgs A) {
+    __shared__ alignas(16) double lds[STAGE_DOUBLES];
+    __shared__ double2 cqs[R5_TILE];// cq_i of the band's trajectories (0: beyond n, or discarded)
+    __shared__ int live[R5_TILE];
+    typedef double row[R5_ROW];
+    typedef double prow[PLANE_ROW];
+    row *tq = (row *)lds, *tp = tq + R5_CHUNK, *ku = tp + R5_CHUNK, *kw = ku + R5_CHUNK;
+    prow *plane = (prow *)lds;                             // [trajectory][tile column] of t; [operator][trajectory] of x
+    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
+    const int D = A.D, M = A.M, C1 = A.C1;
+    const int64_t i0 = (int64_t)blockIdx.y * R5_TILE;
+    const int iv = (int)min((int64_t)R5_TILE, A.n - i0);
+    // the workgroup's operators a0 ... a0 + ov - 1, its tiles, and the columns of an operator inside one tile
+    const bool wide = C1 > R5_TILE;
+    const int per = wide ? 1 : R5_TILE / C1;
+    const int a0 = blockIdx.x * per, ov = min(per, M - a0);
+    const int tiles = wide ? (C1 + R5_TILE - 1) / R5_TILE : 1;
+    const int64_t c0 = (int64_t)a0 * C1, cend = c0 + (int64_t)ov * C1;       // the workgroup's columns
+    const int pr = tid & (R5_TILE - 1), pw = tid >> 6;     // the (trajectory, operator) pairs of the thread: pr, pw + 4 s
+    if (tid < R5_TILE) {
+        const int64_t tr = i0 + tid;
+        const bool in = tid < iv && (!A.kept || A.kept[tr]);
+        cqs[tid] = in ? ((const cplx *)A.cq)[tr] : c_make(0.0, 0.0);
+        live[tid] = in;
+    }
+    double fre[16], fim[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) { fre[s] = 0.0; fim[s] = 0.0; }
+    for (int tile = 0; tile < tiles; ++tile) {
+        const int64_t k0 = c0 + (int64_t)tile * R5_TILE;
+        const int kv = (int)min((int64_t)R5_TILE, cend - k0);                  // valid columns of the tile
+        const int seg = wide ? kv : C1;                    // columns of one operator in this tile
+        double fr[4][4], fi[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { fr[a][b] = 0.0; fi[a][b] = 0.0; }
+        for (int d0 = 0; d0 < D; d0 += R5_CHUNK) {
+            __syncthreads();                               // live[] is written; the last readers of the buffers are done
+            for (int e = tid; e < R5_CHUNK * R5_TILE; e += 256) {
+                const int r = e / R5_CHUNK, k = e - r * R5_CHUNK, d = d0 + k;  // row r of the tile, column k of the chunk
+                double q = 0.0, p = 0.0;
+                if (d < D && live[r]) {
+                    const double *row = A.qp + (i0 + r) * 2 * D;
+                    q = row[d]; p = row[D + d];
+                }
+                tq[k][r] = q; tp[k][r] = p;
+                double u = 0.0, w = 0.0;
+                if (d < D && r < kv) {
+                    const size_t at = (size_t)(k0 + r) * D + d;
+                    u = A.u[at]; w = A.w[at];
+                }
+                ku[k][r] = u; kw[k][r] = w;
+            }
+            __syncthreads();
+#pragma unroll 4
+            for (int k = 0; k < R5_CHUNK; ++k) {
+                double xq[4], xp[4], yu[4], yw[4];
+                load4(&tq[k][4 * ti], xq); load4(&tp[k][4 * ti], xp);
+                load4(&ku[k][4 * tj], yu); load4(&kw[k][4 * tj], yw);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        fr[a][b] = fma(yu[b], xq[a], fr[a][b]);
+                        fi[a][b] = fma(yw[b], xp[a], fi[a][b]);
+                    }
+            }
+        }
+        // t = l z^p, z = k + (fr, fi), in place; the columns beyond kv give zero
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int col = 4 * tj + b;
+            const bool in = col < kv;
+            const cplx kap = in ? ((const cplx *)A.kap)[k0 + col] : c_make(0.0, 0.0);
+            const double lam = in ? A.lam[k0 + col] : 0.0;
+            const bool first = wide ? tile == 0 && col == 0 : col % C1 == 0;  // column 0 of its operator: the first power
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const cplx z = c_make(kap.x + fr[a][b], kap.y + fi[a][b]);
+                const cplx zp = first ? z : c_mul(z, z);
+                fr[a][b] = lam * zp.x; fi[a][b] = lam * zp.y;
+            }
+        }
+        // the columns of every operator, in column order, one plane at a time
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {
+            __syncthreads();                               // the buffers (or the plane before) are free
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) plane[4 * ti + a][4 * tj + b] = part == 0 ? fr[a][b] : fi[a][b];
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                const int o = pw + 4 * s;
+                if (o < ov) {
+                    double acc = part == 0 ? fre[s] : fim[s];
+                    const double *t = &plane[pr][o * seg];
+                    for (int j = 0; j < seg; ++j) acc += t[j];
+                    if (part == 0) fre[s] = acc; else fim[s] = acc;
+                }
+            }
+        }
+    }
+    // x_ia = f_ia g_ia cq_i, as planes [operator][trajectory]; thread (operator po, quarter pq) adds its 16 trajectories in order
+    const int po = tid & (R5_TILE - 1), pq = tid >> 6;
+    double xr[16], sum[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int o = pw + 4 * s;
+            if (o < ov) {
+                if (part == 0) {
+                    cplx x = c_make(0.0, 0.0);
+                    if (live[pr]) {
+                        const cplx g = ((const cplx *)A.g)[(size_t)(i0 + pr) * M + a0 + o];
+                        x = c_mul(c_mul(c_make(fre[s], fim[s]), g), cqs[pr]);
+                    }
+                    fre[s] = x.x; fim[s] = x.y;
+                }
+                plane[o][pr] = part == 0 ? fre[s] : fim[s];
+            }
+        }
+        __syncthreads();
+        if (po < ov) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const double v = plane[po][16 * pq + i];
+                if (part == 0) xr[i] = v;
+                else rows5_add(sum, c_make(xr[i], v));
+            }
+        }
+    }
+    __syncthreads();
+    double (*red)[5][R5_TILE] = (double (*)[5][R5_TILE])lds;
+    if (po < ov)
+#pragma unroll
+        for (int c = 0; c < 5; ++c) red[pq][c][po] = sum[c];
+    __syncthreads();
+    for (int e = tid; e < 5 * ov; e += 256) {
+        const int t = e / 5, c = e - 5 * t;
+        double s = 0.0;
+        for (int q = 0; q < 4; ++q) s += red[q][c][t];
+        A.partials[((size_t)blockIdx.y * M + a0) * 5 + e] = s;
+    }
+}
+
+// out[i][a] = sum over the columns of operator a of  l z^p,  z = k + u.z_i[:D] + i w.z_i[D:]  (p = 1 for column 0, else 2): one
+// (trajectory, operator) pair per thread, the operator index fastest
+__global__ __launch_bounds__(256) void opquad_initial_kernel(const double *z, int64_t n, int D, const double *u, const double *w,
+                                                             const double *kap, const double *lam, int M, int C1, double *out) {
+    const int64_t total = n * M;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t i = e / M;
+        const int a = (int)(e - i * M);
+        const double *row = z + i * 2 * D;
+        cplx f = c_make(0.0, 0.0);
+        for (int j = 0; j < C1; ++j) {
+            const size_t col = (size_t)a * C1 + j;
+            const double *uc = u + col * D, *wc = w + col * D;
+            double re = 0.0, im = 0.0;
+            for (int d = 0; d < D; ++d) {
+                re = fma(uc[d], row[d], re);
+                im = fma(wc[d], row[D + d], im);
+            }
+            const cplx zc = c_make(kap[2 * col] + re, kap[2 * col + 1] + im);
+            const cplx zp = j == 0 ? zc : c_mul(zc, zc);
+            f.x += lam[col] * zp.x; f.y += lam[col] * zp.y;
+        }
+        ((cplx *)out)[e] = f;
+    }
+}
+
+// 0 <= R <= 512 and M (1 + R) < 2^24, after the limits the linear kernels share
+int opquad_limits(const char *who, int64_t n, int D, int M, int R) {
+    if (R < 0) return sc_fail(SC_ERR_BAD_ARGUMENT, "%s: R=%d", who, R);
+    const int rc = sc_rows5_limits(who, "M", "operators", n, D, M, nullptr);
+    if (rc != SC_OK) return rc;
+    if (R > 512) return sc_fail(SC_ERR_UNSUPPORTED, "%s: R=%d outside R <= 512", who, R);
+    if ((int64_t)M * (1 + R) >= ((int64_t)1 << 24))
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: M (1 + R) = %lld columns outside M (1 + R) < 16777216", who,
+                       (long long)M * (1 + R));
+    return SC_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t sc_hk_opquad_rows(int64_t n, int64_t M) { return sc_rows5_bands(n, M); }
+
+extern "C" int sc_hk_opquad_initial(const double *zi, int64_t n, int32_t D, const double *ket_u, const double *ket_w,
+                                    const double *ket_k, const double *ket_l, int32_t M, int32_t RB, double *g, void *stream) {
+    if (!zi || !ket_u || !ket_w || !ket_k || !ket_l || !g) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad_initial: null argument");
+    const int rc = opquad_limits("sc_hk_opquad_initial", n, D, M, RB);
+    if (rc != SC_OK) return rc;
+    if (n == 0) return SC_OK;
+    const int64_t blocks = (n * M + 255) / 256;
+    hipLaunchKernelGGL(opquad_initial_kernel, dim3((unsigned)(blocks < 65535 ? blocks : 65535)), dim3(256), 0, (hipStream_t)stream,
+                       zi, n, D, ket_u, ket_w, ket_k, ket_l, M, 1 + RB, g);
+    return sc_check_launch("sc_hk_opquad_initial");
+}
+
+extern "C" int sc_hk_opquad(const sc_state *st, const double *cq, const double *bra_u, const double *bra_w, const double *bra_k,
+                            const double *bra_l, const double *g, int32_t M, int32_t RA, const uint8_t *kept, double *partials,
+                            double *out, const int64_t *cursor, void *stream) {
+    if (!st || !cq || !bra_u || !bra_w || !bra_k || !bra_l || !g || !partials || !out)
+        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad: null argument");
+    int rc = opquad_limits("sc_hk_opquad", st->n, st->dim, M, RA);
+    if (rc != SC_OK) return rc;
+    if (!st->qp) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad: the state has no qp");
+    const int64_t bands = sc_rows5_bands(st->n, M);
+    hipStream_t s = (hipStream_t)stream;
+    if (bands > 0) {
+        const int C1 = 1 + RA, per = C1 > R5_TILE ? 1 : R5_TILE / C1;
+        OpquadArgs a{st->qp, st->n, st->dim, M, C1, cq, bra_u, bra_w, bra_k, bra_l, g, kept, partials};
+        hipLaunchKernelGGL(opquad_tile_kernel, dim3((unsigned)((M + per - 1) / per), (unsigned)bands), dim3(256), 0, s, a);
+        rc = sc_check_launch("sc_hk_opquad");
+        if (rc != SC_OK) return rc;
+    }
+    return sc_rows5_reduce("sc_hk_opquad (reduction)", partials, bands, M, out, cursor, s);
+}

@@ -116,13 +116,17 @@ def build_problem(task):
 #   stored    the key of the pooled correlation functions; + "_second_moment" and + "_error" by the keep-or-drop rule
 #   what, rows  the nouns of the messages; ndim, expected: the shape check of the first array
 #   stale     derived keys that go stale when the correlation functions change
-RowFamily = namedtuple("RowFamily", "task_key noun buffer idents prefix as_run stored what rows ndim expected stale")
+#   optional  further identifying arrays that a task may leave out: absent means zeros (the Hessians K of the operators, DESIGN.md
+#             section 4.16); carried behind idents, stored only when the task gave them
+RowFamily = namedtuple("RowFamily", "task_key noun buffer idents prefix as_run stored what rows ndim expected stale optional",
+                       defaults=((),))
 ROW_FAMILIES = (
     RowFamily("cross_correlation_targets", "targets", "cross", ("q", "p"), "cross_targets_", tuple, "cross_correlation",
               "cross-correlation functions", "cross-correlation", 2, "arrays of shape (K, D) with K > 0 are", ()),
     RowFamily("operator_correlation", "operators", "opcorr", ("bra_c", "bra_m", "ket_c", "ket_m"), "operator_",
-              lambda a: (tuple(a[:2]), tuple(a[2:])), "operator_correlation", "operator correlation functions",
-              "operator-correlation", 1, "c of shape (M,) with M > 0 is", ("operator_lineshape", "radiative_rate")),
+              lambda a: (tuple(a[:2]) + tuple(a[4:5]), tuple(a[2:4]) + tuple(a[5:6])), "operator_correlation",
+              "operator correlation functions", "operator-correlation", 1, "c of shape (M,) with M > 0 is",
+              ("operator_lineshape", "radiative_rate"), ("bra_k", "ket_k")),
 )
 
 
@@ -137,7 +141,8 @@ class CorrelationStore(object):
     def start(self, task, propagator_name, times, setup, cross_targets=None, operators=None):
         """``cross_targets``: (q, p) of the task's "cross_correlation_targets", or None: a file that is added to has to hold
         exactly these (ConfigurationError otherwise, before any trajectory runs).  ``operators``: (bra_c, bra_m, ket_c, ket_m) of
-        the task's "operator_correlation", or None: the same rule."""
+        the task's "operator_correlation", or None: the same rule; (..., bra_k, ket_k) with Hessians (M, D, D), which a file
+        without them holds as zeros."""
         fresh = task['results'].get('overwrite', True) is True or not os.path.exists(self.path)
         if fresh:
             nt = len(times)
@@ -168,7 +173,14 @@ class CorrelationStore(object):
             raise ConfigurationError(
                 f"{self.path} holds {fam.what if have else 'no ' + fam.what}, this task "
                 f"{'has no' if have else 'has'} \"{fam.task_key}\": they cannot be pooled")
-        if have and not all(np.array_equal(stored[fam.prefix + key], new) for key, new in zip(fam.idents, idents)):
+        same = have and all(np.array_equal(stored[fam.prefix + key], new) for key, new in zip(fam.idents, idents))
+        for at, key in enumerate(fam.optional, len(fam.idents)):         # absent on either side: zeros
+            old, new = stored.get(fam.prefix + key), idents[at] if have and at < len(idents) else None
+            if old is not None and new is not None:
+                same = same and np.array_equal(old, new)
+            else:
+                same = same and not any(np.any(a) for a in (old, new) if a is not None)
+        if have and not same:
             raise ConfigurationError(
                 f"{self.path} holds {fam.what} with other {fam.noun} than this task's "
                 f"(\"{fam.task_key}\"): they are different estimators and cannot be pooled")
@@ -205,7 +217,9 @@ class CorrelationStore(object):
         keep-or-drop rule of the second moments, ``cross_correlation_second_moment`` and ``cross_correlation_error``.  Stored
         targets that differ from the batch's (or exist on one side only) are refused (ConfigurationError).
         ``operators``: the record of the batch's operator correlation functions: 'bra_c', 'ket_c' (M,),
-        'bra_m', 'ket_m' (M, D), 'correlation' (nt, M) and, with standard errors, 'second_moment' (nt, M, 3).  The file then holds
+        'bra_m', 'ket_m' (M, D), optionally the Hessians 'bra_k', 'ket_k' (M, D, D) of quadratic operators (section 4.16; stored as
+        ``operator_bra_k``, ``operator_ket_k`` only when given, absent = zeros), 'correlation' (nt, M) and, with standard errors,
+        'second_moment' (nt, M, 3).  The file then holds
         ``operator_bra_c``, ``operator_bra_m``, ``operator_ket_c``, ``operator_ket_m``, ``operator_correlation`` and, by the same
         keep-or-drop rule, ``operator_correlation_second_moment`` and ``operator_correlation_error``; everything as for ``cross``."""
         stored = dict(np.load(self.path))
@@ -214,7 +228,8 @@ class CorrelationStore(object):
         records = list(zip(ROW_FAMILIES, (cross, operators)))
         if done > 0:
             for fam, record in records:
-                self._check_family(fam, stored, None if record is None else tuple(record[key] for key in fam.idents))
+                self._check_family(fam, stored, None if record is None else
+                                   tuple(record[key] for key in fam.idents + fam.optional if key in record))
         discarding = symplecticity is not None and bool(symplecticity.get('discard', False))
         if done > 0:
             was_discarding = bool(stored.get('symplecticity_discard', False))
@@ -287,7 +302,7 @@ class CorrelationStore(object):
                 continue
             pool = done > 0
             new = np.asarray(record['correlation'], dtype=complex)
-            for key in fam.idents:
+            for key in fam.idents + tuple(key for key in fam.optional if key in record):
                 stored[fam.prefix + key] = np.asarray(record[key], dtype=np.float64)
             stored[fam.stored] = (ntraj * new + done * stored[fam.stored]) / total if pool else new
             moment = record.get('second_moment', None)
@@ -383,8 +398,9 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     ``targets`` = (Q, P), arrays (K, D): the cross-correlation functions with these target coherent states (propagator.run(targets=...));
     the result then ends with one more element still, the record {'q', 'p', 'correlation' (nt, K)} and, with ``errors``,
     'second_moment' (nt, K, 3), the per-sample second moments as (M_C, M_k).  Single rank only: the flush does not carry them.
-    ``operators`` = (bra_c, bra_m, ket_c, ket_m): the operator correlation functions (propagator.run(operators=...)); the result then
-    ends with yet another element, the record {'bra_c', 'bra_m', 'ket_c', 'ket_m', 'correlation' (nt, M)} and, with ``errors``,
+    ``operators`` = (bra_c, bra_m, ket_c, ket_m) or (..., bra_k, ket_k) with the Hessians (M, D, D) of quadratic operators: the
+    operator correlation functions (propagator.run(operators=...)); the result then ends with yet another element, the record
+    {'bra_c', 'bra_m', 'ket_c', 'ket_m', 'correlation' (nt, M)} (and 'bra_k', 'ket_k' when given) and, with ``errors``,
     'second_moment' (nt, M, 3).  Single rank only, for the same reason."""
     given = [(fam, idents) for fam, idents in zip(ROW_FAMILIES, (targets, operators)) if idents is not None]
     for fam, _ in given:
@@ -451,7 +467,7 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     for fam, idents, buf in rows5:
         parts = [propagator.phased_cross(buf[first:first + count], t0, dt, setup.zero_point_energy) for first, count, t0 in pieces]
         X, m3 = (np.concatenate(part) for part in zip(*parts))
-        record = dict(zip(fam.idents, idents), correlation=X)
+        record = dict(zip(fam.idents + fam.optional, idents), correlation=X)
         if errors:
             record['second_moment'] = propagator._ntraj_norm * m3
         tail = tail + (record,)
@@ -483,7 +499,9 @@ def _load_targets(path, dim):
 
 def _load_operators(path, dim):
     """(bra_c, bra_m, ket_c, ket_m), float64 (M,) and (M, D), of an "operator_correlation" file; without ket_c and ket_m the ket's
-    operators are the bra's"""
+    operators are the bra's.  With bra_k or ket_k (M, D, D), the symmetric Hessians of quadratic operators,
+    the result is (..., bra_k, ket_k): a ket without ket_c, ket_m and ket_k takes the bra's K as well, every other K left out is
+    zero."""
     try:
         with np.load(path, allow_pickle=False) as handle:
             bra_c, bra_m = (np.array(handle[key], dtype=np.float64) for key in ('bra_c', 'bra_m'))
@@ -491,6 +509,8 @@ def _load_operators(path, dim):
                 raise KeyError("ket_c and ket_m come together")
             ket_c, ket_m = ((np.array(handle[key], dtype=np.float64) for key in ('ket_c', 'ket_m')) if 'ket_c' in handle else
                             (bra_c.copy(), bra_m.copy()))
+            hessians = {key: np.array(handle[key], dtype=np.float64) for key in ('bra_k', 'ket_k') if key in handle}
+            whole_ket = 'ket_c' not in handle and 'ket_k' not in handle
     except (OSError, KeyError, ValueError) as err:
         raise ConfigurationError(f"'operator_correlation': {path} should be an npz file with arrays bra_c and bra_m (and ket_c, "
                                  f"ket_m) ({err})")
@@ -500,7 +520,14 @@ def _load_operators(path, dim):
                                      f"expected in {path}, got {c.shape} and {m.shape}")
         if not (np.isfinite(c).all() and np.isfinite(m).all()):
             raise ConfigurationError(f"'operator_correlation': non-finite entry in {path}")
-    return bra_c, bra_m, ket_c, ket_m
+    if not hessians:
+        return bra_c, bra_m, ket_c, ket_m
+    shape = (bra_c.shape[0], dim, dim)
+    for key, k in hessians.items():
+        if k.shape != shape or not np.isfinite(k).all() or abs(k - np.swapaxes(k, 1, 2)).max() > 1.0e-12 * abs(k).max():
+            raise ConfigurationError(f"'operator_correlation': {key} of shape {shape}, finite and symmetric, is expected in {path}")
+    bra_k = hessians.get('bra_k', np.zeros(shape))
+    return bra_c, bra_m, ket_c, ket_m, bra_k, hessians.get('ket_k', bra_k.copy() if whole_ket else np.zeros(shape))
 
 
 def run_semiclassical_dynamics(task, device='cuda', comm=None):
@@ -542,7 +569,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     # Two keys the reference does not have, an npz file each, atomic units, in the coordinates of q0.  "cross_correlation_targets":
     # cross-correlation functions with target coherent states, arrays q and p (K, D).  "operator_correlation":
     # correlation functions with linear operators on both sides, arrays bra_c (M,), bra_m (M, D) and optionally
-    # ket_c, ket_m.
+    # ket_c, ket_m; quadratic operators with bra_k (M, D, D) and optionally ket_k.
     targets_file, operators_file = (task.get(fam.task_key, None) for fam in ROW_FAMILIES)
     for fam, file in zip(ROW_FAMILIES, (targets_file, operators_file)):
         if file is not None and task.get('propagator', 'HK') == "WM":

@@ -160,6 +160,62 @@ def fold_linear_operators(c, m, G_traj, G_0, q0, p0, ket):
     return (Sm @ G_traj).contiguous(), (-sign / hbar * Sm).contiguous(), kappa.contiguous()
 
 
+def fold_quadratic_operators(c, m, K, G_traj, G_0, q0, p0, ket):
+    """(u, w, kappa, lam, R): the Gaussian matrix element of the quadratic operators c_a + m_a.x + 1/2 x^T K_a x between phi_0 and a
+    trajectory's Gaussian, divided by their overlap, as 1 + R COLUMNS per operator.  With x the complex
+    mean of ``fold_linear_operators`` and S = (G_traj + G_0)^+ the element is  c + m.x + 1/2 x^T K x + 1/2 tr(K S); with the
+    symmetric eigendecomposition K = sum_r lambda_r v_r v_r^T it reads  sum_col lam_col z_col^(p_col),
+    z_col = kappa_col + u_col.q + i w_col.p:  column 0 the linear part (p = 1, lam = 1, kappa = that of (c, m) + 1/2 tr(K S)),
+    columns 1 ... R the eigenvectors ((u, w, kappa) of the linear operator (0, v_r), p = 2, lam = lambda_r / 2).  Eigenpairs with
+    |lambda_r| <= 1e-12 max |lambda| are dropped; R is the largest number kept by an operator, the others are padded with columns
+    of zeros.  c (M,), m (M, D), K (M, D, D) real or None (= zeros); returns real (M, 1 + R, D) twice, complex (M, 1 + R), real
+    (M, 1 + R) and R.  ValueError for a K that is not symmetric to 1e-12 of its largest entry, a non-finite K, and an m or a kept
+    eigenvector outside the range of G_traj + G_0 (the test of ``fold_linear_operators``)."""
+    M, D = m.shape
+    u0, w0, k0 = fold_linear_operators(c, m, G_traj, G_0, q0, p0, ket)
+    kept = []                                               # per operator: (lambda_r, v_r) of the eigenpairs kept
+    if K is not None:
+        if tuple(K.shape) != (M, D, D):
+            raise ValueError(f"operators: K of shape ({M}, {D}, {D}) is expected, got {tuple(K.shape)}")
+        if not bool(torch.isfinite(K).all()):
+            raise ValueError("operators: non-finite entry in K")
+        e, V = _eigh(G_traj + G_0)
+        keep = abs(e) > ZERO
+        S = torch.einsum('ij,j,kj->ik', V[:, keep], 1.0 / e[keep], V[:, keep])
+        k0 = k0.clone()
+        for a in range(M):
+            Ka = K[a]
+            if float(abs(Ka - Ka.T).max()) > 1.0e-12 * float(abs(Ka).max()):
+                raise ValueError(f"operators: K of operator {a} is not symmetric")
+            lam, vec = _eigh(0.5 * (Ka + Ka.T))
+            big = abs(lam) > 1.0e-12 * float(abs(lam).max())
+            kept.append((lam[big], vec[:, big].T.contiguous()))
+            k0[a] += 0.5 * float(torch.sum(Ka * S))         # tr(K S), both symmetric
+    R = max((int(lam.shape[0]) for lam, _ in kept), default=0)
+    u, w = torch.zeros((M, 1 + R, D), dtype=torch.float64), torch.zeros((M, 1 + R, D), dtype=torch.float64)
+    kappa, lam_out = torch.zeros((M, 1 + R), dtype=C128), torch.zeros((M, 1 + R), dtype=torch.float64)
+    u[:, 0], w[:, 0], kappa[:, 0], lam_out[:, 0] = u0, w0, k0, 1.0
+    if R == 0:
+        return u, w, kappa, lam_out, R
+    fold = lambda vec: fold_linear_operators(torch.zeros(vec.shape[0], dtype=torch.float64), vec, G_traj, G_0, q0, p0, ket)
+    try:
+        ur, wr, kr = fold(torch.cat([vec for _, vec in kept]))          # the eigenvectors of every operator in one call
+    except ValueError:
+        for a, (lam, vec) in enumerate(kept):                           # ... and one by one to name the operator
+            try:
+                fold(vec)
+            except ValueError:
+                raise ValueError(f"operators: K of operator {a} has a component outside the range of the sum of the widths: the "
+                                 "matrix element along a null direction does not exist")
+        raise
+    at = 0
+    for a, (lam, vec) in enumerate(kept):
+        r = int(lam.shape[0])
+        u[a, 1:1 + r], w[a, 1:1 + r], kappa[a, 1:1 + r], lam_out[a, 1:1 + r] = ur[at:at + r], wr[at:at + r], kr[at:at + r], 0.5 * lam
+        at += r
+    return u, w, kappa, lam_out, R
+
+
 def time_grid(nt, dt):
     """t_k of the propagator: t accumulates `t += dt` (propagators.py:655), not k*dt"""
     t, out = 0.0, np.empty(nt)

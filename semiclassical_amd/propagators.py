@@ -834,57 +834,101 @@ class HermanKlukPropagator(object):
         C, m3 = HermanKlukPropagator.phased_cross(cross, t0, dt, energy0_es)
         return C, hostmath.standard_errors(C, m3, ntraj_norm)
 
-    # ---- correlation functions with linear operators (not in the reference) ----
+    # ---- correlation functions with linear and quadratic operators (not in the reference; DESIGN.md sections 4.14, 4.16) ----
     @staticmethod
     def _is_operator_set(x):
-        """(c, m) with c one-dimensional and m two-dimensional"""
+        """(c, m) or (c, m, K) with c one-dimensional, m two-dimensional and K three-dimensional or None"""
         try:
-            return len(x) == 2 and np.ndim(x[0]) == 1 and np.ndim(x[1]) == 2
+            return (len(x) in (2, 3) and np.ndim(x[0]) == 1 and np.ndim(x[1]) == 2
+                    and (len(x) == 2 or x[2] is None or np.ndim(x[2]) == 3))
         except (TypeError, ValueError):
             return False
 
     def _operator_set(self, name, ops):
-        """validated (c (M,), m (M, D)) of one side as fp64 host tensors"""
+        """validated (c (M,), m (M, D)) of one side as fp64 host tensors (its K: _operator_hessians)"""
+        expected = (f"operators: {name} = (c, m) or (c, m, K) with c of shape (M,), m of shape (M, {self.dim}) and K of shape "
+                    f"(M, {self.dim}, {self.dim}) or None is expected")
         if not self._is_operator_set(ops):
-            raise ValueError(f"operators: {name} = (c, m) with c of shape (M,) and m of shape (M, {self.dim}) is expected")
+            raise ValueError(expected)
         try:
             c, m = np.asarray(ops[0], dtype=np.float64), np.asarray(ops[1], dtype=np.float64)
         except (TypeError, ValueError) as err:
             raise ValueError(f"operators: real arrays are expected for {name} ({err})")
         if m.shape != (c.shape[0], self.dim):
-            raise ValueError(f"operators: {name} = (c, m) with c of shape (M,) and m of shape (M, {self.dim}) is expected, got "
-                             f"{c.shape} and {m.shape}")
+            raise ValueError(f"{expected}, got {c.shape} and {m.shape}")
         if c.shape[0] == 0:
             raise ValueError("operators: at least one operator is expected (M = 0)")
         if not (np.isfinite(c).all() and np.isfinite(m).all()):
             raise ValueError(f"operators: non-finite entry in {name}")
         return torch.from_numpy(c.copy()), torch.from_numpy(m.copy())
 
+    @staticmethod
+    def _operator_hessians(name, ops, M, D):
+        """validated K (M, D, D) of one side's (c, m, K) as an fp64 host tensor; None when the set has no K, K is None or every entry
+        is zero: the operators are linear then (the path of section 4.14)"""
+        if len(ops) == 2 or ops[2] is None:
+            return None
+        try:
+            K = np.asarray(ops[2], dtype=np.float64)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"operators: a real array is expected for K of {name} ({err})")
+        if K.shape != (M, D, D):
+            raise ValueError(f"operators: K of {name} of shape ({M}, {D}, {D}) is expected, got {K.shape}")
+        if not np.isfinite(K).all():
+            raise ValueError(f"operators: non-finite entry in K of {name}")
+        for a in range(M):
+            if abs(K[a] - K[a].T).max() > 1.0e-12 * abs(K[a]).max():
+                raise ValueError(f"operators: K of operator {a} of {name} is not symmetric")
+        return torch.from_numpy(K.copy()) if K.any() else None
+
+    def _operator_side(self, name, ops):
+        """(c, m, K or None) of one side"""
+        c, m = self._operator_set(name, ops)
+        return c, m, self._operator_hessians(name, ops, int(c.shape[0]), self.dim)
+
+    @staticmethod
+    def _operators_key(A, B):
+        """what the prepared operators are cached by: the bytes of (c, m, K) of both sides, an absent (or all-zero) K as nothing"""
+        return tuple(b"" if t is None else t.numpy().tobytes() for t in tuple(A) + tuple(B))
+
     def _operators(self, bra, ket=None):
-        """validated operators A_a = cA_a + mA_a.x (``bra``) and B_a (``ket``; None: the bra's), their folded vectors
-        (hostmath.fold_linear_operators) and the ket-side factors g [n][M] of the initial points (sc_hk_opcorr_initial) on the device.
-        Cached per set of operators until the initial conditions change (_finish_state)."""
+        """validated operators A_a = cA_a + mA_a.x + 1/2 x^T KA_a x (``bra``) and B_a (``ket``; None: the bra's, K included), their
+        folded vectors and the ket-side factors g [n][M] of the initial points on the device.  Without a K on either side: the
+        affine forms of hostmath.fold_linear_operators and sc_hk_opcorr_initial (section 4.14); with one: the columns of
+        hostmath.fold_quadratic_operators and sc_hk_opquad_initial (section 4.16), "RA" and "RB" in the dict.  Cached per set of
+        operators until the initial conditions change (_finish_state)."""
         if not self._opcorr_ok:
             raise NotImplementedError(f"{type(self).__name__} has no operator correlation functions: its Gaussians have "
                                       "per-trajectory widths and another prefactor")
-        cA, mA = self._operator_set("bra", bra)
-        cB, mB = (cA, mA) if ket is None else self._operator_set("ket", ket)
+        cA, mA, KA = self._operator_side("bra", bra)
+        cB, mB, KB = (cA, mA, KA) if ket is None else self._operator_side("ket", ket)
         if cB.shape != cA.shape:
             raise ValueError(f"operators: bra and ket have to hold the same number of operators, got {cA.shape[0]} and {cB.shape[0]}")
-        key = tuple(t.numpy().tobytes() for t in (cA, mA, cB, mB))
+        key = self._operators_key((cA, mA, KA), (cB, mB, KB))
         hit = self._opcorr
         if hit is not None and hit["key"] == key:
             return hit
         M, dev = int(cA.shape[0]), self.device
-        uA, wA, kA = hostmath.fold_linear_operators(cA, mA, self._Gt, self._G0h, self._q0h, self._p0h, ket=False)
-        uB, wB, kB = hostmath.fold_linear_operators(cB, mB, self._Gi, self._G0h, self._q0h, self._p0h, ket=True)
-        bufs = [t.to(dev) for t in (uA, wA, kA, uB, wB, kB)]
         g = torch.empty((self.ntraj, M), dtype=C128, device=dev)
-        check(lib.sc_hk_opcorr_initial(ptr(self._zi_t), self.ntraj, self.dim, ptr(bufs[3]), ptr(bufs[4]), ptr(bufs[5]), M, ptr(g),
-                                       self._stream()))
+        host = (self._G0h, self._q0h, self._p0h)
+        if KA is None and KB is None:
+            uA, wA, kA = hostmath.fold_linear_operators(cA, mA, self._Gt, *host, ket=False)
+            uB, wB, kB = hostmath.fold_linear_operators(cB, mB, self._Gi, *host, ket=True)
+            bufs = [t.to(dev) for t in (uA, wA, kA, uB, wB, kB)]
+            check(lib.sc_hk_opcorr_initial(ptr(self._zi_t), self.ntraj, self.dim, ptr(bufs[3]), ptr(bufs[4]), ptr(bufs[5]), M, ptr(g),
+                                           self._stream()))
+            ranks = {}
+        else:
+            *colsA, RA = hostmath.fold_quadratic_operators(cA, mA, KA, self._Gt, *host, ket=False)
+            *colsB, RB = hostmath.fold_quadratic_operators(cB, mB, KB, self._Gi, *host, ket=True)
+            bufs = [t.to(dev) for t in colsA + colsB]      # (u, w, kappa, lambda) of the bra, then of the ket
+            check(lib.sc_hk_opquad_initial(ptr(self._zi_t), self.ntraj, self.dim, ptr(bufs[4]), ptr(bufs[5]), ptr(bufs[6]),
+                                           ptr(bufs[7]), M, RB, ptr(g), self._stream()))
+            ranks = {"RA": RA, "RB": RB}
         partials = torch.empty(max(int(lib.sc_hk_opcorr_rows(self.ntraj, M)) * M * 5, 1), dtype=F64, device=dev)
-        self._opcorr = {"key": key, "M": M, "bra": (cA.numpy(), mA.numpy()), "ket": (cB.numpy(), mB.numpy()), "bufs": bufs, "g": g,
-                        "partials": partials}
+        numpy_set = lambda c, m, K: (c.numpy(), m.numpy()) + (() if K is None else (K.numpy(),))
+        self._opcorr = {"key": key, "M": M, "bra": numpy_set(cA, mA, KA), "ket": numpy_set(cB, mB, KB), "bufs": bufs, "g": g,
+                        "partials": partials, **ranks}
         return self._opcorr
 
     def _prepare_operators(self, operators):
@@ -894,30 +938,39 @@ class HermanKlukPropagator(object):
         try:
             bra, ket = operators
         except (TypeError, ValueError):
-            raise ValueError("operators: (bra, ket) or bra, each a pair (c, m) of arrays (M,) and (M, D), is expected")
+            raise ValueError("operators: (bra, ket) or bra, each (c, m) or (c, m, K) of arrays (M,), (M, D) and (M, D, D), is expected")
         return self._operators(bra, ket)
 
     def _launch_opcorr(self, operators, out_ptr, state=None, cursor=None):
         """the (M, 5) operator-correlation sums of `state` (default: the current one) from the terms _cq the correlate kernel has
         exported for it, into the doubles at `out_ptr`, or into row *cursor of the (., M, 5) buffer there (the cursor is read, not
-        advanced); honours the discard mask"""
+        advanced); honours the discard mask.  sc_hk_opquad when the prepared operators carry columns ("RA"), else sc_hk_opcorr."""
         b = operators["bufs"]
+        st, cur = self._state if state is None else state, None if cursor is None else ptr(cursor)
+        if "RA" in operators:
+            with self._timed("hk_opquad"):
+                check(lib.sc_hk_opquad(st, ptr(self._cq), ptr(b[0]), ptr(b[1]), ptr(b[2]), ptr(b[3]), ptr(operators["g"]),
+                                       operators["M"], operators["RA"], ptr(self._kept), ptr(operators["partials"]), C_void(out_ptr),
+                                       cur, self._stream()))
+            return
         with self._timed("hk_opcorr"):
-            check(lib.sc_hk_opcorr(self._state if state is None else state, ptr(self._cq), ptr(b[0]), ptr(b[1]), ptr(b[2]),
-                                   ptr(operators["g"]), operators["M"], ptr(self._kept), ptr(operators["partials"]), C_void(out_ptr),
-                                   None if cursor is None else ptr(cursor), self._stream()))
+            check(lib.sc_hk_opcorr(st, ptr(self._cq), ptr(b[0]), ptr(b[1]), ptr(b[2]), ptr(operators["g"]), operators["M"],
+                                   ptr(self._kept), ptr(operators["partials"]), C_void(out_ptr), cur, self._stream()))
 
     def operator_correlation(self, bra, ket=None, energy0_es=0.0, standard_errors=False):
-        """X_a(t) = e^{i t E0/hbar} <phi_0| A_a e^{-iHt/hbar} B_a |phi_0> for the current step with M pairs of LINEAR operators
-        A_a = cA_a + mA_a.x, B_a = cB_a + mB_a.x (not in the reference): a complex ndarray (M,).
-        ``bra`` = (c, m), real arrays (M,) and (M, D) in the coordinates of q0; ``ket`` likewise, None = the operators of the bra.
+        """X_a(t) = e^{i t E0/hbar} <phi_0| A_a e^{-iHt/hbar} B_a |phi_0> for the current step with M pairs of linear or quadratic
+        operators A_a = cA_a + mA_a.x + 1/2 x^T KA_a x, B_a likewise (not in the reference; DESIGN.md sections 4.14, 4.16): a complex
+        ndarray (M,).  ``bra`` = (c, m) or (c, m, K), real arrays (M,), (M, D) and (M, D, D) in the coordinates of q0, every K_a the
+        symmetric Hessian of its operator (x_j x_k with j != k is K_jk = K_kj = 1, x_j^2 is K_jj = 2); K = None or all zeros: linear
+        operators, the same bits as (c, m).  ``ket`` likewise, None = the operators of the bra, K included.
         Every trajectory's C_auto term is multiplied by the closed-form Gaussian matrix elements of A at its current and of B at its
         initial phase-space point, the way ``ic_correlation`` treats the non-adiabatic coupling: linear in the ensemble like
         ``autocorrelation()``, which it equals for c = 1, m = 0.  With ``standard_errors`` the result is ``(X, sigma)``, sigma =
         sigma_Re + i sigma_Im per pair (``hostmath.standard_errors``).  Trajectories discarded by ``discard_nonsymplectic`` count as
         samples of value zero, N unchanged.  Synchronises; the state is not touched: the steps that follow give the bits they would
-        have given without the call.  ``ValueError`` for operators of the wrong shape, with non-finite entries, M = 0, or a vector
-        m outside the range of Gamma_0 + Gamma_t (bra) or Gamma_i + Gamma_0 (ket)."""
+        have given without the call.  ``ValueError`` for operators of the wrong shape, with non-finite entries, M = 0, a K that is
+        not symmetric, or a vector m or an eigenvector of K (eigenvalue above 1e-12 of the largest) outside the range of
+        Gamma_0 + Gamma_t (bra) or Gamma_i + Gamma_0 (ket)."""
         operators = self._operators(bra, ket)
         out = torch.zeros((1, operators["M"], 5), dtype=F64, device=self.device)
         slot = torch.zeros(8, dtype=F64, device=self.device)
@@ -972,9 +1025,10 @@ class HermanKlukPropagator(object):
         shapes C and k are the step-at-a-time loop's; everywhere else C, k, moments, blocks and the final state are the same bit for
         bit with or without targets.  ``use_graph=True`` with targets raises ``ValueError``.
 
-        Operator correlation functions: ``operators`` = (bra, ket) or bra alone, each a pair (c (M,), m (M, D)) of linear operators
-        c_a + m_a.x (``operator_correlation``): a ``sc_hk_opcorr`` launch follows every correlate launch, which then exports its
-        per-trajectory terms as it does for blocks.  Everything said of targets holds with ``opcorr`` (>= nt, M, 5) in the place of
+        Operator correlation functions: ``operators`` = (bra, ket) or bra alone, each (c (M,), m (M, D)) or (c, m, K (M, D, D)) of
+        operators c_a + m_a.x + 1/2 x^T K_a x, K_a the symmetric Hessian, None or zeros for linear operators
+        (``operator_correlation``): a ``sc_hk_opcorr`` launch (``sc_hk_opquad`` with a K) follows every correlate launch, which
+        then exports its per-trajectory terms as it does for blocks.  Everything said of targets holds with ``opcorr`` (>= nt, M, 5) in the place of
         ``cross``; ``X`` (nt, M) and ``sigma_X`` come after the cross outputs.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
