@@ -610,6 +610,37 @@ int sc_hk_opquad(const sc_state *st, const double *cq, const double *bra_u, cons
                  const double *bra_l, const double *g, int32_t M, int32_t RA, const uint8_t *kept, double *partials, double *out,
                  const int64_t *cursor, void *stream);
 
+/* Time-averaged Herman-Kluk spectra I_k(E) (Kaledin and Miller, separable prefactor) behind
+ * HermanKlukPropagator.time_average() and run(time_average=...) (not in the reference).  With O_ik the
+ * overlap of sc_hk_cross (bra: trajectory i, width Gamma_t; ket: reference state k, width Gamma_0; La, Lb, Ct, diag, fac,
+ * operands and the rows refs [K][5 D] exactly as sc_hk_cross takes its targets):
+ *   g_ik(t_s) = conj(O_ik) u_i,   u_i = c_i / |c_i| e^{i S_i/hbar},   c_i = sgn_i sqrt(c2_i)   (u_i = 0 where c_i = 0),
+ *   A_ik(E_e) = dt sum_s g_ik(t_s) exp(i E_e t_s / hbar),   t_s = t_a + s dt (a product, s an integer),
+ *   y_ik(e)   = |A_ik(E_e)|^2 / (2 pi hbar mc_norm probi_i),   out[k][e] = (sum_i y_ik(e), sum_i y_ik(e)^2);
+ * the spectrum over a window of ns steps, T = ns dt, is I_k(E_e) = out[k][e][0] / T, its second sum out[k][e][1] / T^2.
+ * All buffers are the caller's: G [TB][n K] complex (row index i K + k), W [TB][NE] complex, A [n K][NE] complex (zeroed by the
+ * caller before the first column), TB = sc_hk_ta_block().
+ *   sc_hk_ta_terms       column `column` (0 ... TB - 1) of G from the state `st`, which may be a view of an intermediate state
+ *                        (sc_hk_step_multi, sc_hk_step_visit): only n, dim, qp, act, c2, sgn are read.  kept: uint8 [n] or NULL; a
+ *                        trajectory with kept == 0 gets exact zeros and its state is not read.  One launch (two for dense widths).
+ *   sc_hk_ta_accumulate  A += sum_{c < count} G[c] (x) W[c],  W[c][e] = dt exp(i E_e (t_a + (s0 + c) dt) / hbar): column c of G holds
+ *                        step s0 + c of the window.  Every W is one sincos of the product E_e t_s -- no recurrence; the columns
+ *                        are added to the stored A in ascending c, so the bits of A do not depend on where the blocks of columns
+ *                        were cut.  Two launches; G and W are free again when they have run.
+ *   sc_hk_ta_finish      out [K][NE][2] from A; partials: scratch of sc_hk_ta_finish_rows(n) * K * NE * 2 doubles.  A trajectory
+ *                        with kept == 0 counts as y = 0 (its rows of A are not read).  Two launches; no atomics, the order of
+ *                        every sum is a function of (n, K, NE) alone: the same bits in every call.  A is not changed.
+ * D <= 512, 1 <= K <= 64, 1 <= NE <= 65535, n <= 64 * 65535; beyond: SC_ERR_UNSUPPORTED.  A null pointer, K < 1, NE < 1, a column
+ * outside 0 ... TB - 1 or a count outside 1 ... TB: SC_ERR_BAD_ARGUMENT. */
+int32_t sc_hk_ta_block(void);
+int sc_hk_ta_terms(const sc_state *st, const double *La, const double *Lb, const double *Ct, int32_t diag, double fac,
+                   const double *refs, int32_t K, const uint8_t *kept, double *operands, double *G, int32_t column, void *stream);
+int sc_hk_ta_accumulate(const double *G, int64_t n, int32_t K, int32_t count, const double *energies, int32_t NE, double t_a,
+                        double dt, int64_t s0, double *W, double *A, void *stream);
+int64_t sc_hk_ta_finish_rows(int64_t n);
+int sc_hk_ta_finish(const double *A, int64_t n, int32_t K, int32_t NE, const double *probi, double mc_norm, const uint8_t *kept,
+                    double *partials, double *out, void *stream);
+
 /* Frozen-Gaussian wavefunction on a spatial grid behind HermanKlukPropagator.wavefunction() (propagators.py:252-292,
  * 688-732):  phi[k] = fac sum_n v_n exp(-1/2 |Lx_k - Lq_n|^2 + i (p_n.x_k - pq_n)),  L = Gamma_t^(1/2).
  * LqT, PT [D][n] (trajectory index fastest), pq [n], v [n] complex, Lx, X [nx][D], phi [nx] complex. */

@@ -195,6 +195,14 @@ SIGNATURES = {
                                        C.c_int32, c_double_p, C.c_void_p]),
     "sc_hk_opquad": (C.c_int, [P(sc_state), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32,
                                C.c_int32, C.c_void_p, c_double_p, c_double_p, C.c_void_p, C.c_void_p]),
+    "sc_hk_ta_block": (C.c_int32, []),
+    "sc_hk_ta_terms": (C.c_int, [P(sc_state), c_double_p, c_double_p, c_double_p, C.c_int32, C.c_double, c_double_p, C.c_int32,
+                                 C.c_void_p, c_double_p, c_double_p, C.c_int32, C.c_void_p]),
+    "sc_hk_ta_accumulate": (C.c_int, [c_double_p, C.c_int64, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_double, C.c_double,
+                                      C.c_int64, c_double_p, c_double_p, C.c_void_p]),
+    "sc_hk_ta_finish_rows": (C.c_int64, [C.c_int64]),
+    "sc_hk_ta_finish": (C.c_int, [c_double_p, C.c_int64, C.c_int32, C.c_int32, c_double_p, C.c_double, C.c_void_p, c_double_p,
+                                  c_double_p, C.c_void_p]),
     "sc_hk_step_diag": (C.c_int, [P(sc_potential), P(sc_state), P(sc_hk_consts), c_double_p, C.c_double, C.c_int32,
                                   c_double_p, C.c_void_p]),
     "sc_grid_sum": (C.c_int, [c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int32, c_double_p,

@@ -15,21 +15,14 @@
 // cross_operands_kernel (dense widths only): the trajectory rows into caller-owned scratch, three D x D mat-vecs per trajectory,
 //   one trajectory per wavefront pass.  Diagonal widths need no pre-pass: the tile kernel scales q and p while it stages them.
 // cross_tile_kernel: the tile mapping, the column reduction and the reduction over the bands of sc_rows5.h, the columns being the
-//   targets.  Per pair and d two FMAs for Re E and one for Im E; then one c_exp per pair and the product with v_i (formed once per
+//   targets.  The staging and the d-loop are cross_tile_exponents of sc_cross_tile.h, shared with the terms kernel of the
+//   time-averaged spectra (sc_timeavg.hip).  Per pair and d two FMAs for Re E and one for Im E; then one c_exp per pair and the product with v_i (formed once per
 //   trajectory by the first 64 threads exactly as hk_correlate_kernel forms it).
 // Discarded trajectories (`kept`) and the rows beyond n are staged as zero operands with v = 0: they add exact zeros and never
 // meet a non-finite value.
-#include "sc_rows5.h"
+#include "sc_cross_tile.h"
 
 namespace {
-
-
-// the LDS of the tile kernel: the d-chunk of both operand sets, reused for the column reduction
-struct alignas(16) CrossStage {
-    typedef double chunk[R5_CHUNK][R5_ROW];
-    chunk ta, tb, tq, tc;      // trajectories: La q, Lb p, q, C p
-    chunk ka, kb, kq, kg;      // targets: La q_k, Lb p_k, q_k, C p_k - p_k
-};
 
 struct CrossArgs {
     sc_state st;
@@ -50,7 +43,6 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
     __shared__ int live[R5_TILE];
     static_assert(sizeof(CrossStage) >= sizeof(double) * R5_REDUCE_DOUBLES, "the column reduction reuses the staging buffers");
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-    const int D = A.st.dim;
     const int64_t n = A.st.n, i0 = (int64_t)blockIdx.y * R5_TILE;
     const int k0 = blockIdx.x * R5_TILE;
     const int iv = (int)min((int64_t)R5_TILE, n - i0), kv = min(R5_TILE, A.K - k0);      // valid rows / targets of the tile
@@ -69,51 +61,7 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
         live[tid] = in;
     }
     double re[4][4], im[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) { re[a][b] = 0.0; im[a][b] = 0.0; }
-    for (int d0 = 0; d0 < D; d0 += R5_CHUNK) {
-        __syncthreads();                                   // live[] is written; the last readers of the chunk before are done
-        for (int e = tid; e < R5_CHUNK * R5_TILE; e += 256) {
-            const int r = e / R5_CHUNK, k = e - r * R5_CHUNK, d = d0 + k;      // row r of the tile, column k of the chunk
-            double a = 0.0, b = 0.0, q = 0.0, c = 0.0;
-            if (d < D && live[r]) {
-                if (DIAG) {
-                    const double *qp = A.st.qp + (i0 + r) * 2 * D;
-                    const double p = qp[D + d];
-                    q = qp[d];
-                    a = A.La[d] * q; b = A.Lb[d] * p; c = A.Cm[d] * p;
-                } else {
-                    const double *row = A.operands + (i0 + r) * 4 * D;
-                    a = row[d]; b = row[D + d]; q = row[2 * D + d]; c = row[3 * D + d];
-                }
-            }
-            S.ta[k][r] = a; S.tb[k][r] = b; S.tq[k][r] = q; S.tc[k][r] = c;
-            a = 0.0; b = 0.0; q = 0.0; c = 0.0;
-            if (d < D && r < kv) {
-                const double *row = A.targets + (size_t)(k0 + r) * 5 * D;
-                a = row[d]; b = row[D + d]; q = row[2 * D + d]; c = row[3 * D + d] - row[4 * D + d];
-            }
-            S.ka[k][r] = a; S.kb[k][r] = b; S.kq[k][r] = q; S.kg[k][r] = c;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int k = 0; k < R5_CHUNK; ++k) {
-            double xa[4], xb[4], xq[4], xc[4], ya[4], yb[4], yq[4], yg[4];
-            load4(&S.ta[k][4 * ti], xa); load4(&S.tb[k][4 * ti], xb); load4(&S.tq[k][4 * ti], xq); load4(&S.tc[k][4 * ti], xc);
-            load4(&S.ka[k][4 * tj], ya); load4(&S.kb[k][4 * tj], yb); load4(&S.kq[k][4 * tj], yq); load4(&S.kg[k][4 * tj], yg);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const double da = ya[b] - xa[a], db = yb[b] - xb[a], dq = yq[b] - xq[a];
-                    re[a][b] = fma(da, da, re[a][b]);
-                    re[a][b] = fma(db, db, re[a][b]);
-                    im[a][b] = fma(dq, yg[b] - xc[a], im[a][b]);
-                }
-        }
-    }
+    cross_tile_exponents<DIAG>(S, live, A.st, A.La, A.Lb, A.Cm, A.operands, A.targets, i0, k0, kv, tid, ti, tj, re, im);
     // x_ik = conj(fac exp(E)) v_i; the thread's four trajectories are added per target in registers
     double sum[4][5];
 #pragma unroll
@@ -122,7 +70,7 @@ __global__ __launch_bounds__(256) void cross_tile_kernel(CrossArgs A) {
         for (int c = 0; c < 5; ++c) sum[b][c] = 0.0;
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            const cplx o = c_scale(c_exp(c_make(-0.5 * re[a][b], -im[a][b] * (1.0 / SC_HBAR))), A.fac);
+            const cplx o = cross_tile_overlap_conj(re[a][b], im[a][b], A.fac);
             const cplx x = c_mul(o, vs[4 * ti + a]);
             rows5_add(sum[b], x);
         }
@@ -157,6 +105,14 @@ __global__ __launch_bounds__(256) void cross_operands_kernel(sc_state st, const 
 
 }  // namespace
 
+int sc_cross_operands(const char *who, const sc_state *st, const double *La, const double *Lb, const double *Ct, double *operands,
+                      hipStream_t stream) {
+    const int64_t blocks = (st->n + 3) / 4;
+    hipLaunchKernelGGL(cross_operands_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256),
+                       (size_t)4 * 2 * st->dim * sizeof(double), stream, *st, La, Lb, Ct, operands);
+    return sc_check_launch(who);
+}
+
 extern "C" int64_t sc_hk_cross_rows(int64_t n, int64_t K) { return sc_rows5_bands(n, K); }
 
 extern "C" int sc_hk_cross(const sc_state *st, const double *La, const double *Lb, const double *Ct, int32_t diag, double fac,
@@ -172,10 +128,7 @@ extern "C" int sc_hk_cross(const sc_state *st, const double *La, const double *L
     hipStream_t s = (hipStream_t)stream;
     if (bands > 0) {
         if (!diag) {
-            const int64_t blocks = (st->n + 3) / 4;
-            hipLaunchKernelGGL(cross_operands_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256),
-                               (size_t)4 * 2 * st->dim * sizeof(double), s, *st, La, Lb, Ct, operands);
-            rc = sc_check_launch("sc_hk_cross (operands)");
+            rc = sc_cross_operands("sc_hk_cross (operands)", st, La, Lb, Ct, operands, s);
             if (rc != SC_OK) return rc;
         }
         CrossArgs a{*st, La, Lb, Ct, operands, targets, K, fac, mc_norm, vi, probi, kept, partials};

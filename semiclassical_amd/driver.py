@@ -138,11 +138,12 @@ class CorrelationStore(object):
     def __init__(self, path):
         self.path = path
 
-    def start(self, task, propagator_name, times, setup, cross_targets=None, operators=None):
+    def start(self, task, propagator_name, times, setup, cross_targets=None, operators=None, time_average=None):
         """``cross_targets``: (q, p) of the task's "cross_correlation_targets", or None: a file that is added to has to hold
         exactly these (ConfigurationError otherwise, before any trajectory runs).  ``operators``: (bra_c, bra_m, ket_c, ket_m) of
         the task's "operator_correlation", or None: the same rule; (..., bra_k, ket_k) with Hessians (M, D, D), which a file
-        without them holds as zeros."""
+        without them holds as zeros.  ``time_average``: (energies, q, p, window) of the task's "time_averaged_spectrum", or None:
+        the same rule for the stored ``ta_energies``, ``ta_references_q``, ``ta_references_p`` and ``ta_window``."""
         fresh = task['results'].get('overwrite', True) is True or not os.path.exists(self.path)
         if fresh:
             nt = len(times)
@@ -160,6 +161,7 @@ class CorrelationStore(object):
         if previous['trajectories'] > 0:
             for fam, idents in zip(ROW_FAMILIES, (cross_targets, operators)):
                 self._check_family(fam, previous, idents)
+            self._check_time_average(previous, time_average)
 
     CROSS_KEYS, OPERATOR_KEYS = (tuple(fam.prefix + key for key in fam.idents) + (fam.stored,) for fam in ROW_FAMILIES)
 
@@ -185,6 +187,23 @@ class CorrelationStore(object):
                 f"{self.path} holds {fam.what} with other {fam.noun} than this task's "
                 f"(\"{fam.task_key}\"): they are different estimators and cannot be pooled")
 
+    TA_IDENT_KEYS = ('ta_energies', 'ta_references_q', 'ta_references_p', 'ta_window')
+    TA_ERROR_KEYS = ('ta_spectrum_second_moment', 'ta_spectrum_error')
+
+    def _check_time_average(self, stored, idents):
+        """the stored time-averaged spectrum belongs to exactly the energies, reference states and window (energies, q, p, T) of
+        the task or batch (None: it has none)"""
+        have = 'ta_energies' in stored
+        if have != (idents is not None):
+            raise ConfigurationError(
+                f"{self.path} holds {'a' if have else 'no'} time-averaged spectrum, this task "
+                f"{'has no' if have else 'has'} \"time_averaged_spectrum\": they cannot be pooled")
+        if have and not all(np.array_equal(stored[key], np.asarray(new, dtype=np.float64)) for key, new in zip(self.TA_IDENT_KEYS, idents)):
+            raise ConfigurationError(
+                f"{self.path} holds a time-averaged spectrum with other energies, reference states or another window than this "
+                "task's (\"time_averaged_spectrum\", \"num_steps\", \"time_step_fs\"): they are different estimators and cannot "
+                "be pooled")
+
     ERROR_KEYS = ('autocorrelation_error', 'ic_correlation_error', 'autocorrelation_second_moment', 'ic_correlation_second_moment')
 
     BLOCK_KEYS = ('autocorrelation_blocks', 'ic_correlation_blocks', 'block_trajectories')
@@ -193,7 +212,7 @@ class CorrelationStore(object):
                           'symplecticity_tolerance', 'symplecticity_kept', 'symplecticity_discard')
 
     def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None, cross=None,
-                  operators=None):
+                  operators=None, time_average=None):
         """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
         per-sample second moments (rows (S_rr, S_ii, S_ri) times the batch size, phase applied) of the batch, folded the same
         way; the standard errors of the pooled means follow from them.  Files and batches that do not both carry them lose
@@ -221,7 +240,13 @@ class CorrelationStore(object):
         ``operator_bra_k``, ``operator_ket_k`` only when given, absent = zeros), 'correlation' (nt, M) and, with standard errors,
         'second_moment' (nt, M, 3).  The file then holds
         ``operator_bra_c``, ``operator_bra_m``, ``operator_ket_c``, ``operator_ket_m``, ``operator_correlation`` and, by the same
-        keep-or-drop rule, ``operator_correlation_second_moment`` and ``operator_correlation_error``; everything as for ``cross``."""
+        keep-or-drop rule, ``operator_correlation_second_moment`` and ``operator_correlation_error``; everything as for ``cross``.
+        ``time_average``: the record of the batch's time-averaged spectrum: 'energies' (NE,), 'q', 'p'
+        (K, D) the reference states, 'window' T, 'spectrum' (K, NE) and, with standard errors, 'second_moment' (K, NE), the
+        per-sample second moment N sum_i y_i^2.  The file then holds ``ta_energies``, ``ta_references_q``, ``ta_references_p``,
+        ``ta_window``, ``ta_spectrum`` (pooled with the weights of ``autocorrelation``) and, by the same keep-or-drop rule,
+        ``ta_spectrum_second_moment`` and ``ta_spectrum_error``.  Other stored energies, reference states or window (or a
+        spectrum on one side only) are refused (ConfigurationError)."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
@@ -230,6 +255,8 @@ class CorrelationStore(object):
             for fam, record in records:
                 self._check_family(fam, stored, None if record is None else
                                    tuple(record[key] for key in fam.idents + fam.optional if key in record))
+            self._check_time_average(stored, None if time_average is None else
+                                     tuple(time_average[key] for key in ('energies', 'q', 'p', 'window')))
         discarding = symplecticity is not None and bool(symplecticity.get('discard', False))
         if done > 0:
             was_discarding = bool(stored.get('symplecticity_discard', False))
@@ -319,6 +346,26 @@ class CorrelationStore(object):
                     stored.pop(drop, None)
             for key in fam.stale:            # computed from the old correlation functions: stale now
                 stored.pop(key, None)
+        if time_average is not None:
+            pool = done > 0
+            new = np.asarray(time_average['spectrum'], dtype=np.float64)
+            for key, name in zip(self.TA_IDENT_KEYS, ('energies', 'q', 'p', 'window')):
+                stored[key] = np.asarray(time_average[name], dtype=np.float64)
+            stored['ta_spectrum'] = (ntraj * new + done * stored['ta_spectrum']) / total if pool else new
+            moment = time_average.get('second_moment', None)
+            key = 'ta_spectrum_second_moment'
+            have_moment = key in stored
+            if moment is not None and (have_moment or not pool):
+                stored[key] = (ntraj * moment + done * stored[key]) / total if pool else np.asarray(moment, dtype=np.float64)
+                m3 = np.zeros(stored[key].shape + (3,))
+                m3[..., 0] = stored[key] / total
+                stored['ta_spectrum_error'] = hostmath.standard_errors(stored['ta_spectrum'], m3, total).real
+            elif have_moment or moment is not None:
+                logger.warning("standard errors of the time-averaged spectrum dropped from %s: %s", self.path,
+                               "the stored trajectories have no second moments" if moment is not None else
+                               "this task does not compute them (\"standard_errors\": true)")
+                for drop in self.TA_ERROR_KEYS:
+                    stored.pop(drop, None)
         stored.pop('ic_rate', None)          # a rate computed from the old correlation function is stale now
         stored.pop('ic_rate_error', None)
         logger.info(f"<phi(0)|phi(0)>= {stored['autocorrelation'][0]}")
@@ -378,7 +425,7 @@ def _check_symplecticity(propagator, step, time, tolerance, log, discard=False):
 
 def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, across_ranks=False, log=True, errors=False,
                     error_blocks=0, symplecticity_every=0, symplecticity_tolerance=None, discard_nonsymplectic=False, targets=None,
-                    operators=None):
+                    operators=None, time_average=None):
     """C_auto(t), k_ic(t) of one batch of trajectories: the device loop leaves the raw per-step sums in a device buffer,
     ``flush`` (None on a single rank) adds the buffers of all ranks -- ONE all-reduce per batch, SURVEY 8e -- and the host
     applies the dynamical phase.  ``norm_every`` > 0 logs the wavefunction norm (the O(n^2) convergence diagnostic of
@@ -401,11 +448,17 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     ``operators`` = (bra_c, bra_m, ket_c, ket_m) or (..., bra_k, ket_k) with the Hessians (M, D, D) of quadratic operators: the
     operator correlation functions (propagator.run(operators=...)); the result then ends with yet another element, the record
     {'bra_c', 'bra_m', 'ket_c', 'ket_m', 'correlation' (nt, M)} (and 'bra_k', 'ket_k' when given) and, with ``errors``,
-    'second_moment' (nt, M, 3).  Single rank only, for the same reason."""
+    'second_moment' (nt, M, 3).  Single rank only, for the same reason.
+    ``time_average`` = (energies, q, p), arrays (NE,), (K, D), (K, D): the time-averaged spectrum of these reference states over
+    the nt steps (propagator.time_average; ONE accumulator across all pieces of the loop, so the cuts change no bit of it); the
+    result then ends with a last element, the record {'energies', 'q', 'p', 'window', 'spectrum' (K, NE)} and, with ``errors``,
+    'second_moment' (K, NE).  Single rank only."""
     given = [(fam, idents) for fam, idents in zip(ROW_FAMILIES, (targets, operators)) if idents is not None]
     for fam, _ in given:
         if flush is not None:
             raise ValueError(f"{fam.noun} are not available with more than one rank: the flush buffer does not carry the {fam.rows} rows")
+    if time_average is not None and flush is not None:
+        raise ValueError("a time-averaged spectrum is not available with more than one rank: the flush buffer does not carry its sums")
     if discard_nonsymplectic and not (symplecticity_every > 0 and symplecticity_tolerance is not None):
         raise ValueError("discard_nonsymplectic needs symplecticity_every > 0 and a symplecticity_tolerance")
     slots = torch.zeros((nt, 5), dtype=torch.float64, device=propagator.device)
@@ -420,6 +473,13 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     if error_blocks:
         blocks = torch.zeros((nt, error_blocks, 4), dtype=torch.float64, device=propagator.device)
         counts = torch.from_numpy(propagator.block_counts(propagator.ntraj, error_blocks)).to(torch.float64)
+    accumulator = None
+    if time_average is not None:
+        energies, ref_q, ref_p = time_average
+        accumulator = propagator.time_average(energies, dt, None if ref_q is None else (ref_q, ref_p))
+        extra_ta = {"time_average": accumulator}
+    else:
+        extra_ta = {}
     # the device loop is cut at the multiples of either diagnostic's period
     cuts = sorted({0} | {s for every in (norm_every, symplecticity_every) if every > 0 for s in range(0, nt, every)}) if nt > 0 else []
     pieces, checks = [], []
@@ -438,7 +498,7 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
             extra.update({fam.noun: fam.as_run(idents), fam.buffer: buf[first:first + count]})
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
                        moments=None if moments is None else moments[first:first + count],
-                       blocks=None if blocks is None else blocks[first:first + count], **extra)
+                       blocks=None if blocks is None else blocks[first:first + count], **extra, **extra_ta)
     if symplecticity_every > 0 and pieces:
         # The clock of a piece is t0 + (dt + dt + ...), which differs from the uncut loop's 0 + dt + dt + ... in the last bits, and
         # with it the dynamical phase.  The check must leave every bit of the correlation functions as it is: the phase is taken
@@ -471,6 +531,14 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         if errors:
             record['second_moment'] = propagator._ntraj_norm * m3
         tail = tail + (record,)
+    if accumulator is not None:
+        raw = accumulator.raw_sums()
+        T, n = accumulator.window, propagator._ntraj_norm
+        record = {'energies': accumulator.energies, 'q': accumulator.references[0], 'p': accumulator.references[1], 'window': T,
+                  'spectrum': raw[..., 0] / T}
+        if errors:
+            record['second_moment'] = n * raw[..., 1] / T ** 2
+        tail = tail + (record,)
     if moments is None:
         parts = [propagator.finalize_slots(slots[first:first + count], t0, dt, setup.zero_point_energy)
                  for first, count, t0 in pieces]
@@ -495,6 +563,30 @@ def _load_targets(path, dim):
     if not (np.isfinite(q).all() and np.isfinite(p).all()):
         raise ConfigurationError(f"'cross_correlation_targets': non-finite entry in {path}")
     return q, p
+
+
+def _load_time_average(path, setup):
+    """(energies, q, p), float64 (NE,), (K, D), (K, D), of a "time_averaged_spectrum" file: the array energies (Hartree) and
+    optionally the reference states q and p; without them the one state (q0, p0) of the initial wavepacket"""
+    dim = int(setup.q0.shape[0])
+    try:
+        with np.load(path, allow_pickle=False) as handle:
+            energies = np.array(handle['energies'], dtype=np.float64)
+            if ('q' in handle) != ('p' in handle):
+                raise KeyError("q and p come together")
+            q, p = ((np.array(handle[key], dtype=np.float64) for key in ('q', 'p')) if 'q' in handle else
+                    (setup.q0.numpy()[None, :].copy(), setup.p0.numpy()[None, :].copy()))
+    except (OSError, KeyError, ValueError) as err:
+        raise ConfigurationError(f"'time_averaged_spectrum': {path} should be an npz file with an array energies (and q, p) ({err})")
+    if energies.ndim != 1 or energies.shape[0] == 0 or not np.isfinite(energies).all():
+        raise ConfigurationError(f"'time_averaged_spectrum': finite energies of shape (NE,) with NE > 0 are expected in {path}, got "
+                                 f"shape {energies.shape}")
+    if q.ndim != 2 or q.shape != p.shape or q.shape[0] == 0 or q.shape[0] > 64 or q.shape[1] != dim:
+        raise ConfigurationError(f"'time_averaged_spectrum': q and p of shape (K, {dim}) with 0 < K <= 64 are expected in {path}, got "
+                                 f"{q.shape} and {p.shape}")
+    if not (np.isfinite(q).all() and np.isfinite(p).all()):
+        raise ConfigurationError(f"'time_averaged_spectrum': non-finite entry in {path}")
+    return energies, q, p
 
 
 def _load_operators(path, dim):
@@ -578,7 +670,17 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         if file is not None and world > 1:
             raise ConfigurationError(f"'{fam.task_key}' is not available with more than one rank: the flush buffer does not "
                                      f"carry the {fam.rows} rows")
+    # "time_averaged_spectrum": the time-averaged HK spectrum I(E) over the whole run, an npz file with the array
+    # energies (NE,), Hartree, and optionally the reference states q and p (K, D)
+    ta_file = task.get('time_averaged_spectrum', None)
+    if ta_file is not None and task.get('propagator', 'HK') == "WM":
+        raise ConfigurationError("'time_averaged_spectrum' is not available with the WM propagator: its Gaussians have "
+                                 "per-trajectory widths and another prefactor")
+    if ta_file is not None and world > 1:
+        raise ConfigurationError("'time_averaged_spectrum' is not available with more than one rank: the flush buffer does not "
+                                 "carry its sums")
     setup = build_problem(task)
+    time_average = None if ta_file is None else _load_time_average(ta_file, setup)
     targets = None if targets_file is None else _load_targets(targets_file, int(setup.q0.shape[0]))
     operators = None if operators_file is None else _load_operators(operators_file, int(setup.q0.shape[0]))
 
@@ -597,7 +699,8 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
 
     store = CorrelationStore(task['results'].get('correlations', 'correlations.npz'))
     if writer:
-        store.start(task, task.get('propagator', 'HK'), times, setup, cross_targets=targets, operators=operators)
+        store.start(task, task.get('propagator', 'HK'), times, setup, cross_targets=targets, operators=operators,
+                    time_average=None if time_average is None else time_average + (nt * dt,))
 
     seed = task.get('manual_seed', None)
     if seed is not None:
@@ -645,8 +748,10 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         out = propagate_batch(propagator, setup, dt, nt, times, norm_every=task.get('calc_norm_every', 0), flush=flush,
                               across_ranks=world > 1 and comm is None, log=writer, errors=errors, error_blocks=error_blocks,
                               symplecticity_every=check_every, symplecticity_tolerance=tolerance, discard_nonsymplectic=discard,
-                              targets=targets, operators=operators)
+                              targets=targets, operators=operators, time_average=time_average)
         records = {}
+        if time_average is not None:
+            out, records['time_average'] = out[:-1], out[-1]
         for fam, idents in reversed(list(zip(ROW_FAMILIES, (targets, operators)))):
             if idents is not None:
                 out, records[fam.noun] = out[:-1], out[-1]
@@ -659,7 +764,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         if writer:
             store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:4] if errors else None,
                             blocks=out[-1] if error_blocks else None, symplecticity=checks, cross=records.get('targets'),
-                            operators=records.get('operators'))
+                            operators=records.get('operators'), time_average=records.get('time_average'))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

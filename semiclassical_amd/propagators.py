@@ -28,7 +28,7 @@ from ._lib import (lib, check, ptr, sc_state, sc_hk_consts, sc_overlap_consts, s
                    sc_dense_scratch, sc_multi_scratch)
 from .units import hbar
 
-__all__ = ['HermanKlukPropagator', 'WaltonManolopoulosPropagator']
+__all__ = ['HermanKlukPropagator', 'WaltonManolopoulosPropagator', 'TimeAverageAccumulator']
 
 logger = logging.getLogger(__name__)
 
@@ -90,6 +90,9 @@ _ROW_FAMILIES = (
     _RowFamily("operators", "opcorr", "M", "operator-correlation", "_prepare_operators", "_launch_opcorr", True),
 )
 _OPERATOR_ROWS = _ROW_FAMILIES[1]
+# The hook of a time-average accumulator in the same place: a terms launch after every correlate launch.
+# It fills no row (field None) and is not an argument family of run(): its "prepared dict" is the accumulator itself.
+_TIME_AVERAGE = _RowFamily("time_average", None, None, "time-average terms", None, "_launch_ta_terms", False)
 
 
 class _StepRows(object):
@@ -693,7 +696,7 @@ class HermanKlukPropagator(object):
                                         ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
                                         ptr(self._mpart) if in_kernel else None, s))
         for fam, prepared in families:
-            getattr(self, fam.launch)(prepared, getattr(row, fam.field), state=state, cursor=cursor)
+            getattr(self, fam.launch)(prepared, None if fam.field is None else getattr(row, fam.field), state=state, cursor=cursor)
         if masked:
             assert cursor is None
             self._masked_sums(nac is not None, row)
@@ -833,6 +836,39 @@ class HermanKlukPropagator(object):
         the error algebra of finalize_moments"""
         C, m3 = HermanKlukPropagator.phased_cross(cross, t0, dt, energy0_es)
         return C, hostmath.standard_errors(C, m3, ntraj_norm)
+
+    # ---- time-averaged spectra (not in the reference; DESIGN.md section 4.17) ----
+    def time_average(self, energies, dt, references=None, max_bytes=2 ** 32):
+        """An accumulator of the time-averaged Herman-Kluk spectrum (Kaledin and Miller, separable prefactor; DESIGN.md section
+        4.17) of the reference states |q_k, p_k, Gamma_0>, ``references`` = (Q, P), arrays (K, D), K <= 64; None: the one state
+        (q0, p0).  ``energies``: the E_e (NE,), Hartree.  Over a window of ns steps of ``dt`` that starts at the current time t_a,
+
+            I_k(E) = sum_i |dt sum_s e^{i E t_s/hbar} <chi_k|q_i(t_s) p_i(t_s)> e^{i S_i/hbar} c_i/|c_i| |^2 / (2 pi hbar T mc_norm P_i),
+
+        t_s = t_a + s dt, T = ns dt: every trajectory adds a non-negative number, the peaks sit at the eigenvalues of the surface
+        the trajectories run on with the weights |<chi_k|n>|^2.  Fill it with ``run(..., time_average=acc)`` or, step by step,
+        ``acc.add()``; read it with ``acc.spectrum()``.  It owns 16 n K NE bytes on the device: ``ValueError`` (naming the size)
+        above ``max_bytes``, for empty or non-finite energies, references of the wrong shape or K > 64."""
+        if not self._cross_ok:
+            raise NotImplementedError(f"{type(self).__name__} has no time-averaged spectra: its Gaussians have per-trajectory "
+                                      "widths and another prefactor")
+        return TimeAverageAccumulator(self, energies, dt, references, max_bytes)
+
+    def _launch_ta_terms(self, acc, out_ptr=None, state=None, cursor=None):
+        """one column of the accumulator's terms from `state` (default: the current one); honours the discard mask"""
+        assert cursor is None
+        acc._append(state)
+
+    @staticmethod
+    def finalize_time_average(raw, T, ntraj_norm):
+        """(I, sigma), real (K, NE): the time-averaged spectrum over a window of length T and its Monte-Carlo standard error from
+        the raw sums (K, NE, 2) of ``TimeAverageAccumulator.raw_sums()`` (added over batches of one N and over ranks when
+        sharded): I = raw[..., 0] / T, sigma = sqrt(max(N raw[..., 1] / T^2 - I^2, 0) / (N - 1)) (``hostmath.standard_errors``)"""
+        raw = raw.detach().cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw, dtype=np.float64)
+        I = raw[..., 0] / T
+        m3 = np.zeros(I.shape + (3,))
+        m3[..., 0] = raw[..., 1] / T ** 2
+        return I, hostmath.standard_errors(I, m3, ntraj_norm).real
 
     # ---- correlation functions with linear and quadratic operators (not in the reference; DESIGN.md sections 4.14, 4.16) ----
     @staticmethod
@@ -978,7 +1014,7 @@ class HermanKlukPropagator(object):
         return self._current_five_sums(out, energy0_es, standard_errors)
 
     def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
-            targets=None, cross=None, operators=None, opcorr=None):
+            targets=None, cross=None, operators=None, opcorr=None, time_average=None):
         """The caller loop of cli.py:401-436 on the device: ``nt`` times (C_auto, k_ic, step), no host sync.
 
         Returns ``(autocorrelation[nt], ic_correlation[nt])`` as complex NumPy arrays.  With ``slots`` (a
@@ -1030,6 +1066,14 @@ class HermanKlukPropagator(object):
         (``operator_correlation``): a ``sc_hk_opcorr`` launch (``sc_hk_opquad`` with a K) follows every correlate launch, which
         then exports its per-trajectory terms as it does for blocks.  Everything said of targets holds with ``opcorr`` (>= nt, M, 5) in the place of
         ``cross``; ``X`` (nt, M) and ``sigma_X`` come after the cross outputs.
+
+        Time-averaged spectra: ``time_average`` = an accumulator of ``time_average()``: a ``sc_hk_ta_terms`` launch follows every
+        correlate launch, the intermediate states of pairs and visits included, and every TB-th column one ``sc_hk_ta_accumulate``
+        launch.  Columns that do not fill a block stay pending in the accumulator across calls (``spectrum()`` / ``raw_sums()``
+        flush them): a loop cut into several ``run()`` calls leaves the bits of the uncut loop.  The return value does not change.
+        As with targets the loop never runs as the one-launch kernel; everywhere else every output and the final state are the
+        same bit for bit with or without the accumulator.  ``ValueError`` for a ``dt`` other than the accumulator's and for
+        ``use_graph=True``.
         """
         assert self.dim == potential.dimensions(), "potential has wrong dimensions"
         if use_graph and self._kept is not None:
@@ -1053,6 +1097,14 @@ class HermanKlukPropagator(object):
             bufs[fam.field] = torch.zeros((nt, counts[fam.letter], 5), dtype=F64, device=self.device) if buf is None else buf
             families.append((fam, prepared))
         dt = float(dt)
+        hooks = list(families)                                     # what follows every correlate launch
+        if time_average is not None:
+            if use_graph:
+                raise ValueError("use_graph=True is not available with time_average: the graph replay has no time-average terms launch")
+            if not isinstance(time_average, TimeAverageAccumulator):
+                raise ValueError("time_average: an accumulator of HermanKlukPropagator.time_average() is expected")
+            time_average._check_run(self, dt)
+            hooks.append((_TIME_AVERAGE, time_average))
         self._remember_nac(potential)
         own = slots is None
         if standard_errors and not own:
@@ -1066,9 +1118,9 @@ class HermanKlukPropagator(object):
         fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model") and self.dim <= 64
                  and self._nac_generic is None)
         desc = self._potential_descriptor(potential, dt) if fused else None
-        if fused and not families and self._whole_loop_applies(desc):
+        if fused and not hooks and self._whole_loop_applies(desc):
             # separable potential, diagonal widths, D <= 12: the whole loop as ONE launch (sc_hk_run; it exports no per-step state
-            # for the targets of a cross-correlation or for operators)
+            # for the targets of a cross-correlation, for operators or for a time-average accumulator)
             self._run_whole_loop(desc, dt, nt, rows, potential)
         elif (use_graph and fused and nt > 2 and not getattr(self, "profile_step_kernel", False) and not self.kernel_timing
               and self._modal_step_constants(potential, desc, dt) is None):
@@ -1079,13 +1131,13 @@ class HermanKlukPropagator(object):
             kmax = self._visit_steps_for(desc) if pairs else 1
             k = 0
             while k < nt:
-                self._launch_correlate(rows.row(k), per_trajectory=False, families=families)
+                self._launch_correlate(rows.row(k), per_trajectory=False, families=hooks)
                 ks = min(kmax, nt - k) if pairs else 1       # never a visit longer than the steps left
                 if ks == 2:
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
-                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, families=families)
+                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, families=hooks)
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -1095,7 +1147,7 @@ class HermanKlukPropagator(object):
                     self._launch_step_visit(desc, dt, ks)
                     for j in range(1, ks):
                         self._launch_correlate(rows.row(k + j), self._multi["states_mid"][j - 1], per_trajectory=False,
-                                               families=families)
+                                               families=hooks)
                     for _ in range(ks):
                         self.t += dt
                     k += ks
@@ -1769,6 +1821,125 @@ class HermanKlukPropagator(object):
         'previous': value at the last tracked step}, built from the device-resident tracker state (read-only views)"""
         return {name: {"signs": getattr(self, s).type(C128), "previous": getattr(self, z)}
                 for name, (s, z) in self._TRACKED.items()}
+
+
+class TimeAverageAccumulator(object):
+    """What ``HermanKlukPropagator.time_average()`` returns: A [n K][NE], the pending columns G [TB][n K] of the terms, their count
+    and the step counter s of the grid t_s = t_a + s dt.  Bound to the propagator and its ensemble."""
+
+    def __init__(self, prop, energies, dt, references, max_bytes):
+        try:
+            E = np.array(energies, dtype=np.float64)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"energies: a real array (NE,) is expected ({err})")
+        if E.ndim != 1 or E.shape[0] == 0:
+            raise ValueError(f"energies: a non-empty one-dimensional array is expected, got shape {E.shape}")
+        if not np.isfinite(E).all():
+            raise ValueError("energies: non-finite entry")
+        if E.shape[0] > 65535:
+            raise ValueError(f"energies: NE = {E.shape[0]} outside NE <= 65535")
+        dt = float(dt)
+        if not (np.isfinite(dt) and dt != 0.0):
+            raise ValueError(f"dt: a finite non-zero time step is expected, got {dt}")
+        D = prop.dim
+        if references is None:
+            Q, P = prop._q0h.numpy()[None, :].copy(), prop._p0h.numpy()[None, :].copy()
+        else:
+            try:
+                Q, P = (np.array(a, dtype=np.float64) for a in references)
+            except (TypeError, ValueError) as err:
+                raise ValueError(f"references: a pair (Q, P) of real arrays of shape (K, {D}) is expected ({err})")
+            if Q.ndim != 2 or Q.shape != P.shape or Q.shape[1] != D or Q.shape[0] == 0:
+                raise ValueError(f"references: Q and P of shape (K, {D}) with K > 0 are expected, got {Q.shape} and {P.shape}")
+            if not (np.isfinite(Q).all() and np.isfinite(P).all()):
+                raise ValueError("references: non-finite entry")
+        K, NE, n = int(Q.shape[0]), int(E.shape[0]), prop.ntraj
+        if K > 64:
+            raise ValueError(f"references: K = {K} outside K <= 64 (one tile column of the terms kernel)")
+        need = 16 * n * K * NE
+        if need > max_bytes:
+            raise ValueError(f"the accumulator A (n K, NE) = ({n} x {K}, {NE}) complex takes {need} bytes, more than max_bytes = "
+                             f"{int(max_bytes)}: fewer energies or reference states, or a smaller batch")
+        dev = prop.device
+        cc = prop._cross_constants()
+        Qt, Pt = torch.from_numpy(Q), torch.from_numpy(P)
+        self._refs = torch.cat((Qt @ cc["La"].T, Pt @ cc["Lb"].T, Qt, Pt @ cc["C"].T, Pt), 1).contiguous().to(dev)
+        self.TB = int(lib.sc_hk_ta_block())
+        self._prop, self._qp = prop, prop._qp                      # (the ensemble: another one has other buffers)
+        self.energies, self.references, self.dt, self.t_start = E, (Q, P), dt, float(prop.t)
+        self.K, self.NE = K, NE
+        self._E = torch.from_numpy(E).to(dev)
+        self._A = torch.zeros((n * K, NE), dtype=C128, device=dev)
+        self._G = torch.empty((self.TB, n * K), dtype=C128, device=dev)
+        self._W = torch.empty((self.TB, NE), dtype=C128, device=dev)
+        self._partials = torch.empty(max(int(lib.sc_hk_ta_finish_rows(n)) * K * NE * 2, 1), dtype=F64, device=dev)
+        self.pending, self.steps = 0, 0
+
+    @property
+    def window(self):
+        """T = ns dt of the steps taken so far"""
+        return self.steps * self.dt
+
+    def _check_owner(self, prop):
+        if prop is not self._prop or prop._qp is not self._qp:
+            raise ValueError("this time-average accumulator belongs to another propagator or to an earlier set of initial conditions")
+
+    def _check_run(self, prop, dt):
+        """run(time_average=self): refused before anything is launched"""
+        self._check_owner(prop)
+        if dt != self.dt:
+            raise ValueError(f"time_average: the accumulator's grid has dt = {self.dt}, this run has dt = {dt}")
+
+    def _append(self, state=None):
+        """the terms of `state` (default: the propagator's current one) as column `pending`; a full block goes into A"""
+        prop = self._prop
+        cc = prop._cross_constants()
+        b = cc["bufs"]
+        with prop._timed("hk_ta_terms"):
+            check(lib.sc_hk_ta_terms(prop._state if state is None else state, ptr(b[0]), ptr(b[1]), ptr(b[2]), int(cc["diag"]),
+                                     cc["fac"], ptr(self._refs), self.K, ptr(prop._kept), ptr(cc["operands"]), ptr(self._G),
+                                     self.pending, prop._stream()))
+        self.pending += 1
+        self.steps += 1
+        if self.pending == self.TB:
+            self._flush()
+
+    def _flush(self):
+        """the pending columns into A"""
+        if self.pending == 0:
+            return
+        prop = self._prop
+        with prop._timed("hk_ta_accumulate"):
+            check(lib.sc_hk_ta_accumulate(ptr(self._G), prop.ntraj, self.K, self.pending, ptr(self._E), self.NE, self.t_start, self.dt,
+                                          self.steps - self.pending, ptr(self._W), ptr(self._A), prop._stream()))
+        self.pending = 0
+
+    def add(self):
+        """append the propagator's current state as the next step of the window (for callers of ``step()``: once per step, before
+        it, as ``run()`` does)"""
+        self._check_owner(self._prop)
+        self._append()
+
+    def raw_sums(self):
+        """the sums (K, NE, 2) over this batch's trajectories of y T and (y T)^2, y_ik(e) = |A_ik(E_e)|^2 / (2 pi hbar T mc_norm
+        P_i), as a NumPy array: plain sums with the global N in the weight, so the buffers of batches of one N and of ranks add;
+        ``finalize_time_average`` finishes them.  Flushes the pending columns; trajectories discarded by now count as y = 0, N
+        unchanged.  Synchronises; the accumulator goes on afterwards."""
+        prop = self._prop
+        self._check_owner(prop)
+        self._flush()
+        out = torch.empty((self.K, self.NE, 2), dtype=F64, device=prop.device)
+        check(lib.sc_hk_ta_finish(ptr(self._A), prop.ntraj, self.K, self.NE, ptr(prop.probi), prop._mc_norm(), ptr(prop._kept),
+                                  ptr(self._partials), ptr(out), prop._stream()))
+        prop.synchronize()
+        return out.cpu().numpy()
+
+    def spectrum(self, standard_errors=False):
+        """I (K, NE) over the window so far, or (I, sigma) with its Monte-Carlo standard errors"""
+        if self.steps == 0:
+            raise ValueError("the window is empty: no step has been added to the accumulator")
+        I, sigma = HermanKlukPropagator.finalize_time_average(self.raw_sums(), self.window, self._prop._ntraj_norm)
+        return (I, sigma) if standard_errors else I
 
 
 class _KernelTimer(object):
