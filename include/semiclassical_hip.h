@@ -747,6 +747,44 @@ int sc_comm_rank_count(void *comm, int32_t *rank_out, int32_t *nranks_out);
 int sc_comm_destroy(void *comm);
 int sc_flush_allreduce(double *sums, int64_t count, void *comm, void *stream);
 
+/* ---- Quartic force field (an addition: the ABI number stays) ---------------------------------------------------------------
+ * A coupled anharmonic Taylor expansion around pos0, behind potentials.QuarticForceFieldPotential (not in the reference, whose
+ * potential protocol, potentials.py:41-204, it implements).  With x = r - pos0, y_i = x_i^2, z_i = x_i^3:
+ *   W_ij   = sum_k t_ijk x_k
+ *   V      = energy0 + g.x + 1/2 x^T H x + 1/6 x^T W x + y^T A y + z^T B x
+ *   dV_m   = g_m + (Hx)_m + 1/2 (Wx)_m + 4 x_m (Ay)_m + 3 x_m^2 (Bx)_m + (B^T z)_m
+ *   d2V_mn = H_mn + W_mn + 8 A_mn x_m x_n + 3 B_mn x_m^2 + 3 B_nm x_n^2 + delta_mn [4 (Ay)_m + 6 x_m (Bx)_m]
+ * cubic holds the DERIVATIVES t_ijk; quartic_a / quartic_b hold the semi-diagonal quartic derivatives FOLDED by the caller:
+ * A_ij = u_iijj / 8 (i != j), A_ii = u_iiii / 24, B_ij = u_iiij / 6 (zero diagonal).  hess0, cubic and quartic_a have to be
+ * symmetric bit for bit (the kernel relies on it for an exactly symmetric Hessian image).  A NULL cubic skips the D^2 x D x n
+ * product, NULL quartic_a and quartic_b skip the quartic terms; either of the two alone counts as zeros. */
+typedef struct sc_qff_model {
+    int32_t dim, _pad;
+    const double *pos0, *grad0, *hess0;      /* [D], [D], [D][D] */
+    const double *cubic;                     /* [D][D][D] derivatives, fully symmetric; NULL = none */
+    const double *quartic_a, *quartic_b;     /* folded A, B [D][D]; NULL = none */
+    double energy0;                          /* energy0 - origin */
+    const double *inv_mass;                  /* [D] */
+} sc_qff_model;
+
+/*   sc_qff_max_dim        96: the largest D (the limit of sc_dense_mono_step's matrix-core route)
+ *   sc_qff_tile           trajectories per workgroup (the tile edges of the n axis; results do not depend on it)
+ *   sc_qff_scratch_bytes  bytes of the `scratch` of sc_qff_stage: stage positions, V and grad of n trajectories; -1 for an
+ *                         invalid shape
+ *   sc_qff_eval           r [n][D] -> energy [n], grad [n][D], hess [n][D][D] (the contract of sc_gdml_eval)
+ *   sc_qff_stage          one RK4 stage of (q, p, S) (the contract of sc_gdml_stage_scratch): stage point, evaluation with the
+ *                         stage Hessian written straight into sc->hess[i][stage], slopes; energy_partials[sc_dense_grid()]
+ * W = T.X runs on v_mfma_f64_16x16x4_f64.  Every sum runs in an order fixed by D: a trajectory's results do not depend on n,
+ * on its index or on the launch shape; no atomics; hess[i][j] == hess[j][i] bit for bit.
+ * A null pointer or a stage outside 0..3: SC_ERR_BAD_ARGUMENT.  D < 1, D > sc_qff_max_dim() or n > 64 * 65535:
+ * SC_ERR_UNSUPPORTED.  n = 0: SC_OK, nothing is launched. */
+int     sc_qff_max_dim(void);
+int     sc_qff_tile(void);
+int64_t sc_qff_scratch_bytes(int64_t n, int32_t dim);
+int sc_qff_eval(const sc_qff_model *m, const double *r, int64_t n, double *energy, double *grad, double *hess, void *stream);
+int sc_qff_stage(const sc_qff_model *m, double *scratch, const sc_state *st, const sc_dense_scratch *sc, double dt,
+                 int32_t stage, double *energy_partials, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

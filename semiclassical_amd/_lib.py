@@ -73,6 +73,12 @@ class sc_dense_scratch(C.Structure):
     _fields_ = [("hess", c_double_p), ("kprev", c_double_p), ("ksum", c_double_p), ("ssum", c_double_p)]
 
 
+class sc_qff_model(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("_pad", C.c_int32),
+                ("pos0", c_double_p), ("grad0", c_double_p), ("hess0", c_double_p), ("cubic", c_double_p),
+                ("quartic_a", c_double_p), ("quartic_b", c_double_p), ("energy0", C.c_double), ("inv_mass", c_double_p)]
+
+
 SC_POT_MORSE, SC_POT_HARMONIC_SEP, SC_POT_EPS_MORSE, SC_POT_HARMONIC_DENSE = 1, 2, 3, 4
 SEPARABLE_KINDS = (SC_POT_MORSE, SC_POT_HARMONIC_SEP, SC_POT_EPS_MORSE)      # sc_pot_is_separable (csrc/sc_common.h)
 SC_MONO_ROWMAJOR, SC_MONO_TILED16 = 0, 1
@@ -81,7 +87,7 @@ SC_MONO_ROWMAJOR, SC_MONO_TILED16 = 0, 1
 P = C.POINTER
 ABI_VERSION = 18              # = SC_ABI_VERSION of include/semiclassical_hip.h these declarations were written against
 STRUCTS = (sc_potential, sc_state, sc_hk_consts, sc_overlap_consts, sc_nac_consts, sc_wm_consts, sc_gdml_model,
-           sc_dense_scratch, sc_multi_scratch)
+           sc_dense_scratch, sc_multi_scratch, sc_qff_model)
 
 SIGNATURES = {
     "sc_version": (C.c_int, []),
@@ -215,6 +221,12 @@ SIGNATURES = {
     "sc_term_masked_scratch_doubles": (C.c_int64, []),
     "sc_term_masked_sums": (C.c_int, [c_double_p, c_double_p, C.c_void_p, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
                                       c_double_p, C.c_void_p]),
+    "sc_qff_max_dim": (C.c_int, []),
+    "sc_qff_tile": (C.c_int, []),
+    "sc_qff_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "sc_qff_eval": (C.c_int, [P(sc_qff_model), c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "sc_qff_stage": (C.c_int, [P(sc_qff_model), c_double_p, P(sc_state), P(sc_dense_scratch), C.c_double, C.c_int32,
+                               c_double_p, C.c_void_p]),
     "sc_comm_available": (C.c_int, []),
     "sc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "sc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(C.c_void_p)]),

@@ -96,6 +96,41 @@ def _setup_adiabatic_shift(section):
                         zero_point, np.nan)
 
 
+@_potential_type("quartic force field")
+def _setup_quartic_force_field(section):
+    """npz model file.  Surface: pos0 (D,), energy0 (), grad0 (D,), hess0 (D, D), masses (D,), coupling (D,) and the optional
+    cubic (D, D, D), quartic_iijj (D, D), quartic_iiij (D, D), origin (); all derivatives at pos0 in atomic units
+    (potentials.QuarticForceFieldPotential).  Wavepacket: q0 (D,), Gamma_0 (D, D), zero_point_energy (), optional p0 (D,)
+    (default 0) and adiabatic_gap (default NaN, as the AS type).  No minimisation: the file says where the origin is."""
+    path = section['model_file']
+    try:
+        with np.load(path) as npz:
+            data = {k: np.asarray(npz[k], dtype=np.float64) for k in npz.files}
+    except Exception as err:
+        raise ConfigurationError(f"'quartic force field': {path} should be an npz file ({err})")
+    required = ("pos0", "energy0", "grad0", "hess0", "masses", "coupling", "q0", "Gamma_0", "zero_point_energy")
+    missing = [k for k in required if k not in data]
+    if missing:
+        raise ConfigurationError(f"'quartic force field': {path} lacks the array(s) {', '.join(missing)}")
+    dim = data["pos0"].size
+    shapes = {"q0": (dim,), "p0": (dim,), "Gamma_0": (dim, dim), "zero_point_energy": (), "adiabatic_gap": (), "origin": ()}
+    for key, shape in shapes.items():
+        if key in data and (data[key].shape != shape or not np.all(np.isfinite(data[key])) and key != "adiabatic_gap"):
+            raise ConfigurationError(f"'quartic force field': {key} of shape {shape}, finite, is expected in {path}, got "
+                                     f"{data[key].shape}")
+    try:
+        surface = potentials.QuarticForceFieldPotential.from_arrays(
+            data["pos0"], data["energy0"], data["grad0"], data["hess0"], cubic=data.get("cubic"),
+            quartic_iijj=data.get("quartic_iijj"), quartic_iiij=data.get("quartic_iiij"), masses=data["masses"],
+            nac0=data["coupling"], origin=float(data.get("origin", 0.0)))
+    except ValueError as err:
+        raise ConfigurationError(f"'quartic force field': {path}: {err}")
+    q0 = torch.from_numpy(data["q0"])
+    p0 = torch.from_numpy(data["p0"]) if "p0" in data else torch.zeros_like(q0)
+    return ProblemSetup(surface, q0, p0, torch.from_numpy(data["Gamma_0"]), float(data["zero_point_energy"]),
+                        float(data.get("adiabatic_gap", np.nan)))
+
+
 def build_problem(task):
     section = task['potential']
     builder = _SETUPS.get(section['type'])

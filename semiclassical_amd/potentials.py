@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._lib import sc_potential, ptr
 
-__all__ = ['NonHarmonicPotential', 'MorsePotential', 'MolecularHarmonicPotential']
+__all__ = ['NonHarmonicPotential', 'MorsePotential', 'MolecularHarmonicPotential', 'QuarticForceFieldPotential']
 
 logger = logging.getLogger(__name__)
 
@@ -290,6 +290,139 @@ class MolecularHarmonicPotential(_MolecularPotentialBase):
                 + 0.5 * torch.einsum('in,ij,jn->n', dr, hess0, dr))
         grad = grad0.unsqueeze(1).expand_as(r) + torch.einsum('ij,jn->in', hess0, dr)
         return vpot - self._origin, grad, hess0.unsqueeze(2).expand(-1, -1, n)
+
+    def derivative_coupling_1st(self, r):
+        return self.nac0.to(r.device).unsqueeze(1).expand_as(r)
+
+    def derivative_coupling_2nd(self, r):
+        return torch.zeros_like(r)
+
+
+def _qff_array(name, x, shape):
+    a = np.array(x, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"{name}: shape {a.shape}, expected {shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name}: non-finite entries")
+    return a
+
+
+def _qff_symmetric(name, a, what="symmetric"):
+    """``a`` has to be invariant under all permutations of its axes, relative to 1e-12 of its largest entry; returns the exact
+    symmetric average (the permuted copies are added in sorted order: the same bits at every permutation of an index tuple)"""
+    import itertools
+    perms = [np.transpose(a, p) for p in itertools.permutations(range(a.ndim))]
+    scale = np.abs(a).max() if a.size else 0.0
+    if any(np.abs(p - a).max() > 1.0e-12 * scale for p in perms[1:]):
+        raise ValueError(f"{name}: not {what} (relative to 1e-12 of its largest entry)")
+    s = np.sort(np.stack(perms), axis=0)             # an array that is symmetric already comes back unchanged
+    return np.ascontiguousarray(s[0] + (s[1:] - s[0]).sum(axis=0) / len(perms))
+
+
+class QuarticForceFieldPotential(_MolecularPotentialBase):
+    """Coupled anharmonic Taylor expansion around ``pos0`` (quartic force field): Hessian, cubic constants t_ijk and the
+    semi-diagonal quartic constants u_iiii, u_iijj, u_iiij, all DERIVATIVES at ``pos0`` in the coordinates of ``pos0``, atomic
+    units.  With x = r - pos0
+
+        V(x) = energy0 - origin + g.x + 1/2 x^T H x + 1/6 sum_ijk t_ijk x_i x_j x_k
+               + 1/24 sum_i u_iiii x_i^4 + 1/4 sum_{i<j} u_iijj x_i^2 x_j^2 + 1/6 sum_{i!=j} u_iiij x_i^3 x_j
+
+    Not in the reference; it implements the reference's potential protocol (potentials.py:41-204).  Up to
+    ``sc_qff_max_dim()`` dimensions the propagators evaluate it with ``sc_qff_stage``; the torch
+    code below serves ``minimize``, the CPU oracle and the generic route beyond that size.  Both use the folded constants
+    A_ij = u_iijj / 8 (i != j), A_ii = u_iiii / 24, B_ij = u_iiij / 6 and the same expressions."""
+
+    @classmethod
+    def from_arrays(cls, pos0, energy0, grad0, hess0, cubic=None, quartic_iijj=None, quartic_iiij=None, masses=None, nac0=None,
+                    origin=0.0):
+        """``cubic`` (D, D, D) = t_ijk; ``quartic_iijj`` (D, D) symmetric = u_iijj with u_iiii on the diagonal; ``quartic_iiij``
+        (D, D) with entry [i][j] = u_iiij and a zero diagonal.  Nothing is symmetrised silently: a wrong shape, a non-finite
+        entry, an asymmetric ``hess0`` / ``cubic`` / ``quartic_iijj`` or a non-zero diagonal of ``quartic_iiij`` is a ValueError."""
+        pot = cls.__new__(cls)
+        p0 = np.array(pos0, dtype=np.float64)
+        if p0.ndim != 1 or p0.size < 1:
+            raise ValueError(f"pos0: shape {p0.shape}, expected (D,)")
+        D = p0.size
+        if masses is None or nac0 is None:
+            raise ValueError("masses and nac0 are required")
+        p0 = _qff_array("pos0", p0, (D,))
+        e0 = _qff_array("energy0", energy0, ())
+        g0 = _qff_array("grad0", grad0, (D,))
+        h0 = _qff_symmetric("hess0", _qff_array("hess0", hess0, (D, D)))
+        m = _qff_array("masses", masses, (D,))
+        nac = _qff_array("nac0", nac0, (D,))
+        t = a = b = None
+        if cubic is not None:
+            t = _qff_symmetric("cubic", _qff_array("cubic", cubic, (D, D, D)), "symmetric under all index permutations")
+        if quartic_iijj is not None:
+            u = _qff_symmetric("quartic_iijj", _qff_array("quartic_iijj", quartic_iijj, (D, D)))
+            a = u / 8.0
+            a[np.diag_indices(D)] = np.diag(u) / 24.0
+        if quartic_iiij is not None:
+            v = _qff_array("quartic_iiij", quartic_iiij, (D, D))
+            if np.any(np.diag(v) != 0.0):
+                raise ValueError("quartic_iiij: the diagonal has to be zero (u_iiii is the diagonal of quartic_iijj)")
+            b = v / 6.0
+        T = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x))
+        pot.pos0, pot.energy0, pot.grad0, pot.hess0 = T(p0), T(e0), T(g0), T(h0)
+        pot.cubic, pot.quartic_a, pot.quartic_b = T(t), T(a), T(b)
+        pot.nac0, pot._masses, pot._dim = T(nac), T(m), D
+        pot._origin = float(origin)
+        pot._model_cache = {}
+        return pot
+
+    def _invalidate_descriptor(self):
+        self._model_cache = {}
+
+    def _qff_model(self, device):
+        """the ``sc_qff_model`` parameter block on ``device`` (device buffers are cached per device)"""
+        key = str(device)
+        hit = self._model_cache.get(key)
+        if hit is None or hit[2] != self._origin:
+            up = lambda t: None if t is None else t.contiguous().to(device)
+            bufs = [up(self.pos0), up(self.grad0), up(self.hess0), up(self.cubic), up(self.quartic_a), up(self.quartic_b),
+                    up(1.0 / self._masses)]
+            m = _lib.sc_qff_model(dim=self._dim, pos0=ptr(bufs[0]), grad0=ptr(bufs[1]), hess0=ptr(bufs[2]), cubic=ptr(bufs[3]),
+                                  quartic_a=ptr(bufs[4]), quartic_b=ptr(bufs[5]), energy0=float(self.energy0) - self._origin,
+                                  inv_mass=ptr(bufs[6]))
+            self._model_cache[key] = hit = (m, bufs, self._origin)
+        return hit[0]
+
+    def harmonic_approximation(self, r):
+        """V (n,), grad (D, n), hess (D, D, n) for positions r (D, n), from the folded forms (plain torch, any device)"""
+        dev = r.device
+        on = lambda t: None if t is None else t.to(dev)
+        g, H, t, A, B = on(self.grad0), on(self.hess0), on(self.cubic), on(self.quartic_a), on(self.quartic_b)
+        dim, n = r.size()
+        x = r - on(self.pos0).unsqueeze(1)
+        Hx = H @ x
+        V = float(self.energy0) - self._origin + torch.einsum('i,in->n', g, x) + 0.5 * torch.sum(x * Hx, dim=0)
+        grad = g.unsqueeze(1) + Hx
+        hess = H.unsqueeze(2).expand(-1, -1, n)
+        if t is not None:
+            W = torch.einsum('ijk,kn->ijn', t, x)
+            Wx = torch.einsum('ijn,jn->in', W, x)
+            V = V + torch.sum(x * Wx, dim=0) / 6.0
+            grad = grad + 0.5 * Wx
+            hess = hess + W
+        if A is not None or B is not None:
+            y = x * x
+            z = y * x
+            diag = torch.zeros_like(x)
+            if A is not None:
+                Ay = A @ y
+                V = V + torch.sum(y * Ay, dim=0)
+                grad = grad + 4.0 * x * Ay
+                hess = hess + 8.0 * A.unsqueeze(2) * x.unsqueeze(1) * x.unsqueeze(0)
+                diag = diag + 4.0 * Ay
+            if B is not None:
+                Bx = B @ x
+                V = V + torch.sum(z * Bx, dim=0)
+                grad = grad + 3.0 * y * Bx + B.t() @ z
+                hess = hess + 3.0 * B.unsqueeze(2) * y.unsqueeze(1) + 3.0 * B.t().unsqueeze(2) * y.unsqueeze(0)
+                diag = diag + 6.0 * x * Bx
+            hess = hess + torch.diag_embed(diag.t()).permute(1, 2, 0)
+        return V, grad, hess
 
     def derivative_coupling_1st(self, r):
         return self.nac0.to(r.device).unsqueeze(1).expand_as(r)

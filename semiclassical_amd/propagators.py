@@ -390,7 +390,14 @@ class HermanKlukPropagator(object):
             self._sync_dense_mono(leave_diagonal=True)
             self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
             nblocks = self._launch_dense_step(potential, dt, s)
-        elif not hasattr(potential, "_descriptor") or self.dim > 64:
+        elif hasattr(potential, "_qff_model") and self.dim <= lib.sc_qff_max_dim():
+            # quartic force field (in front of the descriptor test: the molecular base class carries the descriptor mixin)
+            self._blocks_structurally_diagonal = False
+            self._leave_modal()
+            self._sync_dense_mono(leave_diagonal=True)
+            self._set_mono_layout(_lib.SC_MONO_ROWMAJOR)
+            nblocks = self._launch_qff_step(potential, dt, s)
+        elif not hasattr(potential, "_descriptor") or hasattr(potential, "_qff_model") or self.dim > 64:
             # no device descriptor, or beyond the fused kernels' D <= 64: the potential's own torch code + dense path
             self._blocks_structurally_diagonal = False
             self._leave_modal()
@@ -467,6 +474,24 @@ class HermanKlukPropagator(object):
             with self._timed("gdml_stage"):
                 check(lib.sc_gdml_stage_scratch(model, ptr(self._gdml_scratch), self._state, self._dense, dt, stage,
                                                 ptr(self._epart), s))
+        with self._timed("dense_mono_step"):
+            check(lib.sc_dense_mono_step(self._state, self._hk, model.inv_mass, ptr(self._dense_bufs[0]),
+                                         self._mono_sums_ptr(), dt, 0, s))
+        return self._gdense
+
+    def _launch_qff_step(self, potential, dt, s):
+        """unfused RK4 step on a quartic force field: four sc_qff_stage calls (stage Hessians on the FP64 matrix cores, written
+        straight into the image of the monodromy kernel) + the monodromy kernel"""
+        self._dense_scratch()
+        need = lib.sc_qff_scratch_bytes(self.ntraj, self.dim)
+        have = getattr(self, "_qff_scratch", None)
+        if have is None or have.numel() * 8 < need:
+            self._qff_scratch = torch.empty((need + 7) // 8, dtype=F64, device=self.device)
+        with torch.cuda.device(self.device):
+            model = potential._qff_model(self.device)
+        for stage in range(4):
+            with self._timed("qff_stage"):
+                check(lib.sc_qff_stage(model, ptr(self._qff_scratch), self._state, self._dense, dt, stage, ptr(self._epart), s))
         with self._timed("dense_mono_step"):
             check(lib.sc_dense_mono_step(self._state, self._hk, model.inv_mass, ptr(self._dense_bufs[0]),
                                          self._mono_sums_ptr(), dt, 0, s))
@@ -1115,7 +1140,8 @@ class HermanKlukPropagator(object):
                 moments = torch.zeros((nt, 6), dtype=F64, device=self.device)
         rows = self._rows(self.device, nt, slots, moments, blocks, **bufs, **counts)
         t0 = self.t
-        fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model") and self.dim <= 64
+        fused = (hasattr(potential, "_descriptor") and not hasattr(potential, "_gdml_model")
+                 and not hasattr(potential, "_qff_model") and self.dim <= 64
                  and self._nac_generic is None)
         desc = self._potential_descriptor(potential, dt) if fused else None
         if fused and not hooks and self._whole_loop_applies(desc):

@@ -44,6 +44,53 @@ def sgdml_model(n_atoms, n_train, seed):
     return model, pos
 
 
+QFF_COUPLING_FRACTION = 0.02
+
+
+def qff_model(dim, seed=0, fraction=QFF_COUPLING_FRACTION):
+    """Arrays of a synthetic `dim`-mode quartic force field and of the wavepacket that starts on it (the keys of the driver's
+    "quartic force field" model file, plus dt): rng(seed); omega = linspace(160, 3300) cm^-1, unit masses, pos0 = 0, grad0 = 0,
+    H = diag(omega^2); Morse-like diagonals with chi = 0.02: a_i = sqrt(2 omega_i chi), t_iii = -3 a_i omega_i^2,
+    u_iiii = 7 a_i^2 omega_i^2; off-diagonal t_ijk, u_iijj, u_iiij = `fraction` x U(-1, 1) x the geometric mean of the diagonal
+    constants of the indices involved (|t_iii t_jjj t_kkk|^(1/3), (u_iiii u_jjjj)^(1/2), (u_iiii^3 u_jjjj)^(1/4)); coupling
+    ~ N(0, 1e-4); wavepacket as in the AS model: S = U(0, 0.1) x (+-1), q0 = sign(S) sqrt(2|S|/omega), Gamma_0 = diag(omega);
+    dt = 4 a.u.
+
+    fraction = 0.02 was picked on the CPU through the oracle (tests/test_qff_host.py::test_synthetic_model_conditions repeats
+    it): at D = 6, 17, 40 and 70 the trajectories of the displaced ground-state wavepacket stay bound over 20 steps (energy guard
+    silent), and the anharmonic part of V is more than 1 % of V for the median trajectory."""
+    import itertools
+    rng = np.random.default_rng(seed)
+    omega = np.linspace(160.0, 3300.0, dim) / units.hartree_to_wavenumbers
+    a = np.sqrt(2.0 * omega * 0.02)
+    t_d, u_d = -3.0 * a * omega ** 2, 7.0 * a ** 2 * omega ** 2
+    def sym(x):                                      # exactly symmetric: the permuted copies are added in sorted order
+        s = np.sort(np.stack([np.transpose(x, p) for p in itertools.permutations(range(x.ndim))]), axis=0)
+        return s[0] + (s[1:] - s[0]).sum(axis=0) / len(s)
+    c3 = np.cbrt(np.abs(t_d))
+    cubic = sym(fraction * rng.uniform(-1, 1, (dim, dim, dim)) * c3[:, None, None] * c3[None, :, None] * c3[None, None, :])
+    iijj = sym(fraction * rng.uniform(-1, 1, (dim, dim)) * np.sqrt(u_d[:, None] * u_d[None, :]))
+    iiij = fraction * rng.uniform(-1, 1, (dim, dim)) * (u_d[:, None] ** 3 * u_d[None, :]) ** 0.25
+    idx = np.arange(dim)
+    cubic[idx, idx, idx] = t_d
+    iijj[idx, idx] = u_d
+    iiij[idx, idx] = 0.0
+    S = rng.uniform(0, 0.1, dim) * rng.choice([-1, 1], dim)
+    return {"pos0": np.zeros(dim), "energy0": np.float64(0.0), "grad0": np.zeros(dim), "hess0": np.diag(omega ** 2),
+            "cubic": cubic, "quartic_iijj": iijj, "quartic_iiij": iiij, "masses": np.ones(dim),
+            "coupling": rng.normal(0, 1e-4, dim), "q0": np.sign(S) * np.sqrt(2.0 * np.abs(S) / omega),
+            "Gamma_0": np.diag(omega), "zero_point_energy": np.float64(0.5 * omega.sum()), "dt": 4.0}
+
+
+def qff_potential(model):
+    """QuarticForceFieldPotential of the arrays of qff_model()"""
+    from .potentials import QuarticForceFieldPotential
+    return QuarticForceFieldPotential.from_arrays(
+        model["pos0"], model["energy0"], model["grad0"], model["hess0"], cubic=model.get("cubic"),
+        quartic_iijj=model.get("quartic_iijj"), quartic_iiij=model.get("quartic_iiij"), masses=model["masses"],
+        nac0=model["coupling"], origin=float(model.get("origin", 0.0)))
+
+
 class ArrayFchk(object):
     """the three accessors MolecularGDMLPotential / MolecularHarmonicPotential take from an fchk object"""
 
