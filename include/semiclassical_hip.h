@@ -785,6 +785,62 @@ int sc_qff_eval(const sc_qff_model *m, const double *r, int64_t n, double *energ
 int sc_qff_stage(const sc_qff_model *m, double *scratch, const sc_state *st, const sc_dense_scratch *sc, double dt,
                  int32_t stage, double *energy_partials, void *stream);
 
+/* ---- Thermal ensembles (an addition: the ABI number stays; no existing struct changes) ---------------------------------------
+ * C_auto(t) and k_ic(t) of the canonical density operator of a HARMONIC initial surface, behind
+ * HermanKlukPropagator.thermal_initial_conditions() (not in the reference).  The density operator is a
+ * positive mixture of coherent states of the width Gamma_0 (Glauber-Sudarshan P function): trajectory i carries its own centre,
+ * drawn from P, and the Herman-Kluk expression of sc_hk_correlate is evaluated with that centre in the place of (q0, p0).
+ * With W = m^-1/2 Gamma_0 m^-1/2 hbar = L diag(omega) L^T and the d'' modes of omega_k > 0 a centre is (Q_i, P_i) in
+ * mass-weighted normal coordinates; its Cartesian image is a_i = q0 + map_q Q_i, b_i = map_p P_i.  The bra centre at the time t
+ * of the state rotates on the initial surface,
+ *     Q_ik(t) = Q_ik cos w_k t + P_ik / w_k sin w_k t,     P_ik(t) = P_ik cos w_k t - w_k Q_ik sin w_k t,
+ * and each trajectory carries the phase Phi_i(t) = exp(i / (2 hbar) sum_k [Q_ik P_ik - Q_ik(t) P_ik(t)]).
+ *   dmodes   d'' (1 ... D)
+ *   diag     != 0: d'' == D and mode k IS coordinate k (diagonal Gamma_0): map_q, map_p hold the D scale factors m_k^-1/2,
+ *            m_k^1/2 and no matrix-vector product is formed; 0: map_q = m^-1/2 L, map_p = m^1/2 L, [D][d''] row-major
+ *   centres  [n][2 d''] = (Q_i | P_i) at t = 0; never written by the correlate kernel
+ *   n1       [D] = -hbar^2 tau1 / m (the vector behind sc_nac_consts.p0n1), NULL without coupling */
+typedef struct sc_thermal_consts {
+    int32_t dim, dmodes, diag, _pad;
+    const double *omega;            /* [d''] */
+    const double *map_q, *map_p;
+    const double *q0;               /* [D] minimum of the initial surface */
+    const double *n1;
+    const double *centres;
+} sc_thermal_consts;
+
+/*   sc_hk_thermal_initial    once per ensemble (and per coupling): vi_out[i] = <q_i, p_i, Gamma_i | a_i, b_i, Gamma_0> from the
+ *                            INITIAL points zi [n][2 D] and ovl_i0 (its qk, pk are not read), and
+ *                            nacq_out[i] = n2 + (a_i - q_i).rn + i/hbar [b_i.n1 + (p_i - b_i).gn]  (nc: rn, gn, n2 are read).
+ *                            Either output may be NULL; nacq_out needs nc and th->n1.
+ *   sc_hk_correlate_thermal  sc_hk_correlate for the state `st` AT THE TIME `time` (the caller's clock of that state: the mid
+ *                            states of sc_hk_step_multi / sc_hk_step_visit work through their views; only n, dim, qp, act, c2,
+ *                            sgn are read):
+ *                                cq_i = Phi_i(t) conj(<q_i(t), p_i(t), Gamma_t | a_i(t), b_i(t), Gamma_0>) vi_i sgn_i sqrt(c2_i)
+ *                                       e^{i S_i/hbar} / (mc_norm probi_i)
+ *                                kq_i = nacQ_i nacq_i cq_i / hbar^2,
+ *                                nacQ_i = n2 + (a_i(t) - q_i(t)).rn - i/hbar [b_i(t).n1 + (p_i(t) - b_i(t)).gn]
+ *                            cq_out and kq_out [n] complex are ALWAYS written (kq_out only with nc); partials
+ *                            [sc_correlate_grid()][4] as sc_hk_correlate writes them, so sc_reduce_slot*, sc_term_moments,
+ *                            sc_term_blocks* and sc_term_masked_sums follow unchanged.  cos / sin of omega_k t are formed once
+ *                            per workgroup.  With all centres zero the terms are those of sc_hk_correlate up to rounding.
+ *   sc_sample_thermal        sc_sample_initial with per-trajectory centres drawn ON THE DEVICE: Q_ik = sigma_q[k] g, P_ik =
+ *                            sigma_p[k] g', (g, g') the Box-Muller pair with pair index d' + k of the trajectory's Philox stream
+ *                            (the pairs 0 ... d' - 1 are the xi of sc_sample_initial, bit for bit: with the same seed
+ *                            zi - (a_i, b_i) is the zero-temperature draw minus z0 up to rounding); centres_out [n][2 d''],
+ *                            zi_t = (a_i, b_i) + iLz^T xi, probi and the state as sc_sample_initial writes them.
+ *                            d' + d'' <= 256 (the pair index has eight bits), else SC_ERR_UNSUPPORTED.
+ * D <= 512, n <= 64 * 65535; beyond: SC_ERR_UNSUPPORTED.  A null pointer: SC_ERR_BAD_ARGUMENT.  One launch each; no atomics,
+ * the order of every sum is a function of the shapes alone: the same bits in every call. */
+int sc_hk_thermal_initial(const sc_thermal_consts *th, const sc_overlap_consts *ovl_i0, const sc_nac_consts *nc,
+                          const double *zi, int64_t n, double *vi_out, double *nacq_out, void *stream);
+int sc_hk_correlate_thermal(const sc_state *st, double time, const sc_overlap_consts *ovl_t0, const sc_nac_consts *nc,
+                            const sc_thermal_consts *th, const double *vi, const double *probi, const double *nacq,
+                            double mc_norm, double *cq_out, double *kq_out, double *partials, void *stream);
+int sc_sample_thermal(const sc_state *st, const double *ilz, const sc_thermal_consts *th, const double *sigma_q,
+                      const double *sigma_p, int32_t dprime, double prob0, uint64_t seed, uint64_t subsequence, int64_t first,
+                      int32_t init_state, double *centres_out, double *zi_t, double *probi, double *xi_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,12 @@ class sc_qff_model(C.Structure):
                 ("quartic_a", c_double_p), ("quartic_b", c_double_p), ("energy0", C.c_double), ("inv_mass", c_double_p)]
 
 
+class sc_thermal_consts(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("dmodes", C.c_int32), ("diag", C.c_int32), ("_pad", C.c_int32),
+                ("omega", c_double_p), ("map_q", c_double_p), ("map_p", c_double_p), ("q0", c_double_p), ("n1", c_double_p),
+                ("centres", c_double_p)]
+
+
 SC_POT_MORSE, SC_POT_HARMONIC_SEP, SC_POT_EPS_MORSE, SC_POT_HARMONIC_DENSE = 1, 2, 3, 4
 SEPARABLE_KINDS = (SC_POT_MORSE, SC_POT_HARMONIC_SEP, SC_POT_EPS_MORSE)      # sc_pot_is_separable (csrc/sc_common.h)
 SC_MONO_ROWMAJOR, SC_MONO_TILED16 = 0, 1
@@ -87,7 +93,7 @@ SC_MONO_ROWMAJOR, SC_MONO_TILED16 = 0, 1
 P = C.POINTER
 ABI_VERSION = 18              # = SC_ABI_VERSION of include/semiclassical_hip.h these declarations were written against
 STRUCTS = (sc_potential, sc_state, sc_hk_consts, sc_overlap_consts, sc_nac_consts, sc_wm_consts, sc_gdml_model,
-           sc_dense_scratch, sc_multi_scratch, sc_qff_model)
+           sc_dense_scratch, sc_multi_scratch, sc_qff_model, sc_thermal_consts)
 
 SIGNATURES = {
     "sc_version": (C.c_int, []),
@@ -227,6 +233,14 @@ SIGNATURES = {
     "sc_qff_eval": (C.c_int, [P(sc_qff_model), c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     "sc_qff_stage": (C.c_int, [P(sc_qff_model), c_double_p, P(sc_state), P(sc_dense_scratch), C.c_double, C.c_int32,
                                c_double_p, C.c_void_p]),
+    "sc_hk_thermal_initial": (C.c_int, [P(sc_thermal_consts), P(sc_overlap_consts), P(sc_nac_consts), c_double_p, C.c_int64,
+                                        c_double_p, c_double_p, C.c_void_p]),
+    "sc_hk_correlate_thermal": (C.c_int, [P(sc_state), C.c_double, P(sc_overlap_consts), P(sc_nac_consts), P(sc_thermal_consts),
+                                          c_double_p, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p, c_double_p,
+                                          C.c_void_p]),
+    "sc_sample_thermal": (C.c_int, [P(sc_state), c_double_p, P(sc_thermal_consts), c_double_p, c_double_p, C.c_int32, C.c_double,
+                                    C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
+                                    C.c_void_p]),
     "sc_comm_available": (C.c_int, []),
     "sc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "sc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(C.c_void_p)]),

@@ -319,6 +319,7 @@ inline void sc_sep16_dispatch(int kind, int D, F &&f) {
 }
 int sc_launch_step_sd_multi(const StepArgs &a, const sc_multi_scratch &ms, int ksteps, hipStream_t s);    // sc_hk_step_sd.hip: ksteps = 2 .. 4 steps per visit
 int sc_launch_step_lin(const StepArgs &a, int grid, hipStream_t s);   // sc_hk_step_lin.hip: 1 launched, 0 shape not built
+int sc_launch_mono_identity(const sc_state *st, hipStream_t s);       // sc_sample.hip: st->mono = the identity blocks of t = 0
 
 // host-side error plumbing (sc_api.hip)
 int sc_fail(int code, const char *fmt, ...);

@@ -3,8 +3,8 @@
 //                                                     (reference semiclassical/propagators.py:537-566, 581-603)
 //
 // The reference draws xi with torch's generator on its compute device; the stream of deviates is therefore a property
-// of the torch build, not of the reference.  Here the deviates come from Philox4x32-10 (Salmon et al., SC'11: ten
-// rounds, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85):
+// of the torch build, not of the reference.  Here the deviates come from Philox4x32-10 and Box-Muller (sc_philox.h, shared
+// with the thermal sampler of sc_thermal.hip):
 //     key     = (seed lo, seed hi)
 //     counter = (trajectory index lo, trajectory index hi, pair index | subsequence[32..55] << 8, subsequence[0..31])
 // Every (seed, subsequence, trajectory, pair) is a DISTINCT Philox input (pair index < 256, subsequence < 2^56): no two
@@ -18,33 +18,11 @@
 // zi[i], zi[i + 64], ... as dot products with the columns of iLz (L2 / LDS resident, O(D^2) constants);
 // -|xi|^2/2 by a wave reduction.  Everything written once, coalesced along the trajectory's row.
 #include "sc_common.h"
+#include "sc_philox.h"
 
 namespace {
 
 constexpr int SC_SAMPLE_MAX_E = 512;      // 2 d' deviates of one trajectory staged in LDS (4 trajectories per workgroup)
-
-struct PhiloxKey { uint32_t k0, k1; };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, PhiloxKey key,
-                                              uint32_t (&out)[4]) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-    uint32_t k0 = key.k0, k1 = key.k1;
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-        const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += W0; k1 += W1;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// 53 random bits -> uniform in (0, 1]  (never 0: the logarithm of Box-Muller stays finite)
-__device__ __forceinline__ double uniform_open0(uint32_t hi, uint32_t lo) {
-    const uint64_t bits = (((uint64_t)hi << 32) | lo) >> 11;            // 53 bits
-    return ((double)bits + 1.0) * (1.0 / 9007199254740992.0);
-}
 
 struct SampleArgs {
     sc_state st;
@@ -70,13 +48,8 @@ __global__ __launch_bounds__(256) void sample_initial_kernel(SampleArgs A) {
         double half = 0.0;
         // pair p = (xi_p, xi_{p + d'}): the position and the momentum deviate of non-zero mode p
         for (int p = lane; p < dp; p += 64) {
-            uint32_t r[4];
-            philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)p | sub_hi, sub_lo, key, r);
-            const double u1 = uniform_open0(r[0], r[1]), u2 = uniform_open0(r[2], r[3]);
-            const double rad = sqrt(-2.0 * log(u1));
-            double sn, cs;
-            sincospi(2.0 * u2, &sn, &cs);
-            const double a = rad * cs, b = rad * sn;
+            double a, b;
+            philox_normal_pair(g, (uint32_t)p, sub_hi, sub_lo, key, a, b);
             xis[wave][p] = a; xis[wave][dp + p] = b;
             half += a * a + b * b;
             if (A.xi_out) { A.xi_out[tr * 2 * dp + p] = a; A.xi_out[tr * 2 * dp + dp + p] = b; }
@@ -141,6 +114,11 @@ extern "C" int sc_sample_initial(const sc_state *st, const double *ilz, const do
     hipLaunchKernelGGL(sample_initial_kernel, dim3(grid), dim3(256), 0, s, a);
     int rc = sc_check_launch("sc_sample_initial");
     if (rc != SC_OK || !init_state) return rc;
+    return sc_launch_mono_identity(st, s);
+}
+
+// M(0) = 1 of every trajectory, row-major: a memset and the two diagonals (sc_sample_initial, sc_sample_thermal)
+int sc_launch_mono_identity(const sc_state *st, hipStream_t s) {
     if (hipMemsetAsync(st->mono, 0, sizeof(double) * 4 * (size_t)st->dim * st->dim * (size_t)st->n, s) != hipSuccess)
         return sc_check_launch("sc_sample_initial (memset)");
     const int64_t diag_blocks = (st->n * 2 * st->dim + 255) / 256;

@@ -173,12 +173,23 @@ class CorrelationStore(object):
     def __init__(self, path):
         self.path = path
 
-    def start(self, task, propagator_name, times, setup, cross_targets=None, operators=None, time_average=None):
+    def _check_temperature(self, stored, kelvin):
+        """the stored correlation functions belong to the ensemble of this temperature (``temperature``, Kelvin; no key and None:
+        the one pure state of a task without "temperature")"""
+        have = float(stored['temperature']) if 'temperature' in stored else None
+        if have != (None if kelvin is None else float(kelvin)):
+            say = lambda T: "without a temperature" if T is None else f"at {T:g} K"
+            raise ConfigurationError(
+                f"{self.path} holds correlation functions computed {say(have)}, this task runs {say(kelvin)} "
+                "(\"temperature\"): they are different ensembles and cannot be pooled")
+
+    def start(self, task, propagator_name, times, setup, cross_targets=None, operators=None, time_average=None, temperature=None):
         """``cross_targets``: (q, p) of the task's "cross_correlation_targets", or None: a file that is added to has to hold
         exactly these (ConfigurationError otherwise, before any trajectory runs).  ``operators``: (bra_c, bra_m, ket_c, ket_m) of
         the task's "operator_correlation", or None: the same rule; (..., bra_k, ket_k) with Hessians (M, D, D), which a file
         without them holds as zeros.  ``time_average``: (energies, q, p, window) of the task's "time_averaged_spectrum", or None:
-        the same rule for the stored ``ta_energies``, ``ta_references_q``, ``ta_references_p`` and ``ta_window``."""
+        the same rule for the stored ``ta_energies``, ``ta_references_q``, ``ta_references_p`` and ``ta_window``.  ``temperature``:
+        the task's "temperature" in Kelvin, or None: the same rule for the stored ``temperature``."""
         fresh = task['results'].get('overwrite', True) is True or not os.path.exists(self.path)
         if fresh:
             nt = len(times)
@@ -197,6 +208,7 @@ class CorrelationStore(object):
             for fam, idents in zip(ROW_FAMILIES, (cross_targets, operators)):
                 self._check_family(fam, previous, idents)
             self._check_time_average(previous, time_average)
+            self._check_temperature(previous, temperature)
 
     CROSS_KEYS, OPERATOR_KEYS = (tuple(fam.prefix + key for key in fam.idents) + (fam.stored,) for fam in ROW_FAMILIES)
 
@@ -247,7 +259,7 @@ class CorrelationStore(object):
                           'symplecticity_tolerance', 'symplecticity_kept', 'symplecticity_discard')
 
     def add_batch(self, autocorrelation, ic_correlation, ntraj, second_moments=None, blocks=None, symplecticity=None, cross=None,
-                  operators=None, time_average=None):
+                  operators=None, time_average=None, temperature=None):
         """fold the means over ``ntraj`` new trajectories into the stored means.  ``second_moments``: (M_C, M_k), the
         per-sample second moments (rows (S_rr, S_ii, S_ri) times the batch size, phase applied) of the batch, folded the same
         way; the standard errors of the pooled means follow from them.  Files and batches that do not both carry them lose
@@ -281,10 +293,16 @@ class CorrelationStore(object):
         per-sample second moment N sum_i y_i^2.  The file then holds ``ta_energies``, ``ta_references_q``, ``ta_references_p``,
         ``ta_window``, ``ta_spectrum`` (pooled with the weights of ``autocorrelation``) and, by the same keep-or-drop rule,
         ``ta_spectrum_second_moment`` and ``ta_spectrum_error``.  Other stored energies, reference states or window (or a
-        spectrum on one side only) are refused (ConfigurationError)."""
+        spectrum on one side only) are refused (ConfigurationError).
+        ``temperature``: the temperature in Kelvin of the batch's thermal ensemble, None for the one pure
+        state; the file then holds ``temperature``.  A file of another temperature (or of none) is refused (ConfigurationError)."""
         stored = dict(np.load(self.path))
         done = stored['trajectories']
         total = done + ntraj
+        if done > 0:
+            self._check_temperature(stored, temperature)
+        if temperature is not None:
+            stored['temperature'] = float(temperature)
         records = list(zip(ROW_FAMILIES, (cross, operators)))
         if done > 0:
             for fam, record in records:
@@ -714,6 +732,20 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     if ta_file is not None and world > 1:
         raise ConfigurationError("'time_averaged_spectrum' is not available with more than one rank: the flush buffer does not "
                                  "carry its sums")
+    # "temperature": Kelvin (a key the reference does not have).  The trajectories then sample the canonical
+    # ensemble of the harmonic initial surface (widths Gamma_0, masses of the task's potential) instead of its ground state.
+    kelvin = task.get('temperature', None)
+    if kelvin is not None:
+        if isinstance(kelvin, bool) or not isinstance(kelvin, (int, float)) or not (kelvin >= 0 and np.isfinite(kelvin)):
+            raise ConfigurationError(f"'temperature' should be a non-negative number (Kelvin), got {kelvin!r}")
+        if task.get('propagator', 'HK') == "WM":
+            raise ConfigurationError("'temperature' is not available with the WM propagator: the thermal estimator is the "
+                                     "Herman-Kluk expression with per-trajectory centres")
+        for key in ('cross_correlation_targets', 'operator_correlation', 'time_averaged_spectrum'):
+            if task.get(key, None) is not None:
+                raise ConfigurationError(f"'{key}' is not available with 'temperature': its kernel takes the one centre (q0, p0)")
+        if task.get('calc_norm_every', 0):
+            raise ConfigurationError("'calc_norm_every' is not available with 'temperature': the norm describes one pure state")
     setup = build_problem(task)
     time_average = None if ta_file is None else _load_time_average(ta_file, setup)
     targets = None if targets_file is None else _load_targets(targets_file, int(setup.q0.shape[0]))
@@ -735,7 +767,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     store = CorrelationStore(task['results'].get('correlations', 'correlations.npz'))
     if writer:
         store.start(task, task.get('propagator', 'HK'), times, setup, cross_targets=targets, operators=operators,
-                    time_average=None if time_average is None else time_average + (nt * dt,))
+                    time_average=None if time_average is None else time_average + (nt * dt,), temperature=kelvin)
 
     seed = task.get('manual_seed', None)
     if seed is not None:
@@ -766,7 +798,19 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         logger.info(f"*** Repetition {repetition + 1} ***")
         propagator = make_propagator(task, setup.Gamma_0, device)
         count = mine.stop - mine.start
-        if sampling == 'device':
+        if kelvin is not None:
+            thermal = (setup.q0, setup.p0, setup.Gamma_0, setup.potential.masses(), units.kelvin_to_hartree * float(kelvin))
+            try:
+                if sampling == 'device':
+                    propagator.thermal_initial_conditions(*thermal, ntraj=count, ntraj_total=per_batch, seed=device_seed,
+                                                          subsequence=repetition, first_index=mine.start)
+                elif world == 1:
+                    propagator.thermal_initial_conditions(*thermal, ntraj=per_batch)
+                else:
+                    raise ConfigurationError("'temperature' with 'sampling': 'host' is not available with more than one rank")
+            except ValueError as err:
+                raise ConfigurationError(f"'temperature': {err}")
+        elif sampling == 'device':
             propagator.initial_conditions(setup.q0, setup.p0, setup.Gamma_0, ntraj=count, ntraj_total=per_batch,
                                           seed=device_seed, subsequence=repetition, first_index=mine.start)
         elif world == 1:
@@ -799,7 +843,7 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         if writer:
             store.add_batch(autocorrelation, ic_correlation, per_batch, second_moments=out[2:4] if errors else None,
                             blocks=out[-1] if error_blocks else None, symplecticity=checks, cross=records.get('targets'),
-                            operators=records.get('operators'), time_average=records.get('time_average'))
+                            operators=records.get('operators'), time_average=records.get('time_average'), temperature=kelvin)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -78,6 +78,66 @@ def sampling_matrices(Gamma_i, Gamma_0):
     return U, iGi0, iLz, detLz, dprime
 
 
+class ThermalConstants(object):
+    """Normal modes of the harmonic INITIAL surface and the Glauber-Sudarshan P function of its canonical density operator at
+    ``temperature`` = k_B T in Hartree (not in the reference).
+
+    The ground state of the surface has the width Gamma_0 and the masses m: W = m^-1/2 Gamma_0 m^-1/2 hbar = L diag(omega) L^T.
+    The d'' modes with omega_k > ZERO are the thermal modes (the rule of ``sampling_matrices`` for the range of a singular
+    width); zero modes carry no thermal population.  In mass-weighted normal coordinates the centres of the mixture are
+    Q_k ~ N(0, hbar nbar_k / omega_k), P_k ~ N(0, hbar nbar_k omega_k), nbar_k = 1 / (exp(hbar omega_k / k_B T) - 1); their
+    Cartesian images are a = q0 + map_q Q, b = map_p P with map_q = m^-1/2 L, map_p = m^1/2 L (D, d'').
+
+    ``diag``: Gamma_0 is diagonal and every mode is thermal -- mode k is coordinate k (no eigen-solver, no reordering) and the
+    maps are per-mode scales ``scale_q`` = m^-1/2, ``scale_p`` = m^1/2.  ``p0``, if given, has to be zero: the minimum of the
+    initial surface is at rest.  ValueError for p0 != 0, a negative or non-finite temperature, or masses that are not (D,)
+    positive numbers."""
+
+    def __init__(self, Gamma_0, masses, temperature, p0=None):
+        Gamma_0, masses = as_f64(Gamma_0), as_f64(masses)
+        D = Gamma_0.shape[0]
+        if masses.dim() != 1 or masses.shape[0] != D or not bool((masses > 0).all()) or not bool(torch.isfinite(masses).all()):
+            raise ValueError(f"thermal ensemble: masses of shape ({D},), positive, are expected, got shape {tuple(masses.shape)}")
+        temperature = float(temperature)
+        if not (temperature >= 0.0 and math.isfinite(temperature)):
+            raise ValueError(f"thermal ensemble: the temperature k_B T has to be a non-negative number, got {temperature}")
+        if p0 is not None and bool((as_f64(p0) != 0).any()):
+            raise ValueError("thermal ensemble: p0 has to be zero -- the initial surface is harmonic around (q0, 0); a moving "
+                             "wavepacket is not its thermal state")
+        isq = 1.0 / torch.sqrt(masses)
+        full_diag = is_diagonal(Gamma_0) and bool((torch.diagonal(Gamma_0) * isq * isq * hbar > ZERO).all())
+        if full_diag:
+            omega, L = torch.diagonal(Gamma_0) * isq * isq * hbar, torch.eye(D, dtype=torch.float64)
+        else:
+            w, V = _eigh(isq.unsqueeze(1) * Gamma_0 * isq.unsqueeze(0) * hbar)
+            keep = w > ZERO
+            omega, L = w[keep], V[:, keep]
+        self.dim, self.dmodes, self.diag = D, int(omega.shape[0]), bool(full_diag)
+        if self.dmodes == 0:
+            raise ValueError("thermal ensemble: Gamma_0 has no mode with a positive frequency")
+        self.temperature, self.masses = temperature, masses
+        self.omega, self.L = omega.contiguous(), L.contiguous()
+        self.scale_q, self.scale_p = isq.contiguous(), torch.sqrt(masses).contiguous()
+        self.map_q = (isq.unsqueeze(1) * L).contiguous()
+        self.map_p = (torch.sqrt(masses).unsqueeze(1) * L).contiguous()
+        if temperature > 0.0:
+            self.nbar = 1.0 / torch.expm1(hbar * omega / temperature)
+        else:
+            self.nbar = torch.zeros_like(omega)
+        self.sigma_q = torch.sqrt(hbar * self.nbar / omega)
+        self.sigma_p = torch.sqrt(hbar * self.nbar * omega)
+
+    def draw_centres(self, ntraj, generator=None):
+        """(ntraj, 2 d'') centres (Q | P) from torch's CPU generator"""
+        g = torch.randn((int(ntraj), 2 * self.dmodes), dtype=torch.float64, generator=generator)
+        return g * torch.cat((self.sigma_q, self.sigma_p)).unsqueeze(0)
+
+    def cartesian(self, centres):
+        """(a (n, D), b (n, D)) of centres (n, 2 d'') at t = 0, on the host"""
+        c = torch.as_tensor(centres, dtype=torch.float64).cpu()
+        return c[:, :self.dmodes] @ self.map_q.T, c[:, self.dmodes:] @ self.map_p.T
+
+
 class OverlapConstants(object):
     """constants of <q,p,Gi|q',p',Gj>.  propagators.py:125-179, 230"""
 

@@ -164,6 +164,7 @@ class HermanKlukPropagator(object):
         self.sqGt, self.isqGt = hostmath.sym_sqrtm(Gamma_t)
         self._nac, self._nac_pot, self._nac_fp, self._nac_generic = None, None, None, None
         self._ntraj_norm = None
+        self._thermal = None
 
     # ------------------------------------------------------------------ initial conditions
     def initial_conditions(self, q0, p0, Gamma_0, ntraj=5000, ntraj_total=None, generator=None, seed=None, subsequence=0,
@@ -248,6 +249,104 @@ class HermanKlukPropagator(object):
         self._sgn.fill_(1.0)
         self._finish_state(None)
 
+    # ---- thermal ensembles of a harmonic initial surface (not in the reference) ----
+    _thermal_ok = True              # WM has another prefactor and per-trajectory widths: no thermal ensemble
+    _thermal = None                 # the active thermal ensemble (constants, centres, sc_thermal_consts), None = one pure state
+
+    def _thermal_constants(self, q0, p0, Gamma_0, masses, temperature):
+        if not self._thermal_ok:
+            raise NotImplementedError(f"{type(self).__name__} has no thermal ensembles: the estimator is the Herman-Kluk expression "
+                                      "with per-trajectory centres")
+        q0, Gamma_0 = hostmath.as_f64(q0), hostmath.as_f64(Gamma_0)
+        assert Gamma_0.size() == self._Gi.size(), "Width parameter matrix Gamma_0 has wrong dimensions."
+        return hostmath.ThermalConstants(Gamma_0, masses, temperature, p0=p0)
+
+    def thermal_initial_conditions(self, q0, p0, Gamma_0, masses, temperature, ntraj=5000, ntraj_total=None, generator=None,
+                                   seed=None, subsequence=0, first_index=0):
+        """``initial_conditions`` for the CANONICAL ensemble of the harmonic initial surface whose ground state is
+        |q0, 0, Gamma_0> with the ``masses`` (D,) of the final-surface potential, at ``temperature`` = k_B T in Hartree
+        (``units.kelvin_to_hartree`` converts): C_auto(t) and k_ic(t) become Tr[rho e^{iH_es t} e^{-iH_gs t}] and its coupling
+        analogue.  rho is a positive mixture of coherent states of the width Gamma_0 (Glauber-Sudarshan P function); every
+        trajectory draws its own centre from it (``thermal_centres``) and its phase-space point around that centre exactly as
+        ``initial_conditions`` draws it around (q0, p0) -- ``probi`` is unchanged, the centres carry no weight.  With
+        ``generator`` / by default both are drawn on the host (first the xi of ``initial_conditions``, then the centres), with
+        ``seed`` on the device (``sc_sample_thermal``; ``subsequence``, ``first_index`` as in ``initial_conditions``).  At
+        temperature 0 every centre is (q0, 0) and the estimator is that of ``initial_conditions``.
+
+        While the ensemble is active ``autocorrelation``, ``ic_correlation``, ``autocorrelation_qp``, ``run`` (with standard
+        errors and blocks), ``standard_errors`` and ``discard_nonsymplectic`` work; everything that describes ONE pure state or
+        has no thermal kernel is refused (see ``_refuse_thermal``).  ``initial_conditions`` / ``set_initial_conditions`` return
+        to the zero-temperature path.  ``ValueError`` for p0 != 0, a negative temperature or masses of the wrong shape."""
+        tc = self._thermal_constants(q0, p0, Gamma_0, masses, temperature)
+        q0, p0, Gamma_0 = hostmath.as_f64(q0), hostmath.as_f64(p0), hostmath.as_f64(Gamma_0)
+        assert hostmath.is_symmetric_non_negative(Gamma_0), "Gamma_0 has to be symmetric and positive semi-definite."
+        d = q0.size()[0]
+        U, iGi0, iLz, detLz, dprime = hostmath.sampling_matrices(self._Gi, Gamma_0)
+        prob0 = detLz / (2 * np.pi) ** d
+        if seed is None:
+            zi, probi = self._draw_on_host(torch.zeros(2 * d, dtype=F64), iLz, prob0, dprime, int(ntraj), generator)
+            centres = tc.draw_centres(ntraj, generator)
+            a, b = tc.cartesian(centres)
+            zi = zi + torch.cat((q0.unsqueeze(0) + a, b), 1).T
+            self.set_thermal_initial_conditions(q0, p0, Gamma_0, masses, temperature, centres, zi, probi, ntraj_total=ntraj_total)
+            return
+        assert generator is None, "either a host generator or a device seed"
+        if not 0 <= int(subsequence) < 2 ** 56:
+            raise ValueError(f"subsequence {subsequence} outside [0, 2^56)")
+        dev, ntraj = self.device, int(ntraj)
+        self._begin_state(q0, p0, Gamma_0, U, iGi0, ntraj, ntraj_total)
+        self._zi_t = torch.empty((ntraj, 2 * d), dtype=F64, device=dev)
+        self.probi = torch.empty(ntraj, dtype=F64, device=dev)
+        centres = torch.empty((ntraj, 2 * tc.dmodes), dtype=F64, device=dev)
+        th, bufs = self._thermal_struct(tc, centres)
+        ilz_d, sq, sp = iLz.contiguous().to(dev), tc.sigma_q.to(dev), tc.sigma_p.to(dev)
+        check(lib.sc_sample_thermal(self._state, ptr(ilz_d), th, ptr(sq), ptr(sp), dprime, float(prob0), int(seed) & (2 ** 64 - 1),
+                                    int(subsequence), int(first_index), 1, ptr(centres), ptr(self._zi_t), ptr(self.probi), None,
+                                    self._stream()))
+        self.zi = self._zi_t.t()
+        self._finish_state((ilz_d, sq, sp))
+        self._install_thermal(tc, centres, th, bufs)
+
+    def set_thermal_initial_conditions(self, q0, p0, Gamma_0, masses, temperature, centres, zi, probi, ntraj_total=None):
+        """Start a thermal ensemble (``thermal_initial_conditions``) from given samples: ``centres`` (n, 2 d'') = (Q_i | P_i) in the
+        mass-weighted normal coordinates of ``hostmath.ThermalConstants(Gamma_0, masses, temperature)``, phase-space points
+        ``zi`` (2D, n) drawn around their Cartesian images with the sampling densities ``probi`` (n,)."""
+        tc = self._thermal_constants(q0, p0, Gamma_0, masses, temperature)
+        centres = torch.as_tensor(centres, dtype=F64)
+        n = zi.shape[1]
+        if centres.dim() != 2 or tuple(centres.shape) != (n, 2 * tc.dmodes):
+            raise ValueError(f"centres of shape ({n}, {2 * tc.dmodes}) = (Q | P) in the {tc.dmodes} thermal modes are expected, got "
+                             f"{tuple(centres.shape)}")
+        self.set_initial_conditions(q0, p0, Gamma_0, zi, probi, ntraj_total=ntraj_total)
+        centres = centres.to(self.device).contiguous().clone()
+        th, bufs = self._thermal_struct(tc, centres)
+        self._install_thermal(tc, centres, th, bufs)
+
+    def _thermal_struct(self, tc, centres):
+        """sc_thermal_consts of the constants ``tc`` and the device centres, and the buffers it points to (n1: none yet)"""
+        dev = self.device
+        maps = (tc.scale_q, tc.scale_p) if tc.diag else (tc.map_q, tc.map_p)
+        bufs = [tc.omega.to(dev), maps[0].contiguous().to(dev), maps[1].contiguous().to(dev), self.q0, centres]
+        th = _lib.sc_thermal_consts(dim=self.dim, dmodes=tc.dmodes, diag=int(tc.diag), omega=ptr(bufs[0]), map_q=ptr(bufs[1]),
+                                    map_p=ptr(bufs[2]), q0=ptr(self.q0), n1=None, centres=ptr(centres))
+        return th, bufs
+
+    def _install_thermal(self, tc, centres, th, bufs):
+        """switch the state that _finish_state has just completed to the thermal estimator: the initial overlaps with the
+        per-trajectory centres replace those with (q0, p0)"""
+        self._thermal = {"consts": tc, "centres": centres, "struct": th, "bufs": bufs}
+        check(lib.sc_hk_thermal_initial(th, self._ovl_i0, None, ptr(self._zi_t), self.ntraj, ptr(self._vi), None, self._stream()))
+        self._corr_step = -1
+
+    @property
+    def thermal_centres(self):
+        """(n, 2 d'') centres (Q_i | P_i) of the thermal ensemble at t = 0 on the device (do not write to it), None without one"""
+        return None if self._thermal is None else self._thermal["centres"]
+
+    def _refuse_thermal(self, what, why):
+        if self._thermal is not None:
+            raise NotImplementedError(f"{what} is not available with a thermal ensemble: {why}")
+
     def _begin_state(self, q0, p0, Gamma_0, U, iGi0, n, ntraj_total):
         """host constants + the (uninitialised) engine state of a batch of ``n`` trajectories"""
         dev = self.device
@@ -306,6 +405,7 @@ class HermanKlukPropagator(object):
         self._kept, self._discarded_at, self._kept_count, self._masked_scratch = None, None, None, None
         self._cross = None            # constants and scratch of cross_correlation(): depend on Gamma_0 and n
         self._opcorr = None           # folded operators, g and scratch of operator_correlation(): depend on (zi, Gamma_0, q0, p0) and n
+        self._thermal = None          # thermal ensemble (thermal_initial_conditions installs it after this): None = one pure state
 
         self._prepare()
         self.t = 0.0
@@ -606,6 +706,9 @@ class HermanKlukPropagator(object):
             return
         masses, tau1, tau2, varies = fp
         dev = self.device
+        if bool(varies.item()):
+            self._refuse_thermal("a potential with position-dependent derivative couplings",
+                                 "the thermal correlate kernel takes a constant coupling vector")
         self._nac_pot, self._nac_fp = potential, tuple(x.clone() for x in fp)
         self._corr_step = -1
         if bool(varies.item()):
@@ -623,6 +726,14 @@ class HermanKlukPropagator(object):
                                   p0n1=nc.p0n1, n2=nc.n2)
         self._nac_bufs = bufs
         self._nacq = torch.zeros(self.ntraj, dtype=C128, device=dev)
+        if self._thermal is not None:
+            # the coupling factor of the initial points with the per-trajectory centres; the kernels need the vector n1 itself
+            th = self._thermal
+            th["n1"] = (-hbar ** 2 * tau1 / masses).contiguous().to(dev)
+            th["struct"].n1 = ptr(th["n1"])
+            check(lib.sc_hk_thermal_initial(th["struct"], self._ovl_i0, self._nac, ptr(self._zi_t), self.ntraj, None, ptr(self._nacq),
+                                            self._stream()))
+            return
         check(lib.sc_nac_initial(self._nac, ptr(self._zi_t), self.ntraj, ptr(self._nacq), self._stream()))
 
     def _coupling_vectors(self, potential, r):
@@ -697,13 +808,42 @@ class HermanKlukPropagator(object):
                                       ptr(self._masked_scratch), C_void(row.slot), None if row.moments is None else C_void(row.moments),
                                       None if out is None else C_void(out), self._stream()))
 
-    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=()):
+    def _launch_correlate_thermal(self, row, state, time, cursor, families):
+        """_launch_correlate while a thermal ensemble is active: sc_hk_correlate_thermal, which always exports the terms, in the
+        place of sc_hk_correlate_m; every sum after it is the launch that follows an exporting correlate kernel today.  `time`: the
+        clock of `state` (the bra centres rotate with it)."""
+        if cursor is not None:
+            raise ValueError("use_graph=True is not available with a thermal ensemble: the time of the state is an argument of the "
+                             "correlate kernel, which a graph replay cannot change")
+        if families:
+            raise NotImplementedError(f"{families[0][0].arg} are not available with a thermal ensemble: their kernels take the one "
+                                      "centre (q0, p0)")
+        s, nac, th = self._stream(), self._nac, self._thermal
+        with self._timed("hk_correlate_thermal"):
+            check(lib.sc_hk_correlate_thermal(self._state if state is None else state, float(self.t if time is None else time),
+                                              self._ovl_t0, nac, th["struct"], ptr(self._vi), ptr(self.probi),
+                                              ptr(self._nacq) if nac is not None else None, self._mc_norm(), ptr(self._cq),
+                                              ptr(self._kq) if nac is not None else None, ptr(self._cpart), s))
+        if self._kept is not None:
+            self._masked_sums(nac is not None, row)
+            return
+        if row.blocks is not None:
+            self._term_blocks(nac is not None, row.blocks)
+        self._reduce_into(self._cpart, self._gcorr, row, None)
+        if row.moments is not None:
+            rows = self._term_moments(nac is not None)
+            check(lib.sc_reduce_moments(ptr(self._mpart), rows, C_void(row.moments), s))
+
+    def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=(), time=None):
         """per-trajectory terms + their sums for the current state into `row` (_StepRows): the 5-double slot; the six second-moment
         sums, formed inside the correlate kernel; the block sums -- the terms are exported and sc_term_blocks follows the correlate
-        kernel.  `state`: another view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi.  Under a
+        kernel.  `state`: another view of (q, p, S, c2, sign) -- the state between the two steps of sc_hk_step_multi -- and `time`
+        its clock (None: self.t; read by the thermal kernel only).  Under a
         discard mask the correlate kernel only exports the terms; sc_term_masked_sums forms every sum from them.  `families`:
         (family of _ROW_FAMILIES, its prepared dict) of the five-sum rows wanted: the (count, 5) sums of the same state go to the
         family's field of the row, one launch each after the correlate kernel, which exports its terms where a launch reads them."""
+        if self._thermal is not None:
+            return self._launch_correlate_thermal(row, state, time, cursor, families)
         s = self._stream()
         nac = self._nac
         mom_ptr, blk = row.moments, row.blocks
@@ -787,6 +927,9 @@ class HermanKlukPropagator(object):
         if not self._cross_ok:
             raise NotImplementedError(f"{type(self).__name__} has no cross-correlation with target coherent states: its Gaussians "
                                       "have per-trajectory widths and another prefactor")
+        if getattr(self, "_thermal", None) is not None:
+            raise NotImplementedError("a cross-correlation with target coherent states is not available with a thermal ensemble: "
+                                      "sc_hk_cross takes the one centre (q0, p0)")
         try:
             Q, P = np.asarray(q_targets, dtype=np.float64), np.asarray(p_targets, dtype=np.float64)
         except (TypeError, ValueError) as err:
@@ -877,6 +1020,7 @@ class HermanKlukPropagator(object):
         if not self._cross_ok:
             raise NotImplementedError(f"{type(self).__name__} has no time-averaged spectra: its Gaussians have per-trajectory "
                                       "widths and another prefactor")
+        self._refuse_thermal("a time-averaged spectrum", "its terms take fixed reference states, not per-trajectory centres")
         return TimeAverageAccumulator(self, energies, dt, references, max_bytes)
 
     def _launch_ta_terms(self, acc, out_ptr=None, state=None, cursor=None):
@@ -961,6 +1105,9 @@ class HermanKlukPropagator(object):
         if not self._opcorr_ok:
             raise NotImplementedError(f"{type(self).__name__} has no operator correlation functions: its Gaussians have "
                                       "per-trajectory widths and another prefactor")
+        if getattr(self, "_thermal", None) is not None:
+            raise NotImplementedError("an operator correlation function is not available with a thermal ensemble: the folded "
+                                      "operators take the one centre (q0, p0)")
         cA, mA, KA = self._operator_side("bra", bra)
         cB, mB, KB = (cA, mA, KA) if ket is None else self._operator_side("ket", ket)
         if cB.shape != cA.shape:
@@ -1104,6 +1251,14 @@ class HermanKlukPropagator(object):
         if use_graph and self._kept is not None:
             raise ValueError("use_graph=True is not available once trajectories have been discarded (discard_nonsymplectic): the "
                              "graph replay has no masked reduction")
+        if self._thermal is not None:
+            # (the whole-loop kernels are never taken either: _whole_loop_applies)
+            if use_graph:
+                raise ValueError("use_graph=True is not available with a thermal ensemble: the time of the state is an argument of "
+                                 "the correlate kernel, which a graph replay cannot change")
+            for name, arg in (("targets", targets), ("operators", operators), ("time_average", time_average)):
+                if arg is not None:
+                    self._refuse_thermal(f"run({name}=...)", "its kernel takes the one centre (q0, p0)")
         given = {"targets": targets, "cross": cross, "operators": operators, "opcorr": opcorr}
         families, bufs, counts = [], {}, {}
         for fam in _ROW_FAMILIES:
@@ -1163,7 +1318,8 @@ class HermanKlukPropagator(object):
                     # TWO time steps per visit of a trajectory (sc_hk_step_multi): the second step's loads of the monodromy blocks
                     # hit the memory-side cache instead of HBM; its correlation terms come from the state between the two steps
                     self._launch_step_pair(desc, dt)
-                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, families=hooks)
+                    self._launch_correlate(rows.row(k + 1), self._multi["state_mid"], per_trajectory=False, families=hooks,
+                                           time=self.t + dt)
                     self.t += dt
                     self.t += dt
                     k += 2
@@ -1171,9 +1327,11 @@ class HermanKlukPropagator(object):
                     # three or four (sc_hk_step_visit): the blocks leave and reach HBM once per visit; row k + j of the slots, moments
                     # and blocks comes from the j-th intermediate state
                     self._launch_step_visit(desc, dt, ks)
+                    t_mid = self.t
                     for j in range(1, ks):
+                        t_mid += dt                          # the clock of the j-th intermediate state, accumulated as self.t is
                         self._launch_correlate(rows.row(k + j), self._multi["states_mid"][j - 1], per_trajectory=False,
-                                               families=hooks)
+                                               families=hooks, time=t_mid)
                     for _ in range(ks):
                         self.t += dt
                     k += ks
@@ -1212,7 +1370,8 @@ class HermanKlukPropagator(object):
 
     def _whole_loop_applies(self, desc):
         # (under a discard mask the sums come from the exported terms, which the whole-loop kernels do not write)
-        return (self._whole_loop_ok and self._kept is None and not self.kernel_timing
+        # (nor with a thermal ensemble: the whole-loop kernels know the one centre (q0, p0); the step loop is taken silently)
+        return (self._whole_loop_ok and self._kept is None and self._thermal is None and not self.kernel_timing
                 and not getattr(self, "profile_step_kernel", False) and not self._shortcut_applies(desc)
                 and bool(lib.sc_hk_run_supported(desc, self._hk, self._ovl_t0)))
 
@@ -1676,6 +1835,7 @@ class HermanKlukPropagator(object):
         The discard mask (discard_nonsymplectic) is ignored: discarded trajectories contribute as ever.
         """
         from . import distributed as Dm
+        self._refuse_thermal("norm()", "it describes one pure state, the trajectories belong to a mixture")
         group = self._norm_group(across_ranks, group)
         dev, d, n = self.device, self.dim, self.ntraj
         oc = hostmath.OverlapConstants(self._Gt, self._Gt)
@@ -1757,6 +1917,7 @@ class HermanKlukPropagator(object):
         The pair sum runs in ``sc_density_pair_sum`` on the operands ``norm()`` packs (positions centred on the ensemble mean,
         the grid shifted by u.centre).  Rank-local: this rank's trajectories with this rank's weights, no communication.  The
         discard mask (discard_nonsymplectic) is ignored: discarded trajectories contribute as ever.  The state is not touched."""
+        self._refuse_thermal("reduced_density()", "it describes one pure state, the trajectories belong to a mixture")
         dev, d, n = self.device, self.dim, self.ntraj
         U = self._density_directions(directions)
         sg = torch.as_tensor(np.asarray(s, dtype=np.float64))
@@ -1812,6 +1973,7 @@ class HermanKlukPropagator(object):
         """frozen-Gaussian wavefunction psi(x,t) on a spatial grid x (dim,nx) -> complex ndarray (nx,)
         (reference propagators.py:688-732 with CoherentStatesWavefunction :243-292).  The discard mask (discard_nonsymplectic) is
         ignored: discarded trajectories contribute as ever."""
+        self._refuse_thermal("wavefunction()", "it describes one pure state, the trajectories belong to a mixture")
         x = torch.as_tensor(x, dtype=F64)
         d, nx = x.shape
         assert d == self.dim, "spatial grid has wrong dimensions"
@@ -2017,6 +2179,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
     _multi_ok = False
     _cross_ok = False               # cross_correlation() and run(targets=...) raise NotImplementedError
     _opcorr_ok = False              # operator_correlation() and run(operators=...) raise NotImplementedError
+    _thermal_ok = False             # (set_)thermal_initial_conditions raise NotImplementedError
 
     def __init__(self, Gamma_i, Gamma_t, alpha, beta, device='cuda'):
         super().__init__(Gamma_i, Gamma_t, device=device)      # the Filinov matrix needs the dense monodromy blocks

@@ -13,3 +13,6 @@ amu_to_aumass = 1822.888486192
 
 # not in the reference: the speed of light in atomic units, 1 / alpha (CODATA 2018), for the radiative rate (rates.radiative_rate)
 speed_of_light = 137.035999084
+
+# not in the reference: k_B in Hartree per Kelvin (CODATA 2018), for thermal ensembles (k_B T = kelvin_to_hartree * T / K)
+kelvin_to_hartree = 3.166811563e-6
