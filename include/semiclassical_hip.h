@@ -841,6 +841,35 @@ int sc_sample_thermal(const sc_state *st, const double *ilz, const sc_thermal_co
                       const double *sigma_p, int32_t dprime, double prob0, uint64_t seed, uint64_t subsequence, int64_t first,
                       int32_t init_state, double *centres_out, double *zi_t, double *probi, double *xi_out, void *stream);
 
+/* Thermal operator correlation functions X_a(t) = Tr[rho e^(iH_es t) A_a e^(-iH_gs t) B_a] for M pairs of LINEAR operators
+ * A_a = cA_a + mA_a.x, B_a = cB_a + mB_a.x on a thermal ensemble, behind HermanKlukPropagator.thermal_operator_correlation() and
+ * run(thermal_operators=...) (not in the reference): sc_hk_opcorr with the trajectory's own centre in the
+ * place of (q0, p0), the bra centre rotated to the time of the state.  The caller folds the Cartesian maps of the centres into
+ * the operators, so both kernels take dot products with the mode coordinates (Qc_i | Pc_i) = th->centres [n][2 d''] only:
+ *   g_ia = ket_k[a] + ket_u[a].q_i + i ket_w[a].p_i + ket_ut[a].Qc_i + i ket_wt[a].Pc_i
+ *                                                        sc_hk_opcorr_thermal_initial, from the INITIAL points zi [n][2 D] and the
+ *                                                        centres of t = 0: once per ensemble and set of operators, into g [n][M];
+ *   f_ia = bra_k[a] + bra_u[a].Q_i + i bra_w[a].P_i + bra_ut[a].Qc_i(t) + i bra_wt[a].Pc_i(t)
+ *                                                        from the current (Q_i, P_i) of `st` and the centres rotated to `time`,
+ *                                                        Qc(t) = Qc cos wt + Pc / w sin wt, Pc(t) = Pc cos wt - w Qc sin wt;
+ *   x_ia = f_ia g_ia cq_i                                cq [n] complex: the terms sc_hk_correlate_thermal exports for the same
+ *                                                        state and time (phase, overlaps, prefactor and weight inside);
+ *   out[a] = sum_i (Re x_ia, Im x_ia, (Re x_ia)^2, (Im x_ia)^2, Re x_ia Im x_ia)    -- the row of sc_hk_opcorr, no phase.
+ *   *_u, *_w [M][D] and *_k [M] complex: those of sc_hk_opcorr with p0 = 0.  *_ut, *_wt [M][d''] real: with S as there,
+ *   ut = map_q^T Gamma_0 S m on both sides, wt = -map_p^T S m / hbar (bra), +map_p^T S m / hbar (ket).
+ *   Of `th` only dim, dmodes, omega and centres are read: map_q, map_p, q0 and n1 may be NULL.
+ *   kept, partials (sc_hk_opcorr_thermal_rows(n, M) * M * 5 doubles), out, cursor, `st`: as for sc_hk_opcorr.
+ * sc_hk_opcorr_thermal: two launches; no atomics, the order of every sum is a function of (n, M, D, d'') alone: the same bits in
+ * every call.  D <= 512, 1 <= d'' <= D, 1 <= M <= 65535, n <= 64 * 65535; beyond: SC_ERR_UNSUPPORTED.  A null pointer, M < 1 or
+ * th->dim != st->dim: SC_ERR_BAD_ARGUMENT. */
+int64_t sc_hk_opcorr_thermal_rows(int64_t n, int64_t M);
+int sc_hk_opcorr_thermal_initial(const double *zi, const double *centres, int64_t n, int32_t D, int32_t dmodes,
+                                 const double *ket_u, const double *ket_w, const double *ket_ut, const double *ket_wt,
+                                 const double *ket_k, int32_t M, double *g, void *stream);
+int sc_hk_opcorr_thermal(const sc_state *st, double time, const sc_thermal_consts *th, const double *cq, const double *bra_u,
+                         const double *bra_w, const double *bra_ut, const double *bra_wt, const double *bra_k, const double *g,
+                         int32_t M, const uint8_t *kept, double *partials, double *out, const int64_t *cursor, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

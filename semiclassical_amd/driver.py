@@ -501,7 +501,8 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
     ``operators`` = (bra_c, bra_m, ket_c, ket_m) or (..., bra_k, ket_k) with the Hessians (M, D, D) of quadratic operators: the
     operator correlation functions (propagator.run(operators=...)); the result then ends with yet another element, the record
     {'bra_c', 'bra_m', 'ket_c', 'ket_m', 'correlation' (nt, M)} (and 'bra_k', 'ket_k' when given) and, with ``errors``,
-    'second_moment' (nt, M, 3).  Single rank only, for the same reason.
+    'second_moment' (nt, M, 3).  Single rank only, for the same reason.  On a thermal ensemble they are the linear operators of
+    propagator.run(thermal_operators=...) and fill the same record.
     ``time_average`` = (energies, q, p), arrays (NE,), (K, D), (K, D): the time-averaged spectrum of these reference states over
     the nt steps (propagator.time_average; ONE accumulator across all pieces of the loop, so the cuts change no bit of it); the
     result then ends with a last element, the record {'energies', 'q', 'p', 'window', 'spectrum' (K, NE)} and, with ``errors``,
@@ -548,7 +549,9 @@ def propagate_batch(propagator, setup, dt, nt, times, norm_every=0, flush=None, 
         pieces.append((first, count, propagator.t))
         extra = {}
         for fam, idents, buf in rows5:
-            extra.update({fam.noun: fam.as_run(idents), fam.buffer: buf[first:first + count]})
+            # on a thermal ensemble the operators are run()'s thermal_operators: the same rows
+            prefix = "thermal_" if fam.noun == "operators" and getattr(propagator, "thermal_centres", None) is not None else ""
+            extra.update({prefix + fam.noun: fam.as_run(idents), prefix + fam.buffer: buf[first:first + count]})
         propagator.run(setup.potential, dt, count, slots=slots[first:first + count],
                        moments=None if moments is None else moments[first:first + count],
                        blocks=None if blocks is None else blocks[first:first + count], **extra, **extra_ta)
@@ -741,7 +744,8 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
         if task.get('propagator', 'HK') == "WM":
             raise ConfigurationError("'temperature' is not available with the WM propagator: the thermal estimator is the "
                                      "Herman-Kluk expression with per-trajectory centres")
-        for key in ('cross_correlation_targets', 'operator_correlation', 'time_averaged_spectrum'):
+        # ("operator_correlation" is: linear operators on a thermal ensemble)
+        for key in ('cross_correlation_targets', 'time_averaged_spectrum'):
             if task.get(key, None) is not None:
                 raise ConfigurationError(f"'{key}' is not available with 'temperature': its kernel takes the one centre (q0, p0)")
         if task.get('calc_norm_every', 0):
@@ -750,6 +754,9 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     time_average = None if ta_file is None else _load_time_average(ta_file, setup)
     targets = None if targets_file is None else _load_targets(targets_file, int(setup.q0.shape[0]))
     operators = None if operators_file is None else _load_operators(operators_file, int(setup.q0.shape[0]))
+    if kelvin is not None and operators is not None and len(operators) > 4:
+        raise ConfigurationError("'operator_correlation' with bra_k or ket_k is not available with 'temperature': the thermal "
+                                 "operator correlation functions take linear operators")
 
     dt = task['time_step_fs'] / units.autime_to_fs
     nt = task['num_steps']

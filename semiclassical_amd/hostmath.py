@@ -220,6 +220,24 @@ def fold_linear_operators(c, m, G_traj, G_0, q0, p0, ket):
     return (Sm @ G_traj).contiguous(), (-sign / hbar * Sm).contiguous(), kappa.contiguous()
 
 
+def fold_thermal_linear_operators(c, m, G_traj, G_0, q0, tc, ket):
+    """(u, w, kappa, ut, wt): ``fold_linear_operators`` for a thermal ensemble, where the fixed Gaussian
+    is |a_i, b_i, G_0> with the trajectory's own centre a_i = q0 + map_q Qc_i, b_i = map_p Pc_i (``tc``: the ThermalConstants)
+    in the place of (q0, p0 = 0).  The element is  kappa_a + u_a.q + i w_a.p + ut_a.Qc + i wt_a.Pc  with (u, w, kappa) those of
+    ``fold_linear_operators`` at p0 = 0 and, S = (G_traj + G_0)^+,  ut = map_q^T G_0 S m,  wt = -+ map_p^T S m / hbar  (upper sign:
+    ``ket`` False) -- the kernels never see the Cartesian maps.  With ``tc.diag`` the maps are per-mode scales and ut, wt are
+    elementwise products.  Returns real (M, D) twice, complex (M,), real (M, d'') twice; the refusals of
+    ``fold_linear_operators``."""
+    u, w, kappa = fold_linear_operators(c, m, G_traj, G_0, q0, torch.zeros_like(q0), ket)
+    sign = 1.0 if ket else -1.0
+    SmG0 = (-sign * hbar * w) @ G_0                         # rows (G_0 S m_a)^T: w = -+ S m / hbar
+    if tc.diag:
+        ut, wt = SmG0 * tc.scale_q.unsqueeze(0), -w * tc.scale_p.unsqueeze(0)
+    else:
+        ut, wt = SmG0 @ tc.map_q, -w @ tc.map_p
+    return u, w, kappa, ut.contiguous(), wt.contiguous()
+
+
 def fold_quadratic_operators(c, m, K, G_traj, G_0, q0, p0, ket):
     """(u, w, kappa, lam, R): the Gaussian matrix element of the quadratic operators c_a + m_a.x + 1/2 x^T K_a x between phi_0 and a
     trajectory's Gaussian, divided by their overlap, as 1 + R COLUMNS per operator.  With x the complex

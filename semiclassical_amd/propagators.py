@@ -83,13 +83,17 @@ _Row = collections.namedtuple("_Row", "slot moments blocks cross slots k opcorr"
 # The two families of five-sum rows as run() and _launch_correlate treat them.  arg: the argument of run(); field: its buffer
 # argument and the field of _Row; letter: the count and its key in the prepared dict; what: the launch in messages; prepare: the
 # method that validates the caller's argument into the prepared dict; launch: the method that fills a row from it; needs_terms:
-# the launch reads the per-trajectory terms, which the correlate kernel then has to export.
-_RowFamily = collections.namedtuple("_RowFamily", "arg field letter what prepare launch needs_terms")
+# the launch reads the per-trajectory terms, which the correlate kernel then has to export; row: the field of _Row and the buffer
+# keyword of _StepRows where they differ from `field` -- the thermal operators travel in the opcorr
+# field: a state has a thermal ensemble or it has none, the two operator families never share a row.
+_RowFamily = collections.namedtuple("_RowFamily", "arg field letter what prepare launch needs_terms row", defaults=(None,))
 _ROW_FAMILIES = (
     _RowFamily("targets", "cross", "K", "cross-correlation", "_prepare_targets", "_launch_cross", False),
     _RowFamily("operators", "opcorr", "M", "operator-correlation", "_prepare_operators", "_launch_opcorr", True),
+    _RowFamily("thermal_operators", "thermal_opcorr", "M", "thermal operator-correlation", "_prepare_thermal_operators",
+               "_launch_thermal_opcorr", True, "opcorr"),
 )
-_OPERATOR_ROWS = _ROW_FAMILIES[1]
+_OPERATOR_ROWS, _THERMAL_OPERATOR_ROWS = _ROW_FAMILIES[1], _ROW_FAMILIES[2]
 # The hook of a time-average accumulator in the same place: a terms launch after every correlate launch.
 # It fills no row (field None) and is not an argument family of run(): its "prepared dict" is the accumulator itself.
 _TIME_AVERAGE = _RowFamily("time_average", None, None, "time-average terms", None, "_launch_ta_terms", False)
@@ -252,6 +256,7 @@ class HermanKlukPropagator(object):
     # ---- thermal ensembles of a harmonic initial surface (not in the reference) ----
     _thermal_ok = True              # WM has another prefactor and per-trajectory widths: no thermal ensemble
     _thermal = None                 # the active thermal ensemble (constants, centres, sc_thermal_consts), None = one pure state
+    _thermal_opcorr = None
 
     def _thermal_constants(self, q0, p0, Gamma_0, masses, temperature):
         if not self._thermal_ok:
@@ -274,7 +279,8 @@ class HermanKlukPropagator(object):
         temperature 0 every centre is (q0, 0) and the estimator is that of ``initial_conditions``.
 
         While the ensemble is active ``autocorrelation``, ``ic_correlation``, ``autocorrelation_qp``, ``run`` (with standard
-        errors and blocks), ``standard_errors`` and ``discard_nonsymplectic`` work; everything that describes ONE pure state or
+        errors and blocks), ``standard_errors``, ``discard_nonsymplectic`` and ``thermal_operator_correlation`` /
+        ``run(thermal_operators=...)`` work; everything that describes ONE pure state or
         has no thermal kernel is refused (see ``_refuse_thermal``).  ``initial_conditions`` / ``set_initial_conditions`` return
         to the zero-temperature path.  ``ValueError`` for p0 != 0, a negative temperature or masses of the wrong shape."""
         tc = self._thermal_constants(q0, p0, Gamma_0, masses, temperature)
@@ -406,6 +412,7 @@ class HermanKlukPropagator(object):
         self._cross = None            # constants and scratch of cross_correlation(): depend on Gamma_0 and n
         self._opcorr = None           # folded operators, g and scratch of operator_correlation(): depend on (zi, Gamma_0, q0, p0) and n
         self._thermal = None          # thermal ensemble (thermal_initial_conditions installs it after this): None = one pure state
+        self._thermal_opcorr = None   # folded operators, g and scratch of thermal_operator_correlation(): as _opcorr, and the centres
 
         self._prepare()
         self.t = 0.0
@@ -815,15 +822,19 @@ class HermanKlukPropagator(object):
         if cursor is not None:
             raise ValueError("use_graph=True is not available with a thermal ensemble: the time of the state is an argument of the "
                              "correlate kernel, which a graph replay cannot change")
-        if families:
-            raise NotImplementedError(f"{families[0][0].arg} are not available with a thermal ensemble: their kernels take the one "
-                                      "centre (q0, p0)")
+        for fam, _ in families:
+            if fam is not _THERMAL_OPERATOR_ROWS:
+                raise NotImplementedError(f"{fam.arg} are not available with a thermal ensemble: their kernels take the one "
+                                          "centre (q0, p0)")
         s, nac, th = self._stream(), self._nac, self._thermal
+        time = float(self.t if time is None else time)
         with self._timed("hk_correlate_thermal"):
-            check(lib.sc_hk_correlate_thermal(self._state if state is None else state, float(self.t if time is None else time),
+            check(lib.sc_hk_correlate_thermal(self._state if state is None else state, time,
                                               self._ovl_t0, nac, th["struct"], ptr(self._vi), ptr(self.probi),
                                               ptr(self._nacq) if nac is not None else None, self._mc_norm(), ptr(self._cq),
                                               ptr(self._kq) if nac is not None else None, ptr(self._cpart), s))
+        for fam, prepared in families:
+            getattr(self, fam.launch)(prepared, getattr(row, fam.row or fam.field), state=state, time=time)
         if self._kept is not None:
             self._masked_sums(nac is not None, row)
             return
@@ -861,7 +872,8 @@ class HermanKlukPropagator(object):
                                         ptr(self._kq) if per_trajectory else None, ptr(self._cpart),
                                         ptr(self._mpart) if in_kernel else None, s))
         for fam, prepared in families:
-            getattr(self, fam.launch)(prepared, None if fam.field is None else getattr(row, fam.field), state=state, cursor=cursor)
+            getattr(self, fam.launch)(prepared, None if fam.field is None else getattr(row, fam.row or fam.field), state=state,
+                                      cursor=cursor)
         if masked:
             assert cursor is None
             self._masked_sums(nac is not None, row)
@@ -1107,7 +1119,8 @@ class HermanKlukPropagator(object):
                                       "per-trajectory widths and another prefactor")
         if getattr(self, "_thermal", None) is not None:
             raise NotImplementedError("an operator correlation function is not available with a thermal ensemble: the folded "
-                                      "operators take the one centre (q0, p0)")
+                                      "operators take the one centre (q0, p0); the trace over the ensemble is "
+                                      "thermal_operator_correlation() / run(thermal_operators=...)")
         cA, mA, KA = self._operator_side("bra", bra)
         cB, mB, KB = (cA, mA, KA) if ket is None else self._operator_side("ket", ket)
         if cB.shape != cA.shape:
@@ -1185,8 +1198,84 @@ class HermanKlukPropagator(object):
         self._launch_correlate(self._rows.single(slot, opcorr=out), families=((_OPERATOR_ROWS, operators),))
         return self._current_five_sums(out, energy0_es, standard_errors)
 
+    # ---- operator correlation functions of a thermal ensemble, linear operators (not in the reference) ----
+    def _thermal_operators(self, bra, ket=None):
+        """``_operators`` for the active thermal ensemble: validated linear operators, the folded vectors of
+        hostmath.fold_thermal_linear_operators -- (u, w, ut, wt, kappa) of the bra, then of the ket -- and the ket-side factors
+        g [n][M] of sc_hk_opcorr_thermal_initial.  Cached per set of operators until the initial conditions change."""
+        if not self._opcorr_ok:
+            raise NotImplementedError(f"{type(self).__name__} has no operator correlation functions: its Gaussians have "
+                                      "per-trajectory widths and another prefactor")
+        if self._thermal is None:
+            raise ValueError("thermal operators need a thermal ensemble (thermal_initial_conditions): the expectation value in "
+                             "the one state phi_0 is operator_correlation() / run(operators=...)")
+        cA, mA, KA = self._operator_side("bra", bra)
+        cB, mB, KB = (cA, mA, KA) if ket is None else self._operator_side("ket", ket)
+        if KA is not None or KB is not None:
+            raise NotImplementedError("quadratic operators (a K) are not available with a thermal ensemble: "
+                                      "thermal_operator_correlation() takes linear operators (c, m)")
+        if cB.shape != cA.shape:
+            raise ValueError(f"operators: bra and ket have to hold the same number of operators, got {cA.shape[0]} and {cB.shape[0]}")
+        key = self._operators_key((cA, mA), (cB, mB))
+        hit = self._thermal_opcorr
+        if hit is not None and hit["key"] == key:
+            return hit
+        M, dev, th = int(cA.shape[0]), self.device, self._thermal
+        tc = th["consts"]
+        folded = (hostmath.fold_thermal_linear_operators(cA, mA, self._Gt, self._G0h, self._q0h, tc, ket=False)
+                  + hostmath.fold_thermal_linear_operators(cB, mB, self._Gi, self._G0h, self._q0h, tc, ket=True))
+        bufs = [folded[i].to(dev) for i in (0, 1, 3, 4, 2, 5, 6, 8, 9, 7)]        # (u, w, ut, wt, kappa) twice
+        g = torch.empty((self.ntraj, M), dtype=C128, device=dev)
+        check(lib.sc_hk_opcorr_thermal_initial(ptr(self._zi_t), ptr(th["centres"]), self.ntraj, self.dim, tc.dmodes, ptr(bufs[5]),
+                                               ptr(bufs[6]), ptr(bufs[7]), ptr(bufs[8]), ptr(bufs[9]), M, ptr(g), self._stream()))
+        partials = torch.empty(max(int(lib.sc_hk_opcorr_thermal_rows(self.ntraj, M)) * M * 5, 1), dtype=F64, device=dev)
+        self._thermal_opcorr = {"key": key, "M": M, "bra": (cA.numpy(), mA.numpy()), "ket": (cB.numpy(), mB.numpy()),
+                                "bufs": bufs, "g": g, "partials": partials}
+        return self._thermal_opcorr
+
+    def _prepare_thermal_operators(self, operators):
+        """run(thermal_operators=...): the caller's (bra, ket), or bra alone, into the prepared dict of _thermal_operators"""
+        if self._is_operator_set(operators):
+            operators = (operators, None)
+        try:
+            bra, ket = operators
+        except (TypeError, ValueError):
+            raise ValueError("operators: (bra, ket) or bra, each (c, m) of arrays (M,) and (M, D), is expected")
+        return self._thermal_operators(bra, ket)
+
+    def _launch_thermal_opcorr(self, operators, out_ptr, state=None, time=None, cursor=None):
+        """the (M, 5) thermal operator-correlation sums of `state` (default: the current one), whose clock reads `time` (None:
+        self.t), from the terms _cq sc_hk_correlate_thermal has exported for it, into the doubles at `out_ptr`; honours the
+        discard mask"""
+        assert cursor is None
+        b, th = operators["bufs"], self._thermal
+        with self._timed("hk_opcorr_thermal"):
+            check(lib.sc_hk_opcorr_thermal(self._state if state is None else state, float(self.t if time is None else time),
+                                           th["struct"], ptr(self._cq), ptr(b[0]), ptr(b[1]), ptr(b[2]), ptr(b[3]), ptr(b[4]),
+                                           ptr(operators["g"]), operators["M"], ptr(self._kept), ptr(operators["partials"]),
+                                           C_void(out_ptr), None, self._stream()))
+
+    def thermal_operator_correlation(self, bra, ket=None, energy0_es=0.0, standard_errors=False):
+        """X_a(t) = e^{i t E0/hbar} Tr[rho e^{i H_es t/hbar} A_a e^{-i H_gs t/hbar} B_a] for the current step of a thermal ensemble
+        (``thermal_initial_conditions``) with M pairs of LINEAR operators A_a = cA_a + mA_a.x, B_a likewise (not in the reference;
+        DESIGN.md section 4.20): a complex ndarray (M,) -- the Herzberg-Teller dipole correlation function at a temperature.
+        ``bra`` = (c, m), real arrays (M,) and (M, D) in the coordinates of q0; ``ket`` likewise, None = the operators of the bra.
+        Every trajectory's thermal C_auto term is multiplied by the Gaussian matrix elements of A between its own centre, rotated to
+        the current time, and its current point, and of B between its initial point and its centre: ``operator_correlation`` with
+        per-trajectory centres, which it equals at temperature 0, and ``autocorrelation()`` for c = 1, m = 0.  With
+        ``standard_errors`` the result is ``(X, sigma)``.  Discarded trajectories count as samples of value zero, N unchanged.
+        Synchronises; the state is not touched: the steps that follow give the bits they would have given without the call.
+        ``ValueError`` without a thermal ensemble (the quantity is ``operator_correlation`` then), for operators of the wrong
+        shape, with non-finite entries, M = 0, another M on the ket, or a vector m outside the range of Gamma_0 + Gamma_t (bra) or
+        Gamma_i + Gamma_0 (ket); ``NotImplementedError`` for operators with a K."""
+        operators = self._thermal_operators(bra, ket)
+        out = torch.zeros((1, operators["M"], 5), dtype=F64, device=self.device)
+        slot = torch.zeros(8, dtype=F64, device=self.device)
+        self._launch_correlate(self._rows.single(slot, opcorr=out), families=((_THERMAL_OPERATOR_ROWS, operators),))
+        return self._current_five_sums(out, energy0_es, standard_errors)
+
     def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
-            targets=None, cross=None, operators=None, opcorr=None, time_average=None):
+            targets=None, cross=None, operators=None, opcorr=None, time_average=None, thermal_operators=None, thermal_opcorr=None):
         """The caller loop of cli.py:401-436 on the device: ``nt`` times (C_auto, k_ic, step), no host sync.
 
         Returns ``(autocorrelation[nt], ic_correlation[nt])`` as complex NumPy arrays.  With ``slots`` (a
@@ -1239,6 +1328,11 @@ class HermanKlukPropagator(object):
         then exports its per-trajectory terms as it does for blocks.  Everything said of targets holds with ``opcorr`` (>= nt, M, 5) in the place of
         ``cross``; ``X`` (nt, M) and ``sigma_X`` come after the cross outputs.
 
+        Thermal operator correlation functions: ``thermal_operators`` = (bra, ket) or bra alone, each (c (M,), m (M, D)), on a
+        thermal ensemble (``thermal_operator_correlation``): a ``sc_hk_opcorr_thermal`` launch with the state's own time follows
+        every ``sc_hk_correlate_thermal`` launch, the intermediate states of pairs and visits included.  Everything said of
+        operators holds with ``thermal_opcorr`` (>= nt, M, 5) in the place of ``opcorr``; ``ValueError`` without a thermal ensemble.
+
         Time-averaged spectra: ``time_average`` = an accumulator of ``time_average()``: a ``sc_hk_ta_terms`` launch follows every
         correlate launch, the intermediate states of pairs and visits included, and every TB-th column one ``sc_hk_ta_accumulate``
         launch.  Columns that do not fill a block stay pending in the accumulator across calls (``spectrum()`` / ``raw_sums()``
@@ -1259,7 +1353,8 @@ class HermanKlukPropagator(object):
             for name, arg in (("targets", targets), ("operators", operators), ("time_average", time_average)):
                 if arg is not None:
                     self._refuse_thermal(f"run({name}=...)", "its kernel takes the one centre (q0, p0)")
-        given = {"targets": targets, "cross": cross, "operators": operators, "opcorr": opcorr}
+        given = {"targets": targets, "cross": cross, "operators": operators, "opcorr": opcorr,
+                 "thermal_operators": thermal_operators, "thermal_opcorr": thermal_opcorr}
         families, bufs, counts = [], {}, {}
         for fam in _ROW_FAMILIES:
             arg, buf = given[fam.arg], given[fam.field]
@@ -1274,7 +1369,9 @@ class HermanKlukPropagator(object):
                                  f"tensor (>= nt, {fam.letter}, 5), to receive those of the {fam.arg}")
             prepared = getattr(self, fam.prepare)(arg)
             counts[fam.letter] = prepared[fam.letter]
-            bufs[fam.field] = torch.zeros((nt, counts[fam.letter], 5), dtype=F64, device=self.device) if buf is None else buf
+            if buf is not None and fam.row is not None:        # validated under the caller's name, then a buffer of the row's field
+                self._rows._check(fam.field, buf, nt, (counts[fam.letter], 5), self.device)
+            bufs[fam.row or fam.field] = torch.zeros((nt, counts[fam.letter], 5), dtype=F64, device=self.device) if buf is None else buf
             families.append((fam, prepared))
         dt = float(dt)
         hooks = list(families)                                     # what follows every correlate launch
@@ -1345,7 +1442,7 @@ class HermanKlukPropagator(object):
         self.synchronize()
         tail = ()
         for fam, _ in families:
-            X, sigma_X = self.finalize_cross(bufs[fam.field][:nt], t0, dt, energy0_es, self._ntraj_norm)
+            X, sigma_X = self.finalize_cross(bufs[fam.row or fam.field][:nt], t0, dt, energy0_es, self._ntraj_norm)
             tail = tail + ((X, sigma_X) if standard_errors else (X,))
         if standard_errors:
             return (self.finalize_slots(slots, t0, dt, energy0_es)
