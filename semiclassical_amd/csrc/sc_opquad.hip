@@ -10,8 +10,8 @@
 //   f_ia  = l_0 z_0 + sum_{col >= 1} l_col z_col^2          (column 0: the linear part, to the first power; the others squared)
 //   x_ia  = f_ia g_ia cq_i,  row a of the output: the five sums of x_ia over i (sc_rows5.h).
 //
-// opquad_tile_kernel: the tile mapping and the staged d-loop of sc_rows5.h / opcorr_tile_kernel, the tile columns being the COLUMNS
-//   of the operators, all of them in one array [M (1 + R)][D].  With 1 + R <= 64 a workgroup owns one tile of floor(64 / (1 + R))
+// opquad_tile_kernel: the band header and the staged d-loop of sc_optile.h, the tile columns being the COLUMNS of the operators,
+//   all of them in one array [M (1 + R)][D].  With 1 + R <= 64 a workgroup owns one tile of floor(64 / (1 + R))
 //   whole operators (their columns are contiguous, so the tile is a contiguous range of columns; the rest of the 64 is staged as
 //   zeros); with 1 + R > 64 a workgroup owns ONE operator and loops over its ceil((1 + R) / 64) tiles, f carried in registers.
 //   After the d-loop of a tile every thread forms t = l z^p of its 4 x 4 pairs; the t go through the staging LDS one plane (real,
@@ -19,13 +19,11 @@
 //   the operator's columns in column order.  Then x = f g cq, x through the same LDS, and thread (operator, quarter of the band)
 //   adds its 16 trajectories in order; the four quarters are added in order: partials[band][M][5] for sc_rows5_reduce.
 //   The order of every sum is a function of (n, M, R) alone.
-// Discarded trajectories (`kept`) and the rows beyond n are staged as zero operands, and their cq and g are never loaded (x = 0 by
-// selection, not by a product): a non-finite value of a discarded trajectory cannot reach a sum.
-#include "sc_rows5.h"
+#include "sc_optile.h"
 
 namespace {
 
-constexpr int STAGE_DOUBLES = 4 * R5_CHUNK * R5_ROW;       // the d-chunk of Q, P (trajectories) and u, w (columns)
+constexpr int STAGE_DOUBLES = sizeof(OpStage) / sizeof(double);
 constexpr int PLANE_ROW = R5_TILE + 1;                     // row stride of a plane of t or x: lane = row reads without conflicts
 static_assert(R5_TILE * PLANE_ROW <= STAGE_DOUBLES, "a plane of t fits the staging buffers");
 static_assert(4 * 5 * R5_TILE <= STAGE_DOUBLES, "the four quarters of the five sums fit the staging buffers");
@@ -44,17 +42,14 @@ struct OpquadArgs {
 };
 
 __global__ __launch_bounds__(256) void opquad_tile_kernel(OpquadArgs A) {
-    __shared__ alignas(16) double lds[STAGE_DOUBLES];
+    __shared__ OpStage S;      // the planes of t and x and the four quarters of the sums reuse it
     __shared__ double2 cqs[R5_TILE];// cq_i of the band's trajectories (0: beyond n, or discarded)
     __shared__ int live[R5_TILE];
-    typedef double row[R5_ROW];
     typedef double prow[PLANE_ROW];
-    row *tq = (row *)lds, *tp = tq + R5_CHUNK, *ku = tp + R5_CHUNK, *kw = ku + R5_CHUNK;
-    prow *plane = (prow *)lds;                             // [trajectory][tile column] of t; [operator][trajectory] of x
+    prow *plane = (prow *)&S;                              // [trajectory][tile column] of t; [operator][trajectory] of x
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
     const int D = A.D, M = A.M, C1 = A.C1;
     const int64_t i0 = (int64_t)blockIdx.y * R5_TILE;
-    const int iv = (int)min((int64_t)R5_TILE, A.n - i0);
     // the workgroup's operators a0 ... a0 + ov - 1, its tiles, and the columns of an operator inside one tile
     const bool wide = C1 > R5_TILE;
     const int per = wide ? 1 : R5_TILE / C1;
@@ -62,12 +57,7 @@ __global__ __launch_bounds__(256) void opquad_tile_kernel(OpquadArgs A) {
     const int tiles = wide ? (C1 + R5_TILE - 1) / R5_TILE : 1;
     const int64_t c0 = (int64_t)a0 * C1, cend = c0 + (int64_t)ov * C1;       // the workgroup's columns
     const int pr = tid & (R5_TILE - 1), pw = tid >> 6;     // the (trajectory, operator) pairs of the thread: pr, pw + 4 s
-    if (tid < R5_TILE) {
-        const int64_t tr = i0 + tid;
-        const bool in = tid < iv && (!A.kept || A.kept[tr]);
-        cqs[tid] = in ? ((const cplx *)A.cq)[tr] : c_make(0.0, 0.0);
-        live[tid] = in;
-    }
+    optile_band_header(live, cqs, A.n, i0, A.kept, A.cq, tid);
     double fre[16], fim[16];
 #pragma unroll
     for (int s = 0; s < 16; ++s) { fre[s] = 0.0; fim[s] = 0.0; }
@@ -75,43 +65,8 @@ __global__ __launch_bounds__(256) void opquad_tile_kernel(OpquadArgs A) {
         const int64_t k0 = c0 + (int64_t)tile * R5_TILE;
         const int kv = (int)min((int64_t)R5_TILE, cend - k0);                  // valid columns of the tile
         const int seg = wide ? kv : C1;                    // columns of one operator in this tile
-        double fr[4][4], fi[4][4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) { fr[a][b] = 0.0; fi[a][b] = 0.0; }
-        for (int d0 = 0; d0 < D; d0 += R5_CHUNK) {
-            __syncthreads();                               // live[] is written; the last readers of the buffers are done
-            for (int e = tid; e < R5_CHUNK * R5_TILE; e += 256) {
-                const int r = e / R5_CHUNK, k = e - r * R5_CHUNK, d = d0 + k;  // row r of the tile, column k of the chunk
-                double q = 0.0, p = 0.0;
-                if (d < D && live[r]) {
-                    const double *row = A.qp + (i0 + r) * 2 * D;
-                    q = row[d]; p = row[D + d];
-                }
-                tq[k][r] = q; tp[k][r] = p;
-                double u = 0.0, w = 0.0;
-                if (d < D && r < kv) {
-                    const size_t at = (size_t)(k0 + r) * D + d;
-                    u = A.u[at]; w = A.w[at];
-                }
-                ku[k][r] = u; kw[k][r] = w;
-            }
-            __syncthreads();
-#pragma unroll 4
-            for (int k = 0; k < R5_CHUNK; ++k) {
-                double xq[4], xp[4], yu[4], yw[4];
-                load4(&tq[k][4 * ti], xq); load4(&tp[k][4 * ti], xp);
-                load4(&ku[k][4 * tj], yu); load4(&kw[k][4 * tj], yw);
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        fr[a][b] = fma(yu[b], xq[a], fr[a][b]);
-                        fi[a][b] = fma(yw[b], xp[a], fi[a][b]);
-                    }
-            }
-        }
+        double fr[4][4] = {}, fi[4][4] = {};
+        optile_staged_loop(S, live, A.qp, D, A.u, A.w, i0, k0, kv, tid, ti, tj, fr, fi);
         // t = l z^p, z = k + (fr, fi), in place; the columns beyond kv give zero
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -180,7 +135,7 @@ __global__ __launch_bounds__(256) void opquad_tile_kernel(OpquadArgs A) {
         }
     }
     __syncthreads();
-    double (*red)[5][R5_TILE] = (double (*)[5][R5_TILE])lds;
+    double (*red)[5][R5_TILE] = (double (*)[5][R5_TILE])&S;
     if (po < ov)
 #pragma unroll
         for (int c = 0; c < 5; ++c) red[pq][c][po] = sum[c];
@@ -201,16 +156,11 @@ __global__ __launch_bounds__(256) void opquad_initial_kernel(const double *z, in
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int64_t i = e / M;
         const int a = (int)(e - i * M);
-        const double *row = z + i * 2 * D;
         cplx f = c_make(0.0, 0.0);
         for (int j = 0; j < C1; ++j) {
             const size_t col = (size_t)a * C1 + j;
-            const double *uc = u + col * D, *wc = w + col * D;
             double re = 0.0, im = 0.0;
-            for (int d = 0; d < D; ++d) {
-                re = fma(uc[d], row[d], re);
-                im = fma(wc[d], row[D + d], im);
-            }
+            optile_affine_dot(u + col * D, w + col * D, z + i * 2 * D, D, re, im);
             const cplx zc = c_make(kap[2 * col] + re, kap[2 * col + 1] + im);
             const cplx zp = j == 0 ? zc : c_mul(zc, zc);
             f.x += lam[col] * zp.x; f.y += lam[col] * zp.y;
@@ -241,9 +191,8 @@ extern "C" int sc_hk_opquad_initial(const double *zi, int64_t n, int32_t D, cons
     const int rc = opquad_limits("sc_hk_opquad_initial", n, D, M, RB);
     if (rc != SC_OK) return rc;
     if (n == 0) return SC_OK;
-    const int64_t blocks = (n * M + 255) / 256;
-    hipLaunchKernelGGL(opquad_initial_kernel, dim3((unsigned)(blocks < 65535 ? blocks : 65535)), dim3(256), 0, (hipStream_t)stream,
-                       zi, n, D, ket_u, ket_w, ket_k, ket_l, M, 1 + RB, g);
+    hipLaunchKernelGGL(opquad_initial_kernel, sc_optile_prepass_grid(n, M), dim3(256), 0, (hipStream_t)stream, zi, n, D, ket_u, ket_w,
+                       ket_k, ket_l, M, 1 + RB, g);
     return sc_check_launch("sc_hk_opquad_initial");
 }
 
@@ -252,17 +201,11 @@ extern "C" int sc_hk_opquad(const sc_state *st, const double *cq, const double *
                             double *out, const int64_t *cursor, void *stream) {
     if (!st || !cq || !bra_u || !bra_w || !bra_k || !bra_l || !g || !partials || !out)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad: null argument");
-    int rc = opquad_limits("sc_hk_opquad", st->n, st->dim, M, RA);
+    const int rc = opquad_limits("sc_hk_opquad", st->n, st->dim, M, RA);
     if (rc != SC_OK) return rc;
     if (!st->qp) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad: the state has no qp");
-    const int64_t bands = sc_rows5_bands(st->n, M);
-    hipStream_t s = (hipStream_t)stream;
-    if (bands > 0) {
-        const int C1 = 1 + RA, per = C1 > R5_TILE ? 1 : R5_TILE / C1;
-        OpquadArgs a{st->qp, st->n, st->dim, M, C1, cq, bra_u, bra_w, bra_k, bra_l, g, kept, partials};
-        hipLaunchKernelGGL(opquad_tile_kernel, dim3((unsigned)((M + per - 1) / per), (unsigned)bands), dim3(256), 0, s, a);
-        rc = sc_check_launch("sc_hk_opquad");
-        if (rc != SC_OK) return rc;
-    }
-    return sc_rows5_reduce("sc_hk_opquad (reduction)", partials, bands, M, out, cursor, s);
+    const int C1 = 1 + RA, per = C1 > R5_TILE ? 1 : R5_TILE / C1;
+    OpquadArgs a{st->qp, st->n, st->dim, M, C1, cq, bra_u, bra_w, bra_k, bra_l, g, kept, partials};
+    return sc_optile_rows("sc_hk_opquad", (const void *)opquad_tile_kernel, &a, (unsigned)((M + per - 1) / per), st->n, M, partials,
+                          out, cursor, (hipStream_t)stream);
 }

@@ -1,6 +1,7 @@
 // Five-sum rows (sc_rows5.h): the reduction over the bands and the limits that sc_hk_cross and
-// sc_hk_opcorr share.
-#include "sc_rows5.h"
+// sc_hk_opcorr share, and the launch helpers of the operator tile kernels (sc_optile.h).
+#include <cstdio>
+#include "sc_optile.h"
 
 namespace {
 
@@ -49,4 +50,23 @@ int sc_rows5_reduce(const char *who, const double *partials, int64_t bands, int 
     hipLaunchKernelGGL(rows5_reduce_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, partials, bands, total, out,
                        (const long long *)cursor);
     return sc_check_launch(who);
+}
+
+// ---- operator tiles (sc_optile.h) ----
+dim3 sc_optile_prepass_grid(int64_t n, int M) {
+    const int64_t blocks = (n * M + 255) / 256;
+    return dim3((unsigned)(blocks < 65535 ? blocks : 65535));
+}
+
+int sc_optile_rows(const char *who, const void *tile, void *args, unsigned columns, int64_t n, int M, const double *partials,
+                   double *out, const int64_t *cursor, hipStream_t stream) {
+    const int64_t bands = sc_rows5_bands(n, M);
+    if (bands > 0) {
+        (void)hipLaunchKernel(tile, dim3(columns, (unsigned)bands), dim3(256), &args, 0, stream);
+        const int rc = sc_check_launch(who);
+        if (rc != SC_OK) return rc;
+    }
+    char reduction[96];
+    snprintf(reduction, sizeof reduction, "%s (reduction)", who);
+    return sc_rows5_reduce(reduction, partials, bands, M, out, cursor, stream);
 }

@@ -11,17 +11,14 @@
 //   x_ia = f_ia g_ia cq_i,   row a of the output: the five sums of x_ia over i (sc_rows5.h)
 //   Qc(t) = Qc cos wt + Pc / w sin wt,   Pc(t) = Pc cos wt - w Qc sin wt
 //
-// thermal_opcorr_tile_kernel: the tile mapping and the accumulators of opcorr_tile_kernel; after the staged loop over D a second one
-//   over the d'' modes, whose trajectory planes are the centres rotated WHILE STAGING.  A staging thread keeps one mode index k
-//   through a chunk (256 is a multiple of R5_CHUNK): cos, sin and 1 / w of the chunk's 16 modes are formed once per chunk and
-//   workgroup into a 48-double table.  th->map_q, map_p, q0, n1 are not read.
-// Discarded trajectories (`kept`) and the rows beyond n are staged as zero operands, and their cq, g and centres are never loaded.
-#include "sc_rows5.h"
+// thermal_opcorr_tile_kernel: opcorr_tile_kernel (the pieces of sc_optile.h) with a second staged loop between the loop over D and
+//   the finish, over the d'' modes, whose trajectory planes are the centres rotated WHILE STAGING.  A staging thread keeps one mode
+//   index k through a chunk (256 is a multiple of R5_CHUNK): cos, sin and 1 / w of the chunk's 16 modes are formed once per chunk
+//   and workgroup into a 48-double table.  th->map_q, map_p, q0, n1 are not read.  The centres of discarded trajectories and of the
+//   rows beyond n are never loaded either.
+#include "sc_optile.h"
 
 namespace {
-
-constexpr int STAGE_DOUBLES = 4 * R5_CHUNK * R5_ROW;       // a chunk of the two trajectory planes and the two operator planes
-constexpr int LDS_DOUBLES = STAGE_DOUBLES > R5_REDUCE_DOUBLES ? STAGE_DOUBLES : R5_REDUCE_DOUBLES;   // reused by the reduction
 
 struct ThermalOpcorrArgs {
     const double *qp;               // [n][2 D]
@@ -39,69 +36,19 @@ struct ThermalOpcorrArgs {
     double *partials;               // [bands][M][5]
 };
 
-typedef double stage_row[R5_ROW];
-
-// fr += yu (x) xq, fi += yw (x) xp over the staged chunk: the thread's 4 x 4 pairs
-__device__ __forceinline__ void chunk_fma(const stage_row *tq, const stage_row *tp, const stage_row *ku, const stage_row *kw, int ti,
-                                          int tj, double (&fr)[4][4], double (&fi)[4][4]) {
-#pragma unroll 4
-    for (int k = 0; k < R5_CHUNK; ++k) {
-        double xq[4], xp[4], yu[4], yw[4];
-        load4(&tq[k][4 * ti], xq); load4(&tp[k][4 * ti], xp);
-        load4(&ku[k][4 * tj], yu); load4(&kw[k][4 * tj], yw);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                fr[a][b] = fma(yu[b], xq[a], fr[a][b]);
-                fi[a][b] = fma(yw[b], xp[a], fi[a][b]);
-            }
-    }
-}
-
 __global__ __launch_bounds__(256) void thermal_opcorr_tile_kernel(ThermalOpcorrArgs A) {
-    __shared__ alignas(16) double lds[LDS_DOUBLES];
+    __shared__ OpTileLds lds;
     __shared__ double2 cqs[R5_TILE];// cq_i of the band's trajectories (0: beyond n, or discarded)
     __shared__ int live[R5_TILE];
     __shared__ double rot[3][R5_CHUNK];                    // cos w t, sin w t, 1 / w of the chunk's modes
-    stage_row *tq = (stage_row *)lds, *tp = tq + R5_CHUNK, *ku = tp + R5_CHUNK, *kw = ku + R5_CHUNK;
+    OpStage &S = lds.S;
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-    const int D = A.D, dm = A.dm, M = A.M;
+    const int dm = A.dm;
     const int64_t i0 = (int64_t)blockIdx.y * R5_TILE;
-    const int k0 = blockIdx.x * R5_TILE;
-    const int iv = (int)min((int64_t)R5_TILE, A.n - i0), kv = min(R5_TILE, M - k0);      // valid rows / operators of the tile
-    if (tid < R5_TILE) {
-        const int64_t tr = i0 + tid;
-        const bool in = tid < iv && (!A.kept || A.kept[tr]);
-        cqs[tid] = in ? ((const cplx *)A.cq)[tr] : c_make(0.0, 0.0);
-        live[tid] = in;
-    }
-    double fr[4][4], fi[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) { fr[a][b] = 0.0; fi[a][b] = 0.0; }
-    // the current points against u, w: the loop of opcorr_tile_kernel
-    for (int d0 = 0; d0 < D; d0 += R5_CHUNK) {
-        __syncthreads();                                   // live[] is written; the last readers of the chunk before are done
-        for (int e = tid; e < R5_CHUNK * R5_TILE; e += 256) {
-            const int r = e / R5_CHUNK, k = e - r * R5_CHUNK, d = d0 + k;      // row r of the tile, column k of the chunk
-            double q = 0.0, p = 0.0;
-            if (d < D && live[r]) {
-                const double *row = A.qp + (i0 + r) * 2 * D;
-                q = row[d]; p = row[D + d];
-            }
-            tq[k][r] = q; tp[k][r] = p;
-            double u = 0.0, w = 0.0;
-            if (d < D && r < kv) {
-                const size_t at = (size_t)(k0 + r) * D + d;
-                u = A.u[at]; w = A.w[at];
-            }
-            ku[k][r] = u; kw[k][r] = w;
-        }
-        __syncthreads();
-        chunk_fma(tq, tp, ku, kw, ti, tj, fr, fi);
-    }
+    const int k0 = blockIdx.x * R5_TILE, kv = min(R5_TILE, A.M - k0);          // the operators of the tile
+    optile_band_header(live, cqs, A.n, i0, A.kept, A.cq, tid);
+    double fr[4][4] = {}, fi[4][4] = {};
+    optile_staged_loop(S, live, A.qp, A.D, A.u, A.w, i0, k0, kv, tid, ti, tj, fr, fi);       // the current points against u, w
     // the rotated centres against ut, wt.  The table of chunk c + 1 is written after the second barrier of chunk c, behind which no
     // staging thread of chunk c reads it any more, and before the first barrier of chunk c + 1.
     for (int m0 = 0; m0 < dm; m0 += R5_CHUNK) {
@@ -127,38 +74,18 @@ __global__ __launch_bounds__(256) void thermal_opcorr_tile_kernel(ThermalOpcorrA
                 qt = fma(pc * iw, s, qc * c);
                 pt = fma(-om * qc, s, pc * c);
             }
-            tq[k][r] = qt; tp[k][r] = pt;
+            S.tq[k][r] = qt; S.tp[k][r] = pt;
             double u = 0.0, w = 0.0;
             if (mode < dm && r < kv) {
                 const size_t at = (size_t)(k0 + r) * dm + mode;
                 u = A.ut[at]; w = A.wt[at];
             }
-            ku[k][r] = u; kw[k][r] = w;
+            S.ku[k][r] = u; S.kw[k][r] = w;
         }
         __syncthreads();
-        chunk_fma(tq, tp, ku, kw, ti, tj, fr, fi);
+        optile_chunk_fma(S, ti, tj, fr, fi);
     }
-    // x_ia = f_ia g_ia cq_i; the thread's four trajectories are added per operator in registers
-    double sum[4][5];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c) sum[b][c] = 0.0;
-        const int op = 4 * tj + b;
-        const cplx kap = op < kv ? ((const cplx *)A.kap)[k0 + op] : c_make(0.0, 0.0);
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int r = 4 * ti + a;
-            cplx x = c_make(0.0, 0.0);
-            if (op < kv && live[r]) {
-                const cplx g = ((const cplx *)A.g)[(size_t)(i0 + r) * M + k0 + op];
-                const cplx f = c_make(kap.x + fr[a][b], kap.y + fi[a][b]);
-                x = c_mul(c_mul(f, g), cqs[r]);
-            }
-            rows5_add(sum[b], x);
-        }
-    }
-    rows5_store_partials(sum, lds, tid, ti, tj, kv, k0, M, A.partials);
+    optile_finish_linear(fr, fi, live, cqs, A.kap, A.g, i0, k0, kv, A.M, &lds, tid, ti, tj, A.partials);
 }
 
 // out[i][a] = k_a + u_a.z_i[:D] + i w_a.z_i[D:] + ut_a.c_i[:d''] + i wt_a.c_i[d'':], one (trajectory, operator) pair per thread,
@@ -170,17 +97,9 @@ __global__ __launch_bounds__(256) void thermal_opcorr_affine_kernel(const double
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int64_t i = e / M;
         const int a = (int)(e - i * M);
-        const double *row = z + i * 2 * D, *ua = u + (size_t)a * D, *wa = w + (size_t)a * D;
-        const double *crow = cen + i * 2 * dm, *uta = ut + (size_t)a * dm, *wta = wt + (size_t)a * dm;
         double re = 0.0, im = 0.0;
-        for (int d = 0; d < D; ++d) {
-            re = fma(ua[d], row[d], re);
-            im = fma(wa[d], row[D + d], im);
-        }
-        for (int k = 0; k < dm; ++k) {
-            re = fma(uta[k], crow[k], re);
-            im = fma(wta[k], crow[dm + k], im);
-        }
+        optile_affine_dot(u + (size_t)a * D, w + (size_t)a * D, z + i * 2 * D, D, re, im);
+        optile_affine_dot(ut + (size_t)a * dm, wt + (size_t)a * dm, cen + i * 2 * dm, dm, re, im);
         ((cplx *)out)[e] = c_make(kap[2 * a] + re, kap[2 * a + 1] + im);
     }
 }
@@ -205,9 +124,8 @@ extern "C" int sc_hk_opcorr_thermal_initial(const double *zi, const double *cent
     const int rc = thermal_opcorr_limits("sc_hk_opcorr_thermal_initial", n, D, dmodes, M);
     if (rc != SC_OK) return rc;
     if (n == 0) return SC_OK;
-    const int64_t blocks = (n * M + 255) / 256;
-    hipLaunchKernelGGL(thermal_opcorr_affine_kernel, dim3((unsigned)(blocks < 65535 ? blocks : 65535)), dim3(256), 0,
-                       (hipStream_t)stream, zi, centres, n, D, dmodes, ket_u, ket_w, ket_ut, ket_wt, ket_k, M, g);
+    hipLaunchKernelGGL(thermal_opcorr_affine_kernel, sc_optile_prepass_grid(n, M), dim3(256), 0, (hipStream_t)stream, zi, centres, n,
+                       D, dmodes, ket_u, ket_w, ket_ut, ket_wt, ket_k, M, g);
     return sc_check_launch("sc_hk_opcorr_thermal_initial");
 }
 
@@ -217,21 +135,14 @@ extern "C" int sc_hk_opcorr_thermal(const sc_state *st, double time, const sc_th
                                     double *out, const int64_t *cursor, void *stream) {
     if (!st || !th || !cq || !bra_u || !bra_w || !bra_ut || !bra_wt || !bra_k || !g || !partials || !out)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opcorr_thermal: null argument");
-    int rc = thermal_opcorr_limits("sc_hk_opcorr_thermal", st->n, st->dim, th->dmodes, M);
+    const int rc = thermal_opcorr_limits("sc_hk_opcorr_thermal", st->n, st->dim, th->dmodes, M);
     if (rc != SC_OK) return rc;
     if (!st->qp) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opcorr_thermal: the state has no qp");
     if (!th->omega || !th->centres || th->dim != st->dim)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opcorr_thermal: thermal constants for D = %d without omega or centres, state D = %d",
                        th->dim, st->dim);
-    const int64_t bands = sc_rows5_bands(st->n, M);
-    hipStream_t s = (hipStream_t)stream;
-    if (bands > 0) {
-        ThermalOpcorrArgs a{st->qp, st->n, st->dim, th->dmodes, M, time, th->omega, th->centres, cq, bra_u, bra_w, bra_ut, bra_wt,
-                            bra_k, g, kept, partials};
-        hipLaunchKernelGGL(thermal_opcorr_tile_kernel, dim3((unsigned)((M + R5_TILE - 1) / R5_TILE), (unsigned)bands), dim3(256), 0,
-                           s, a);
-        rc = sc_check_launch("sc_hk_opcorr_thermal");
-        if (rc != SC_OK) return rc;
-    }
-    return sc_rows5_reduce("sc_hk_opcorr_thermal (reduction)", partials, bands, M, out, cursor, s);
+    ThermalOpcorrArgs a{st->qp, st->n, st->dim, th->dmodes, M, time, th->omega, th->centres, cq, bra_u, bra_w, bra_ut, bra_wt,
+                        bra_k, g, kept, partials};
+    return sc_optile_rows("sc_hk_opcorr_thermal", (const void *)thermal_opcorr_tile_kernel, &a, (unsigned)((M + R5_TILE - 1) / R5_TILE),
+                          st->n, M, partials, out, cursor, (hipStream_t)stream);
 }

@@ -794,6 +794,10 @@ class HermanKlukPropagator(object):
         check(lib.sc_term_moments(ptr(self._cq), ptr(self._kq) if has_k else None, self.ntraj, ptr(self._mpart), self._stream()))
         return self._gterm
 
+    def _term_moments_into(self, has_k, moments):
+        """the six moment sums of the exported per-trajectory terms into the doubles at `moments`"""
+        check(lib.sc_reduce_moments(ptr(self._mpart), self._term_moments(has_k), C_void(moments), self._stream()))
+
     def _term_blocks(self, has_k, blk, cursor=None):
         """block sums of the exported per-trajectory terms _cq (and _kq) into the (B, 4) doubles at blk = (address, B), or into
         row *cursor of the (., B, 4) buffer there (the cursor is read, not advanced: launch before the reduction that advances it)"""
@@ -842,8 +846,7 @@ class HermanKlukPropagator(object):
             self._term_blocks(nac is not None, row.blocks)
         self._reduce_into(self._cpart, self._gcorr, row, None)
         if row.moments is not None:
-            rows = self._term_moments(nac is not None)
-            check(lib.sc_reduce_moments(ptr(self._mpart), rows, C_void(row.moments), s))
+            self._term_moments_into(nac is not None, row.moments)
 
     def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=(), time=None):
         """per-trajectory terms + their sums for the current state into `row` (_StepRows): the 5-double slot; the six second-moment
@@ -888,8 +891,7 @@ class HermanKlukPropagator(object):
                 self._term_blocks(True, blk)
             if mom_ptr is not None:
                 # k_ic terms formed by torch (position-dependent couplings): the moments of the exported terms
-                rows = self._term_moments(True)
-                check(lib.sc_reduce_moments(ptr(self._mpart), rows, C_void(mom_ptr), s))
+                self._term_moments_into(True, mom_ptr)
 
     def _correlate_current(self, need_nac):
         if self._corr_step == self._nsteps and (self._corr_has_nac or not need_nac):
@@ -1108,59 +1110,75 @@ class HermanKlukPropagator(object):
         """what the prepared operators are cached by: the bytes of (c, m, K) of both sides, an absent (or all-zero) K as nothing"""
         return tuple(b"" if t is None else t.numpy().tobytes() for t in tuple(A) + tuple(B))
 
-    def _operators(self, bra, ket=None):
-        """validated operators A_a = cA_a + mA_a.x + 1/2 x^T KA_a x (``bra``) and B_a (``ket``; None: the bra's, K included), their
-        folded vectors and the ket-side factors g [n][M] of the initial points on the device.  Without a K on either side: the
-        affine forms of hostmath.fold_linear_operators and sc_hk_opcorr_initial (section 4.14); with one: the columns of
-        hostmath.fold_quadratic_operators and sc_hk_opquad_initial (section 4.16), "RA" and "RB" in the dict.  Cached per set of
-        operators until the initial conditions change (_finish_state)."""
+    def _operator_pair(self, cache, bra, ket, refused, refused_k, fold, rows):
+        """The preparation of an operator pair, shared by both families: the class refusal, the family's refusal of the ensemble
+        (``refused``: an exception or None), both sides validated (``ket`` None: the bra's, K included), its refusal of a K
+        (``refused_k``), the count check; the prepared dict, cached in the attribute ``cache`` per set of operators until the initial
+        conditions change (_finish_state).  ``fold(A, B, M, g)``: the family's folded buffers on the device and its *_initial launch
+        into g, returns (bufs, further entries of the dict); ``rows``: its *_rows query."""
         if not self._opcorr_ok:
             raise NotImplementedError(f"{type(self).__name__} has no operator correlation functions: its Gaussians have "
                                       "per-trajectory widths and another prefactor")
-        if getattr(self, "_thermal", None) is not None:
-            raise NotImplementedError("an operator correlation function is not available with a thermal ensemble: the folded "
-                                      "operators take the one centre (q0, p0); the trace over the ensemble is "
-                                      "thermal_operator_correlation() / run(thermal_operators=...)")
-        cA, mA, KA = self._operator_side("bra", bra)
-        cB, mB, KB = (cA, mA, KA) if ket is None else self._operator_side("ket", ket)
-        if cB.shape != cA.shape:
-            raise ValueError(f"operators: bra and ket have to hold the same number of operators, got {cA.shape[0]} and {cB.shape[0]}")
-        key = self._operators_key((cA, mA, KA), (cB, mB, KB))
-        hit = self._opcorr
+        if refused is not None:
+            raise refused
+        A = self._operator_side("bra", bra)
+        B = A if ket is None else self._operator_side("ket", ket)
+        if refused_k is not None and (A[2] is not None or B[2] is not None):
+            raise refused_k
+        if B[0].shape != A[0].shape:
+            raise ValueError(f"operators: bra and ket have to hold the same number of operators, got {A[0].shape[0]} and {B[0].shape[0]}")
+        key = self._operators_key(A, B)
+        hit = getattr(self, cache)
         if hit is not None and hit["key"] == key:
             return hit
-        M, dev = int(cA.shape[0]), self.device
-        g = torch.empty((self.ntraj, M), dtype=C128, device=dev)
-        host = (self._G0h, self._q0h, self._p0h)
-        if KA is None and KB is None:
-            uA, wA, kA = hostmath.fold_linear_operators(cA, mA, self._Gt, *host, ket=False)
-            uB, wB, kB = hostmath.fold_linear_operators(cB, mB, self._Gi, *host, ket=True)
+        M = int(A[0].shape[0])
+        g = torch.empty((self.ntraj, M), dtype=C128, device=self.device)
+        bufs, more = fold(A, B, M, g)
+        partials = torch.empty(max(int(rows(self.ntraj, M)) * M * 5, 1), dtype=F64, device=self.device)
+        numpy_set = lambda c, m, K: (c.numpy(), m.numpy()) + (() if K is None else (K.numpy(),))
+        setattr(self, cache, {"key": key, "M": M, "bra": numpy_set(*A), "ket": numpy_set(*B), "bufs": bufs, "g": g,
+                              "partials": partials, **more})
+        return getattr(self, cache)
+
+    def _operators(self, bra, ket=None):
+        """validated operators A_a = cA_a + mA_a.x + 1/2 x^T KA_a x (``bra``) and B_a (``ket``), their folded vectors and the
+        ket-side factors g [n][M] of the initial points on the device (_operator_pair, _fold_operators)"""
+        refused = None if getattr(self, "_thermal", None) is None else NotImplementedError(
+            "an operator correlation function is not available with a thermal ensemble: the folded operators take the one centre "
+            "(q0, p0); the trace over the ensemble is thermal_operator_correlation() / run(thermal_operators=...)")
+        return self._operator_pair("_opcorr", bra, ket, refused, None, self._fold_operators, lib.sc_hk_opcorr_rows)
+
+    def _fold_operators(self, A, B, M, g):
+        """Without a K on either side: the affine forms of hostmath.fold_linear_operators and sc_hk_opcorr_initial (section 4.14);
+        with one: the columns of hostmath.fold_quadratic_operators and sc_hk_opquad_initial (section 4.16), and the ranks"""
+        dev, host = self.device, (self._G0h, self._q0h, self._p0h)
+        if A[2] is None and B[2] is None:
+            uA, wA, kA = hostmath.fold_linear_operators(*A[:2], self._Gt, *host, ket=False)
+            uB, wB, kB = hostmath.fold_linear_operators(*B[:2], self._Gi, *host, ket=True)
             bufs = [t.to(dev) for t in (uA, wA, kA, uB, wB, kB)]
             check(lib.sc_hk_opcorr_initial(ptr(self._zi_t), self.ntraj, self.dim, ptr(bufs[3]), ptr(bufs[4]), ptr(bufs[5]), M, ptr(g),
                                            self._stream()))
-            ranks = {}
-        else:
-            *colsA, RA = hostmath.fold_quadratic_operators(cA, mA, KA, self._Gt, *host, ket=False)
-            *colsB, RB = hostmath.fold_quadratic_operators(cB, mB, KB, self._Gi, *host, ket=True)
-            bufs = [t.to(dev) for t in colsA + colsB]      # (u, w, kappa, lambda) of the bra, then of the ket
-            check(lib.sc_hk_opquad_initial(ptr(self._zi_t), self.ntraj, self.dim, ptr(bufs[4]), ptr(bufs[5]), ptr(bufs[6]),
-                                           ptr(bufs[7]), M, RB, ptr(g), self._stream()))
-            ranks = {"RA": RA, "RB": RB}
-        partials = torch.empty(max(int(lib.sc_hk_opcorr_rows(self.ntraj, M)) * M * 5, 1), dtype=F64, device=dev)
-        numpy_set = lambda c, m, K: (c.numpy(), m.numpy()) + (() if K is None else (K.numpy(),))
-        self._opcorr = {"key": key, "M": M, "bra": numpy_set(cA, mA, KA), "ket": numpy_set(cB, mB, KB), "bufs": bufs, "g": g,
-                        "partials": partials, **ranks}
-        return self._opcorr
+            return bufs, {}
+        *colsA, RA = hostmath.fold_quadratic_operators(*A, self._Gt, *host, ket=False)
+        *colsB, RB = hostmath.fold_quadratic_operators(*B, self._Gi, *host, ket=True)
+        bufs = [t.to(dev) for t in colsA + colsB]          # (u, w, kappa, lambda) of the bra, then of the ket
+        check(lib.sc_hk_opquad_initial(ptr(self._zi_t), self.ntraj, self.dim, ptr(bufs[4]), ptr(bufs[5]), ptr(bufs[6]),
+                                       ptr(bufs[7]), M, RB, ptr(g), self._stream()))
+        return bufs, {"RA": RA, "RB": RB}
 
-    def _prepare_operators(self, operators):
-        """run(operators=...): the caller's (bra, ket), or bra alone, into the prepared dict of _operators"""
+    def _parse_operator_pair(self, operators, sets):
+        """the (bra, ket), or bra alone, of run() as (bra, ket or None); ``sets``: one side of the family, for the error text"""
         if self._is_operator_set(operators):
             operators = (operators, None)
         try:
             bra, ket = operators
         except (TypeError, ValueError):
-            raise ValueError("operators: (bra, ket) or bra, each (c, m) or (c, m, K) of arrays (M,), (M, D) and (M, D, D), is expected")
-        return self._operators(bra, ket)
+            raise ValueError(f"operators: (bra, ket) or bra, each {sets}, is expected")
+        return bra, ket
+
+    def _prepare_operators(self, operators):
+        """run(operators=...): the prepared dict of _operators"""
+        return self._operators(*self._parse_operator_pair(operators, "(c, m) or (c, m, K) of arrays (M,), (M, D) and (M, D, D)"))
 
     def _launch_opcorr(self, operators, out_ptr, state=None, cursor=None):
         """the (M, 5) operator-correlation sums of `state` (default: the current one) from the terms _cq the correlate kernel has
@@ -1192,56 +1210,42 @@ class HermanKlukPropagator(object):
         have given without the call.  ``ValueError`` for operators of the wrong shape, with non-finite entries, M = 0, a K that is
         not symmetric, or a vector m or an eigenvector of K (eigenvalue above 1e-12 of the largest) outside the range of
         Gamma_0 + Gamma_t (bra) or Gamma_i + Gamma_0 (ket)."""
-        operators = self._operators(bra, ket)
+        return self._current_operator_rows(_OPERATOR_ROWS, self._operators(bra, ket), energy0_es, standard_errors)
+
+    def _current_operator_rows(self, family, operators, energy0_es, standard_errors):
+        """X, or (X, sigma), of the current step: the correlate kernel and the launch of ``family`` into one raw row.  Synchronises."""
         out = torch.zeros((1, operators["M"], 5), dtype=F64, device=self.device)
         slot = torch.zeros(8, dtype=F64, device=self.device)
-        self._launch_correlate(self._rows.single(slot, opcorr=out), families=((_OPERATOR_ROWS, operators),))
+        self._launch_correlate(self._rows.single(slot, opcorr=out), families=((family, operators),))
         return self._current_five_sums(out, energy0_es, standard_errors)
 
     # ---- operator correlation functions of a thermal ensemble, linear operators (not in the reference; DESIGN.md section 4.20) ----
     def _thermal_operators(self, bra, ket=None):
-        """``_operators`` for the active thermal ensemble: validated linear operators, the folded vectors of
-        hostmath.fold_thermal_linear_operators -- (u, w, ut, wt, kappa) of the bra, then of the ket -- and the ket-side factors
-        g [n][M] of sc_hk_opcorr_thermal_initial.  Cached per set of operators until the initial conditions change."""
-        if not self._opcorr_ok:
-            raise NotImplementedError(f"{type(self).__name__} has no operator correlation functions: its Gaussians have "
-                                      "per-trajectory widths and another prefactor")
-        if self._thermal is None:
-            raise ValueError("thermal operators need a thermal ensemble (thermal_initial_conditions): the expectation value in "
-                             "the one state phi_0 is operator_correlation() / run(operators=...)")
-        cA, mA, KA = self._operator_side("bra", bra)
-        cB, mB, KB = (cA, mA, KA) if ket is None else self._operator_side("ket", ket)
-        if KA is not None or KB is not None:
-            raise NotImplementedError("quadratic operators (a K) are not available with a thermal ensemble: "
-                                      "thermal_operator_correlation() takes linear operators (c, m)")
-        if cB.shape != cA.shape:
-            raise ValueError(f"operators: bra and ket have to hold the same number of operators, got {cA.shape[0]} and {cB.shape[0]}")
-        key = self._operators_key((cA, mA), (cB, mB))
-        hit = self._thermal_opcorr
-        if hit is not None and hit["key"] == key:
-            return hit
-        M, dev, th = int(cA.shape[0]), self.device, self._thermal
+        """``_operators`` for the active thermal ensemble: validated linear operators, their folded vectors and the ket-side factors
+        g [n][M] on the device (_operator_pair, _fold_thermal_operators)"""
+        refused = None if self._thermal is not None else ValueError(
+            "thermal operators need a thermal ensemble (thermal_initial_conditions): the expectation value in the one state phi_0 "
+            "is operator_correlation() / run(operators=...)")
+        refused_k = NotImplementedError("quadratic operators (a K) are not available with a thermal ensemble: "
+                                        "thermal_operator_correlation() takes linear operators (c, m)")
+        return self._operator_pair("_thermal_opcorr", bra, ket, refused, refused_k, self._fold_thermal_operators,
+                                   lib.sc_hk_opcorr_thermal_rows)
+
+    def _fold_thermal_operators(self, A, B, M, g):
+        """the folded vectors of hostmath.fold_thermal_linear_operators -- (u, w, ut, wt, kappa) of the bra, then of the ket -- and
+        sc_hk_opcorr_thermal_initial"""
+        th = self._thermal
         tc = th["consts"]
-        folded = (hostmath.fold_thermal_linear_operators(cA, mA, self._Gt, self._G0h, self._q0h, tc, ket=False)
-                  + hostmath.fold_thermal_linear_operators(cB, mB, self._Gi, self._G0h, self._q0h, tc, ket=True))
-        bufs = [folded[i].to(dev) for i in (0, 1, 3, 4, 2, 5, 6, 8, 9, 7)]        # (u, w, ut, wt, kappa) twice
-        g = torch.empty((self.ntraj, M), dtype=C128, device=dev)
+        folded = (hostmath.fold_thermal_linear_operators(*A[:2], self._Gt, self._G0h, self._q0h, tc, ket=False)
+                  + hostmath.fold_thermal_linear_operators(*B[:2], self._Gi, self._G0h, self._q0h, tc, ket=True))
+        bufs = [folded[i].to(self.device) for i in (0, 1, 3, 4, 2, 5, 6, 8, 9, 7)]        # (u, w, ut, wt, kappa) twice
         check(lib.sc_hk_opcorr_thermal_initial(ptr(self._zi_t), ptr(th["centres"]), self.ntraj, self.dim, tc.dmodes, ptr(bufs[5]),
                                                ptr(bufs[6]), ptr(bufs[7]), ptr(bufs[8]), ptr(bufs[9]), M, ptr(g), self._stream()))
-        partials = torch.empty(max(int(lib.sc_hk_opcorr_thermal_rows(self.ntraj, M)) * M * 5, 1), dtype=F64, device=dev)
-        self._thermal_opcorr = {"key": key, "M": M, "bra": (cA.numpy(), mA.numpy()), "ket": (cB.numpy(), mB.numpy()),
-                                "bufs": bufs, "g": g, "partials": partials}
-        return self._thermal_opcorr
+        return bufs, {}
 
     def _prepare_thermal_operators(self, operators):
-        """run(thermal_operators=...): the caller's (bra, ket), or bra alone, into the prepared dict of _thermal_operators"""
-        if self._is_operator_set(operators):
-            operators = (operators, None)
-        try:
-            bra, ket = operators
-        except (TypeError, ValueError):
-            raise ValueError("operators: (bra, ket) or bra, each (c, m) of arrays (M,) and (M, D), is expected")
-        return self._thermal_operators(bra, ket)
+        """run(thermal_operators=...): the prepared dict of _thermal_operators"""
+        return self._thermal_operators(*self._parse_operator_pair(operators, "(c, m) of arrays (M,) and (M, D)"))
 
     def _launch_thermal_opcorr(self, operators, out_ptr, state=None, time=None, cursor=None):
         """the (M, 5) thermal operator-correlation sums of `state` (default: the current one), whose clock reads `time` (None:
@@ -1268,11 +1272,7 @@ class HermanKlukPropagator(object):
         ``ValueError`` without a thermal ensemble (the quantity is ``operator_correlation`` then), for operators of the wrong
         shape, with non-finite entries, M = 0, another M on the ket, or a vector m outside the range of Gamma_0 + Gamma_t (bra) or
         Gamma_i + Gamma_0 (ket); ``NotImplementedError`` for operators with a K."""
-        operators = self._thermal_operators(bra, ket)
-        out = torch.zeros((1, operators["M"], 5), dtype=F64, device=self.device)
-        slot = torch.zeros(8, dtype=F64, device=self.device)
-        self._launch_correlate(self._rows.single(slot, opcorr=out), families=((_THERMAL_OPERATOR_ROWS, operators),))
-        return self._current_five_sums(out, energy0_es, standard_errors)
+        return self._current_operator_rows(_THERMAL_OPERATOR_ROWS, self._thermal_operators(bra, ket), energy0_es, standard_errors)
 
     def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
             targets=None, cross=None, operators=None, opcorr=None, time_average=None, thermal_operators=None, thermal_opcorr=None):

@@ -278,6 +278,23 @@ def test_correlation_terms_are_defined_once_in_the_source():
     assert corr.count("p0n1 +") == 1 and "nac_initial_kernel" in corr.split("p0n1 +")[0].rsplit("__global__", 1)[1]
 
 
+def test_operator_tile_is_defined_once_in_the_source():
+    """the 4 x 4 FMA pair of the operator tile kernels is written out in csrc/sc_optile.h alone; the 16-byte reads of a staged chunk
+    stand in the tile headers only (their definition, load4, in sc_rows5.h); and no file that includes sc_optile.h selects the live
+    trajectories of a band itself: sc_opcorr.hip, sc_opquad.hip and sc_thermal_opcorr.hip call optile_band_header,
+    optile_staged_loop and optile_chunk_fma"""
+    import glob
+    csrc = os.path.join(ROOT, "semiclassical_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) > 20
+    holders = lambda needle: [os.path.basename(f) for f in files if needle in open(f).read()]
+    assert holders("fma(yu[b]") == ["sc_optile.h"]
+    assert set(holders("load4(&")) <= {"sc_rows5.h", "sc_cross_tile.h", "sc_optile.h"} and "sc_optile.h" in holders("load4(&")
+    users = holders('#include "sc_optile.h"')
+    assert {"sc_opcorr.hip", "sc_opquad.hip", "sc_thermal_opcorr.hip"} <= set(users)
+    assert not set(users) & set(holders("!A.kept || A.kept[tr]"))
+
+
 def test_normal_mode_step_matrices_reproduce_the_full_step_matrix():
     """MolecularHarmonicPotential._normal_modes (sc_hk_run_modal): T blockdiag-by-mode(phi) T^-1 with T = diag(A, B) is the RK4 step
     matrix Phi(dt) of _step_matrix, including zero-frequency modes (free motion) and a wide mass ratio"""

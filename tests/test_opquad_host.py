@@ -223,10 +223,10 @@ def test_refusals():
                 (c, m, good, good)):
         with pytest.raises(ValueError):
             side(ops)
-    # a ket with another M: refused by _operators before anything touches the device
+    # a ket with another M: refused by the preparation of the pair before anything touches the device
     prop = types.SimpleNamespace(_opcorr_ok=True, _operator_side=lambda name, ops: HK._operator_side(stub, name, ops))
     with pytest.raises(ValueError, match="same number"):
-        HK._operators(prop, (c, m, good), (np.zeros(3), np.zeros((3, D)), None))
+        HK._operator_pair(prop, "_opcorr", (c, m, good), (np.zeros(3), np.zeros((3, D)), None), None, None, None, None)
 
 
 # ------------------------------------------------------------------------------------------- 4. equivalent inputs
