@@ -528,6 +528,24 @@ int sc_density_pair_sum(const double *X1, const double *Y1, int32_t K1, const do
                         const double *a_ket, const double *b_ket, const double *inv_two_sigma2, int32_t M,
                         const double *s, const double *s_origin, int32_t ns, double *partials, double *rho, void *stream);
 
+/* Expectation values of M quadratic operators in the frozen-Gaussian wavepacket, behind HermanKlukPropagator.expectation() (not in
+ * the reference):
+ *   out[a] = sum_ij T_ij (kap[a] + sum_col lam[col] z_col^p),  a < M,      out[M] = sum_ij T_ij      (complex),
+ * T_ij = wb_i wk_j exp(E_ij) the pair term of sc_pair_sum_rect from the same operands X1 ... wk, z_col = za[col][i] + zb[col][j], the
+ * sum over the 1 + R columns col = a (1 + R) + r of operator a: r = 0 to the first power (p = 1), r = 1 ... R squared (p = 2).
+ *   za [M (1 + R)][ni], zb [M (1 + R)][nj] complex (trajectory index fastest), lam [M (1 + R)] real, kap [M] complex,
+ *   out [M + 1] complex; partials: scratch of sc_pair_expect_tiles(ni, nj) * (M + 1) * 2 doubles, free again when the call's work
+ *   on `stream` has run.
+ * Two launches; one writer per output, no floating-point atomics, nothing skipped by magnitude, summation order a function of
+ * (ni, nj, M, R) alone: the same bits in every run.  The limits of sc_pair_sum_rect, 1 <= M <= 65535, 0 <= R <= 512,
+ * M (1 + R) < 2^24; beyond: SC_ERR_UNSUPPORTED.  A null pointer, M < 1, R < 0 or K < 0: SC_ERR_BAD_ARGUMENT.  ni <= 0 or nj <= 0:
+ * out = 0. */
+int64_t sc_pair_expect_tiles(int64_t ni, int64_t nj);
+int sc_pair_expect(const double *X1, const double *Y1, int32_t K1, const double *X2, const double *Y2, int32_t K2,
+                   const double *rs_i, const double *rs_j, const double *ib, const double *ik, const double *wb,
+                   const double *wk, int64_t ni, int64_t nj, const double *za, const double *zb, const double *lam,
+                   const double *kap, int32_t M, int32_t R, double *partials, double *out, void *stream);
+
 /* Cross-correlation of the Herman-Kluk wavepacket with K target coherent states |q_k, p_k, Gamma_0>, behind
  * HermanKlukPropagator.cross_correlation() and run(targets=...) (not in the reference, whose CoherentStatesOverlap,
  * propagators.py:181-240, defines the overlap).  With dq = q_k - q_i, dp = p_k - p_i and A, B, C, fac the

@@ -238,6 +238,16 @@ def fold_thermal_linear_operators(c, m, G_traj, G_0, q0, tc, ket):
     return u, w, kappa, ut.contiguous(), wt.contiguous()
 
 
+def _kept_eigenpairs(Ka, a, name):
+    """(lambda_r, v_r as rows) of the symmetric matrix ``Ka`` of operator ``a`` without the pairs of |lambda_r| <= 1e-12 max |lambda|;
+    ValueError for a matrix that is not symmetric to 1e-12 of its largest entry"""
+    if float(abs(Ka - Ka.T).max()) > 1.0e-12 * float(abs(Ka).max()):
+        raise ValueError(f"operators: {name} of operator {a} is not symmetric")
+    lam, vec = _eigh(0.5 * (Ka + Ka.T))
+    big = abs(lam) > 1.0e-12 * float(abs(lam).max())
+    return lam[big], vec[:, big].T.contiguous()
+
+
 def fold_quadratic_operators(c, m, K, G_traj, G_0, q0, p0, ket):
     """(u, w, kappa, lam, R): the Gaussian matrix element of the quadratic operators c_a + m_a.x + 1/2 x^T K_a x between phi_0 and a
     trajectory's Gaussian, divided by their overlap, as 1 + R COLUMNS per operator.  With x the complex
@@ -263,11 +273,7 @@ def fold_quadratic_operators(c, m, K, G_traj, G_0, q0, p0, ket):
         k0 = k0.clone()
         for a in range(M):
             Ka = K[a]
-            if float(abs(Ka - Ka.T).max()) > 1.0e-12 * float(abs(Ka).max()):
-                raise ValueError(f"operators: K of operator {a} is not symmetric")
-            lam, vec = _eigh(0.5 * (Ka + Ka.T))
-            big = abs(lam) > 1.0e-12 * float(abs(lam).max())
-            kept.append((lam[big], vec[:, big].T.contiguous()))
+            kept.append(_kept_eigenpairs(Ka, a, "K"))
             k0[a] += 0.5 * float(torch.sum(Ka * S))         # tr(K S), both symmetric
     R = max((int(lam.shape[0]) for lam, _ in kept), default=0)
     u, w = torch.zeros((M, 1 + R, D), dtype=torch.float64), torch.zeros((M, 1 + R, D), dtype=torch.float64)
@@ -292,6 +298,91 @@ def fold_quadratic_operators(c, m, K, G_traj, G_0, q0, p0, ket):
         u[a, 1:1 + r], w[a, 1:1 + r], kappa[a, 1:1 + r], lam_out[a, 1:1 + r] = ur[at:at + r], wr[at:at + r], kr[at:at + r], 0.5 * lam
         at += r
     return u, w, kappa, lam_out, R
+
+
+def fold_expectation_operators(c, m, K, n, W, Gamma_t):
+    """(uq, up, lam, kappa, R): the matrix element of the operators  c_a + m_a.x + 1/2 x^T K_a x + n_a.p + 1/2 p^T W_a p  between two
+    Gaussians |q_i, p_i, Gamma_t>, |q_j, p_j, Gamma_t> of ONE width, divided by their overlap, as 1 + R columns per operator
+    (DESIGN.md section 4.21).  With B = (2 Gamma_t)^+ and the complex pair means
+        xbar = (q_i + q_j) / 2 + i B (p_j - p_i) / hbar,    pbar = (p_i + p_j) / 2 + i hbar Gamma_t (q_i - q_j) / 2
+    the element is  kappa_a + sum_col lam_col z_col^(p_col),  z_col = a_i + conj(a_j),  a_i = uq_col.q_i + up_col.p_i:
+        a linear form v.xbar has uq = v / 2, up = -i B v / hbar;   a form v.pbar has up = v / 2, uq = i hbar Gamma_t v / 2;
+    column 0 (p = 1, lam = 1) is the sum of the x-form of m and the p-form of n, columns 1 ... R (p = 2, lam = lambda_r / 2) the kept
+    eigenpairs of K (x-forms), then of W (p-forms), by the drop rule of ``fold_quadratic_operators``;
+    kappa_a = c_a + 1/2 tr(K_a B) + hbar^2 / 4 tr(W_a Gamma_t).  R is the largest number of columns kept by an operator, the others
+    are padded with columns of zeros.
+    c (M,), m, n (M, D), K, W (M, D, D) real, any of them None (= zeros) but not all; returns complex (M, 1 + R, D) twice, real
+    (M, 1 + R), complex (M,) and R.  ValueError for shapes that do not agree, a non-finite entry, a K or W that is not symmetric to
+    1e-12 of its largest entry, and an m, n or kept eigenvector outside the range of Gamma_t (relative 1e-8, the test of
+    reduced_density), naming the operator."""
+    Gamma_t = as_f64(Gamma_t)
+    D = Gamma_t.shape[0]
+    parts = {}
+    for name, val, tail in (("c", c, ()), ("x", m, (D,)), ("xx", K, (D, D)), ("p", n, (D,)), ("pp", W, (D, D))):
+        if val is None:
+            continue
+        try:
+            t = as_f64(val)
+        except (TypeError, ValueError, RuntimeError) as err:
+            raise ValueError(f"operators: {name}: a real array is expected ({err})")
+        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+            raise ValueError(f"operators: {name} of shape {('M',) + tail} is expected, got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"operators: non-finite entry in {name}")
+        parts[name] = t
+    if not parts:
+        raise ValueError("operators: at least one of c, x, xx, p, pp has to be given")
+    counts = {name: int(t.shape[0]) for name, t in parts.items()}
+    M = next(iter(counts.values()))
+    if M < 1 or any(v != M for v in counts.values()):
+        raise ValueError(f"operators: the parts have to hold the same number M >= 1 of operators, got {counts}")
+    e, V = _eigh(Gamma_t)
+    keep = abs(e) > ZERO
+    Vk = V[:, keep]
+    B = torch.einsum('ij,j,kj->ik', Vk, 0.5 / e[keep], Vk)          # (2 Gamma_t)^+
+
+    def in_range(vec, a, what):
+        outside = torch.linalg.norm(vec - (vec @ Vk) @ Vk.T, dim=1) > 1.0e-8 * torch.linalg.norm(vec, dim=1)
+        if bool(outside.any()):
+            raise ValueError(f"operators: {what} of operator {a} has a component outside the range of Gamma_t: the matrix element "
+                             "along a null direction does not exist")
+
+    x_form = lambda vec: (torch.complex(0.5 * vec, torch.zeros_like(vec)), torch.complex(torch.zeros_like(vec), -(vec @ B) / hbar))
+    p_form = lambda vec: (torch.complex(torch.zeros_like(vec), 0.5 * hbar * (vec @ Gamma_t)), torch.complex(0.5 * vec, torch.zeros_like(vec)))
+    kappa = torch.zeros(M, dtype=C128)
+    if "c" in parts:
+        kappa += parts["c"]
+    cols = []                                               # per operator: (lam, uq, up) of the squared columns
+    for a in range(M):
+        lam_a, uq_a, up_a = [], [], []
+        for name, form, weight in (("xx", x_form, B), ("pp", p_form, 0.5 * hbar ** 2 * Gamma_t)):
+            if name not in parts:
+                continue
+            Ma = parts[name][a]
+            lam, vec = _kept_eigenpairs(Ma, a, name)
+            in_range(vec, a, name)
+            kappa[a] += 0.5 * float(torch.sum(Ma * weight))   # 1/2 tr(K B), hbar^2 / 4 tr(W Gamma_t): both factors symmetric
+            uq, up = form(vec)
+            lam_a.append(0.5 * lam)
+            uq_a.append(uq)
+            up_a.append(up)
+        cols.append((torch.cat(lam_a), torch.cat(uq_a), torch.cat(up_a)) if lam_a else None)
+    R = max((int(t[0].shape[0]) for t in cols if t is not None), default=0)
+    uq, up = torch.zeros((M, 1 + R, D), dtype=C128), torch.zeros((M, 1 + R, D), dtype=C128)
+    lam_out = torch.zeros((M, 1 + R), dtype=torch.float64)
+    lam_out[:, 0] = 1.0
+    for name, form in (("x", x_form), ("p", p_form)):
+        if name in parts:
+            for a in range(M):
+                in_range(parts[name][a:a + 1], a, name)
+            fq, fp = form(parts[name])
+            uq[:, 0] += fq
+            up[:, 0] += fp
+    for a, t in enumerate(cols):
+        if t is not None:
+            r = int(t[0].shape[0])
+            lam_out[a, 1:1 + r], uq[a, 1:1 + r], up[a, 1:1 + r] = t
+    return uq.contiguous(), up.contiguous(), lam_out.contiguous(), kappa.contiguous(), R
 
 
 def time_grid(nt, dt):

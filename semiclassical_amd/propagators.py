@@ -2066,6 +2066,127 @@ class HermanKlukPropagator(object):
                                           ns, ptr(partials), ptr(rho), self._stream()))
         return rho[:, :, 0].cpu().numpy()
 
+    def _pair_operands(self):
+        """the rank-local operands of the pair exponent as ``norm()`` packs them (positions centred on the ensemble mean):
+        (X1, Y1, X2, Y2, rs, ib, ik, wb, wk) on the device"""
+        dev, d, n = self.device, self.dim, self.ntraj
+        oc = hostmath.OverlapConstants(self._Gt, self._Gt)
+        A, B, Cm = (m.to(dev) for m in (oc.A, oc.B, oc.C))
+        q = self._qp[:, :d] - (self._qp[:, :d].sum(0) / float(n)).unsqueeze(0)
+        p = self._qp[:, d:]
+        Aq, Bp, Cp = q @ A.T, p @ B.T / hbar ** 2, p @ Cm.T / hbar
+        # exponent_ij = rs_i + rs_j + X1_i.Y1_j + i (ib_i + ik_j + X2_i.Y2_j)
+        X1 = torch.cat((q, p), 1).contiguous()
+        Y1 = torch.cat((Aq, Bp), 1).contiguous()
+        X2 = torch.cat((q, Cp, q), 1).contiguous()
+        Y2 = torch.cat((p / hbar, -q, -Cp), 1).contiguous()
+        rs = (-0.5 * (q * Aq).sum(1) - 0.5 * (p * Bp).sum(1)).contiguous()
+        cc = (q * Cp).sum(1)
+        ib = cc.contiguous()
+        ik = (cc - (p * q).sum(1) / hbar).contiguous()
+        v = self.coefficients()
+        return X1, Y1, X2, Y2, rs, ib, ik, (oc.fac * v.conj()).contiguous(), v.contiguous()
+
+    def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True):
+        """Expectation values of M quadratic operators in the wavepacket (not in the reference):
+
+            A_a = c_a + x_a.x + 1/2 x^T xx_a x + p_a.p + 1/2 p^T pp_a p        (p = -i hbar d/dx; no x-p cross terms),
+            E_a = <psi|A_a|psi> = sum_ij v_i^* v_j O_ij F_a,ij,      N2 = sum_ij v_i^* v_j O_ij = norm()**2,
+
+        O_ij the overlaps and v the coefficients of ``norm()``, F_a,ij the Gaussian matrix element of A_a divided by the overlap
+        (``hostmath.fold_expectation_operators``).  ``c`` (M,), ``x``, ``p`` (M, D), ``xx``, ``pp`` (M, D, D) real symmetric; any
+        of them may be None (= zeros), M is taken from the ones given.  Returns ``(values, norm2)``: the complex ndarray (M,) of
+        E_a / N2 -- of E_a with ``normalise=False`` -- and the float N2.  The imaginary part of the value of a Hermitian operator is
+        rounding.
+
+        For a singular Gamma_t every x_a, p_a and eigenvector of xx_a, pp_a (eigenvalues above 1e-12 of the largest) has to lie
+        in the range of Gamma_t: ``ValueError`` naming the operator otherwise, as for parts whose shapes do not agree, a
+        non-symmetric xx or pp and non-finite entries.  The value is then the formula with the pseudo-inverse conventions of the
+        overlaps.
+
+        The pair sum runs in ``sc_pair_expect`` on the operands ``norm()`` packs.  Rank-local: this rank's trajectories with
+        this rank's weights, no communication.  The discard mask (discard_nonsymplectic) is ignored: discarded trajectories
+        contribute as ever.  No step is taken and the state is not touched.  The value is quadratic in the ensemble, not
+        additive over batches: there is no hook in ``run()``."""
+        self._refuse_thermal("expectation()", "it describes one pure state, the trajectories belong to a mixture")
+        dev, d, n = self.device, self.dim, self.ntraj
+        uq, up, lam, kap, R = hostmath.fold_expectation_operators(c, x, xx, p, pp, self._Gt)
+        M = int(kap.shape[0])
+        X1, Y1, X2, Y2, rs, ib, ik, wb, wk = self._pair_operands()
+        # the columns a_i = uq.q_i + up.p_i from the actual positions, [M (1 + R)][n]; the kets take the conjugates
+        qT, pT = self._qp[:, :d].T, self._qp[:, d:].T
+        uq, up = uq.reshape(-1, d).to(dev), up.reshape(-1, d).to(dev)
+        zre, zim = uq.real @ qT + up.real @ pT, uq.imag @ qT + up.imag @ pT
+        za, zb = torch.complex(zre, zim).contiguous(), torch.complex(zre, -zim).contiguous()
+        lam_d, kap_d = lam.reshape(-1).to(dev).contiguous(), kap.to(dev).contiguous()
+        tiles = lib.sc_pair_expect_tiles(n, n)
+        partials = torch.empty((max(int(tiles), 1), M + 1, 2), dtype=F64, device=dev)
+        out = torch.empty(M + 1, dtype=C128, device=dev)
+        with self._timed("expectation"):
+            check(lib.sc_pair_expect(ptr(X1), ptr(Y1), 2 * d, ptr(X2), ptr(Y2), 3 * d, ptr(rs), ptr(rs), ptr(ib), ptr(ik), ptr(wb),
+                                     ptr(wk), n, n, ptr(za), ptr(zb), ptr(lam_d), ptr(kap_d), M, R, ptr(partials), ptr(out),
+                                     self._stream()))
+        res = out.cpu().numpy()
+        norm2 = float(res[M].real)
+        return (res[:M] / norm2 if normalise else res[:M].copy()), norm2
+
+    def _width_has_full_rank(self):
+        """no eigenvalue of Gamma_t below the threshold of the pseudo-inverses"""
+        return bool((abs(torch.linalg.eigvalsh(hostmath.as_f64(self._Gt))) > hostmath.ZERO).all())
+
+    def wavepacket_moments(self, directions=None):
+        """Centre and widths of the wavepacket along chosen directions u: a dict with ``x`` = <u.x>, ``p`` = <u.p>, ``var_x`` =
+        <(u.x)^2> - <u.x>^2, ``var_p`` = <(u.p)^2> - <u.p>^2, real ndarrays (M,) of the values normalised with ``norm2`` = norm()**2,
+        which comes along.  ``directions`` as in ``reduced_density``: mode indices or vectors of length D; None means the D axes,
+        for a Gamma_t of full rank only (``ValueError`` otherwise: give directions in its range).  One ``expectation`` call with
+        four operators per direction; what is said there about ranks, the discard mask and the state holds here."""
+        self._refuse_thermal("wavepacket_moments()", "it describes one pure state, the trajectories belong to a mixture")
+        d = self.dim
+        if directions is None:
+            if not self._width_has_full_rank():
+                raise ValueError("wavepacket_moments: Gamma_t is singular, the moments along its null directions do not exist: give "
+                                 "directions in the range of Gamma_t")
+            U = torch.eye(d, dtype=F64)
+        else:
+            U = self._density_directions(directions)
+            if bool((torch.linalg.norm(U, dim=1) == 0).any()):
+                raise ValueError("directions: zero vector")
+        Md = U.shape[0]
+        zv, zm = torch.zeros((Md, d), dtype=F64), torch.zeros((Md, d, d), dtype=F64)
+        uu = 2.0 * U.unsqueeze(2) * U.unsqueeze(1)          # 1/2 x^T (2 u u^T) x = (u.x)^2
+        vals, norm2 = self.expectation(x=torch.cat((U, zv, zv, zv)), xx=torch.cat((zm, uu, zm, zm)),
+                                       p=torch.cat((zv, zv, U, zv)), pp=torch.cat((zm, zm, zm, uu)))
+        ex, exx, ep, epp = (vals[k * Md:(k + 1) * Md].real for k in range(4))
+        return {"x": ex, "p": ep, "var_x": exx - ex ** 2, "var_p": epp - ep ** 2, "norm2": norm2}
+
+    def energy_expectation(self, potential):
+        """<psi| p^T m^-1 p / 2 + V(x) |psi> / norm()**2 for a potential whose Hessian is constant: ``MolecularHarmonicPotential``
+        and ``MorsePotential`` with all chi = 0 (``NotImplementedError`` for every other: V is not a quadratic operator).  A float:
+        the real part of one ``expectation`` value.  A singular Gamma_t is refused with ``ValueError``: the kinetic energy along
+        its null directions does not exist, and projecting it is the caller's decision (``expectation`` with a projected pp)."""
+        from . import potentials as P
+        self._refuse_thermal("energy_expectation()", "it describes one pure state, the trajectories belong to a mixture")
+        d = self.dim
+        if isinstance(potential, P.MolecularHarmonicPotential):
+            H, x0, g = (hostmath.as_f64(t) for t in (potential.hess0, potential.pos0, potential.grad0))
+            H = 0.5 * (H + H.T)
+            const = float(potential.energy0) - potential._origin - float(g @ x0) + 0.5 * float(x0 @ H @ x0)
+            lin = g - H @ x0
+        elif isinstance(potential, P.MorsePotential) and potential._is_harmonic():
+            H = torch.diag(hostmath.as_f64(potential.omega) ** 2)
+            const, lin = 0.0, torch.zeros(d, dtype=F64)
+        else:
+            raise NotImplementedError(f"energy_expectation: {type(potential).__name__} is not a potential with a constant Hessian "
+                                      "(MolecularHarmonicPotential, MorsePotential with chi = 0): <V> is not a quadratic operator's")
+        if potential.dimensions() != d:
+            raise ValueError(f"energy_expectation: the potential has {potential.dimensions()} dimensions, the propagator {d}")
+        if not self._width_has_full_rank():
+            raise ValueError("energy_expectation: Gamma_t is singular, the kinetic energy along its null directions does not exist; "
+                             "projecting it is the caller's decision (expectation() with a projected pp)")
+        W = torch.diag(1.0 / hostmath.as_f64(potential.masses()))
+        vals, _ = self.expectation(c=torch.tensor([const], dtype=F64), x=lin.unsqueeze(0), xx=H.unsqueeze(0), pp=W.unsqueeze(0))
+        return float(vals[0].real)
+
     def wavefunction(self, x):
         """frozen-Gaussian wavefunction psi(x,t) on a spatial grid x (dim,nx) -> complex ndarray (nx,)
         (reference propagators.py:688-732 with CoherentStatesWavefunction :243-292).  The discard mask (discard_nonsymplectic) is
@@ -2437,6 +2558,10 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
 
     def reduced_density(self, directions, s):
         raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
+                                  "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
+
+    def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True):
+        raise NotImplementedError("expectation is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
     def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=()):
