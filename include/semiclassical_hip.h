@@ -888,6 +888,28 @@ int sc_hk_opcorr_thermal(const sc_state *st, double time, const sc_thermal_const
                          const double *bra_w, const double *bra_ut, const double *bra_wt, const double *bra_k, const double *g,
                          int32_t M, const uint8_t *kept, double *partials, double *out, const int64_t *cursor, void *stream);
 
+/* The same with QUADRATIC operators A_a = c_a + m_a.x + 1/2 x^T K_a x on both sides, behind
+ * HermanKlukPropagator.thermal_quadratic_correlation() and run(thermal_quadratic=...) (not in the reference; DESIGN.md section
+ * 4.22): the columns of sc_hk_opquad with the trajectory's own centre of sc_hk_opcorr_thermal.  One side of an operator is 1 + R
+ * columns,
+ *   z_col = k[col] + u[col].Q_i + i w[col].P_i + ut[col].Qc_i(t) + i wt[col].Pc_i(t),   f_ia = sum_col l[col] z_col^p
+ *   (p = 1 for column 0 of an operator, else 2), the ket from the initial points and the centres of t = 0 into g [n][M]
+ *   (sc_hk_opquad_thermal_initial, RB), the bra from `st` and the centres rotated to `time` (RA);  x_ia = f_ia g_ia cq_i and the
+ *   row of five sums as above.
+ *   *_u, *_w [M (1 + R)][D], *_k [M (1 + R)] complex, *_l [M (1 + R)]: those of sc_hk_opquad with p0 = 0; *_ut, *_wt
+ *   [M (1 + R)][d'']: those of sc_hk_opcorr_thermal of every column's vector (zeros in padding columns).
+ *   th, cq, kept, partials (sc_hk_opquad_thermal_rows(n, M) * M * 5 doubles), out, cursor, `st`: as for sc_hk_opcorr_thermal.
+ * sc_hk_opquad_thermal: two launches; no atomics, the order of every sum is a function of (n, M, R, D, d'') alone: the same bits in
+ * every call.  The limits and codes of sc_hk_opquad (R <= 512, M (1 + R) < 2^24) and of sc_hk_opcorr_thermal (1 <= d'' <= D <= 512). */
+int64_t sc_hk_opquad_thermal_rows(int64_t n, int64_t M);
+int sc_hk_opquad_thermal_initial(const double *zi, const double *centres, int64_t n, int32_t D, int32_t dmodes,
+                                 const double *ket_u, const double *ket_w, const double *ket_ut, const double *ket_wt,
+                                 const double *ket_k, const double *ket_l, int32_t M, int32_t RB, double *g, void *stream);
+int sc_hk_opquad_thermal(const sc_state *st, double time, const sc_thermal_consts *th, const double *cq, const double *bra_u,
+                         const double *bra_w, const double *bra_ut, const double *bra_wt, const double *bra_k, const double *bra_l,
+                         const double *g, int32_t M, int32_t RA, const uint8_t *kept, double *partials, double *out,
+                         const int64_t *cursor, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,13 @@ SIGNATURES = {
     "sc_hk_opcorr_thermal": (C.c_int, [P(sc_state), C.c_double, P(sc_thermal_consts), c_double_p, c_double_p, c_double_p,
                                        c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_void_p, c_double_p,
                                        c_double_p, C.c_void_p, C.c_void_p]),
+    "sc_hk_opquad_thermal_rows": (C.c_int64, [C.c_int64, C.c_int64]),
+    "sc_hk_opquad_thermal_initial": (C.c_int, [c_double_p, c_double_p, C.c_int64, C.c_int32, C.c_int32, c_double_p, c_double_p,
+                                               c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32, c_double_p,
+                                               C.c_void_p]),
+    "sc_hk_opquad_thermal": (C.c_int, [P(sc_state), C.c_double, P(sc_thermal_consts), c_double_p, c_double_p, c_double_p,
+                                       c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32, C.c_void_p,
+                                       c_double_p, c_double_p, C.c_void_p, C.c_void_p]),
     "sc_comm_available": (C.c_int, []),
     "sc_comm_unique_id": (C.c_int, [C.c_void_p]),
     "sc_comm_init": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(C.c_void_p)]),

@@ -169,8 +169,10 @@ __global__ __launch_bounds__(256) void opquad_initial_kernel(const double *z, in
     }
 }
 
+}  // namespace
+
 // 0 <= R <= 512 and M (1 + R) < 2^24, after the limits the linear kernels share
-int opquad_limits(const char *who, int64_t n, int D, int M, int R) {
+int sc_opquad_limits(const char *who, int64_t n, int D, int M, int R) {
     if (R < 0) return sc_fail(SC_ERR_BAD_ARGUMENT, "%s: R=%d", who, R);
     const int rc = sc_rows5_limits(who, "M", "operators", n, D, M, nullptr);
     if (rc != SC_OK) return rc;
@@ -181,14 +183,12 @@ int opquad_limits(const char *who, int64_t n, int D, int M, int R) {
     return SC_OK;
 }
 
-}  // namespace
-
 extern "C" int64_t sc_hk_opquad_rows(int64_t n, int64_t M) { return sc_rows5_bands(n, M); }
 
 extern "C" int sc_hk_opquad_initial(const double *zi, int64_t n, int32_t D, const double *ket_u, const double *ket_w,
                                     const double *ket_k, const double *ket_l, int32_t M, int32_t RB, double *g, void *stream) {
     if (!zi || !ket_u || !ket_w || !ket_k || !ket_l || !g) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad_initial: null argument");
-    const int rc = opquad_limits("sc_hk_opquad_initial", n, D, M, RB);
+    const int rc = sc_opquad_limits("sc_hk_opquad_initial", n, D, M, RB);
     if (rc != SC_OK) return rc;
     if (n == 0) return SC_OK;
     hipLaunchKernelGGL(opquad_initial_kernel, sc_optile_prepass_grid(n, M), dim3(256), 0, (hipStream_t)stream, zi, n, D, ket_u, ket_w,
@@ -201,7 +201,7 @@ extern "C" int sc_hk_opquad(const sc_state *st, const double *cq, const double *
                             double *out, const int64_t *cursor, void *stream) {
     if (!st || !cq || !bra_u || !bra_w || !bra_k || !bra_l || !g || !partials || !out)
         return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad: null argument");
-    const int rc = opquad_limits("sc_hk_opquad", st->n, st->dim, M, RA);
+    const int rc = sc_opquad_limits("sc_hk_opquad", st->n, st->dim, M, RA);
     if (rc != SC_OK) return rc;
     if (!st->qp) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_hk_opquad: the state has no qp");
     const int C1 = 1 + RA, per = C1 > R5_TILE ? 1 : R5_TILE / C1;

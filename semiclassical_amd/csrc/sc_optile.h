@@ -1,5 +1,5 @@
-// Operator tiles: what the tile and pre-pass kernels of sc_opcorr.hip, sc_opquad.hip and
-// sc_thermal_opcorr.hip share.  Every operator, or column of an operator, is an affine form of a phase-space point,
+// Operator tiles: what the tile and pre-pass kernels of sc_opcorr.hip, sc_opquad.hip,
+// sc_thermal_opcorr.hip and sc_thermal_opquad.hip share.  Every operator, or column of an operator, is an affine form of a phase-space point,
 //   z = kappa + u.Q + i w.P,
 // and a workgroup forms it for a 64 x 64 tile of (trajectory, column) pairs.  The tile mapping is that of sc_rows5.h: thread
 // (ti, tj) owns the trajectories 4 ti + a and the columns 4 tj + b.
@@ -77,6 +77,56 @@ __device__ __forceinline__ void optile_staged_loop(OpStage &S, const int *live, 
     }
 }
 
+// The same over the d'' thermal modes of an ensemble with per-trajectory centres: fr[a][b] += ut_col.Qc_i(t),
+// fi[a][b] += wt_col.Pc_i(t) with the centres rotated WHILE STAGING,
+//   Qc(t) = Qc cos wt + Pc / w sin wt,   Pc(t) = Pc cos wt - w Qc sin wt.
+// A staging thread keeps one mode index k through a chunk (256 is a multiple of R5_CHUNK): cos, sin and 1 / w of the chunk's 16 modes
+// are formed once per chunk and workgroup into the 48-double table `rot`.  centres [n][2 dm] at t = 0: the rows i0 + r with
+// live[r] != 0 are read; ut, wt [.][dm]: the columns k0 ... k0 + kv - 1.  The table of chunk c + 1 is written after the second barrier
+// of chunk c, behind which no staging thread of chunk c reads it any more, and before the first barrier of chunk c + 1; that first
+// barrier also ends the reads of the buffers by whoever ran before the loop.
+typedef double OpRotTable[3][R5_CHUNK];                    // cos w t, sin w t, 1 / w of the chunk's modes
+template <typename Column>
+__device__ __forceinline__ void optile_rotated_loop(OpStage &S, OpRotTable &rot, const int *live, const double *omega, double time,
+                                                    const double *centres, int dm, const double *ut, const double *wt, int64_t i0,
+                                                    Column k0, int kv, int tid, int ti, int tj, double (&fr)[4][4],
+                                                    double (&fi)[4][4]) {
+    for (int m0 = 0; m0 < dm; m0 += R5_CHUNK) {
+        if (tid < R5_CHUNK) {
+            double c = 1.0, s = 0.0, iw = 0.0;
+            if (m0 + tid < dm) {
+                const double om = omega[m0 + tid];
+                sincos(om * time, &s, &c);
+                iw = 1.0 / om;
+            }
+            rot[0][tid] = c; rot[1][tid] = s; rot[2][tid] = iw;
+        }
+        __syncthreads();
+        const int k = tid & (R5_CHUNK - 1), mode = m0 + k; // the thread's mode through the chunk
+        const double c = rot[0][k], s = rot[1][k], iw = rot[2][k];
+        const double om = mode < dm ? omega[mode] : 0.0;
+        for (int e = tid; e < R5_CHUNK * R5_TILE; e += 256) {
+            const int r = e / R5_CHUNK;
+            double qt = 0.0, pt = 0.0;
+            if (mode < dm && live[r]) {
+                const double *row = centres + (i0 + r) * 2 * dm;
+                const double qc = row[mode], pc = row[dm + mode];
+                qt = fma(pc * iw, s, qc * c);
+                pt = fma(-om * qc, s, pc * c);
+            }
+            S.tq[k][r] = qt; S.tp[k][r] = pt;
+            double u = 0.0, w = 0.0;
+            if (mode < dm && r < kv) {
+                const size_t at = (size_t)(k0 + r) * dm + mode;
+                u = ut[at]; w = wt[at];
+            }
+            S.ku[k][r] = u; S.kw[k][r] = w;
+        }
+        __syncthreads();
+        optile_chunk_fma(S, ti, tj, fr, fi);
+    }
+}
+
 // The finish of a linear tile kernel: x_ia = (kappa_a + f_ia) g_ia cq_i, x = 0 by selection for a column beyond kv or a row that is
 // not live (its g is not read); the thread's four trajectories are added per operator in registers, then the tail of sc_rows5.h.
 // kap [M] complex, g [n][M] complex, lds: the staging buffers.
@@ -127,3 +177,7 @@ dim3 sc_optile_prepass_grid(int64_t n, int M);
 // in an error, "`who` (reduction)" the reduction.
 int sc_optile_rows(const char *who, const void *tile, void *args, unsigned columns, int64_t n, int M, const double *partials,
                    double *out, const int64_t *cursor, hipStream_t stream);
+// the limits of the quadratic tile kernels (sc_opquad.hip): 0 <= R <= 512 and M (1 + R) < 2^24, after those of sc_rows5_limits
+int sc_opquad_limits(const char *who, int64_t n, int D, int M, int R);
+// 1 <= d'' <= D of the thermal tile kernels (sc_thermal_opcorr.hip)
+int sc_thermal_modes_limit(const char *who, int D, int dm);

@@ -12,9 +12,8 @@
 //   Qc(t) = Qc cos wt + Pc / w sin wt,   Pc(t) = Pc cos wt - w Qc sin wt
 //
 // thermal_opcorr_tile_kernel: opcorr_tile_kernel (the pieces of sc_optile.h) with a second staged loop between the loop over D and
-//   the finish, over the d'' modes, whose trajectory planes are the centres rotated WHILE STAGING.  A staging thread keeps one mode
-//   index k through a chunk (256 is a multiple of R5_CHUNK): cos, sin and 1 / w of the chunk's 16 modes are formed once per chunk
-//   and workgroup into a 48-double table.  th->map_q, map_p, q0, n1 are not read.  The centres of discarded trajectories and of the
+//   the finish, over the d'' modes, whose trajectory planes are the centres rotated WHILE STAGING (optile_rotated_loop of
+//   sc_optile.h, which sc_thermal_opquad.hip shares).  th->map_q, map_p, q0, n1 are not read.  The centres of discarded trajectories and of the
 //   rows beyond n are never loaded either.
 #include "sc_optile.h"
 
@@ -40,7 +39,7 @@ __global__ __launch_bounds__(256) void thermal_opcorr_tile_kernel(ThermalOpcorrA
     __shared__ OpTileLds lds;
     __shared__ double2 cqs[R5_TILE];// cq_i of the band's trajectories (0: beyond n, or discarded)
     __shared__ int live[R5_TILE];
-    __shared__ double rot[3][R5_CHUNK];                    // cos w t, sin w t, 1 / w of the chunk's modes
+    __shared__ OpRotTable rot;
     OpStage &S = lds.S;
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
     const int dm = A.dm;
@@ -49,42 +48,8 @@ __global__ __launch_bounds__(256) void thermal_opcorr_tile_kernel(ThermalOpcorrA
     optile_band_header(live, cqs, A.n, i0, A.kept, A.cq, tid);
     double fr[4][4] = {}, fi[4][4] = {};
     optile_staged_loop(S, live, A.qp, A.D, A.u, A.w, i0, k0, kv, tid, ti, tj, fr, fi);       // the current points against u, w
-    // the rotated centres against ut, wt.  The table of chunk c + 1 is written after the second barrier of chunk c, behind which no
-    // staging thread of chunk c reads it any more, and before the first barrier of chunk c + 1.
-    for (int m0 = 0; m0 < dm; m0 += R5_CHUNK) {
-        if (tid < R5_CHUNK) {
-            double c = 1.0, s = 0.0, iw = 0.0;
-            if (m0 + tid < dm) {
-                const double om = A.omega[m0 + tid];
-                sincos(om * A.time, &s, &c);
-                iw = 1.0 / om;
-            }
-            rot[0][tid] = c; rot[1][tid] = s; rot[2][tid] = iw;
-        }
-        __syncthreads();
-        const int k = tid & (R5_CHUNK - 1), mode = m0 + k; // the thread's mode through the chunk
-        const double c = rot[0][k], s = rot[1][k], iw = rot[2][k];
-        const double om = mode < dm ? A.omega[mode] : 0.0;
-        for (int e = tid; e < R5_CHUNK * R5_TILE; e += 256) {
-            const int r = e / R5_CHUNK;
-            double qt = 0.0, pt = 0.0;
-            if (mode < dm && live[r]) {
-                const double *row = A.centres + (i0 + r) * 2 * dm;
-                const double qc = row[mode], pc = row[dm + mode];
-                qt = fma(pc * iw, s, qc * c);
-                pt = fma(-om * qc, s, pc * c);
-            }
-            S.tq[k][r] = qt; S.tp[k][r] = pt;
-            double u = 0.0, w = 0.0;
-            if (mode < dm && r < kv) {
-                const size_t at = (size_t)(k0 + r) * dm + mode;
-                u = A.ut[at]; w = A.wt[at];
-            }
-            S.ku[k][r] = u; S.kw[k][r] = w;
-        }
-        __syncthreads();
-        optile_chunk_fma(S, ti, tj, fr, fi);
-    }
+    // the rotated centres against ut, wt
+    optile_rotated_loop(S, rot, live, A.omega, A.time, A.centres, dm, A.ut, A.wt, i0, k0, kv, tid, ti, tj, fr, fi);
     optile_finish_linear(fr, fi, live, cqs, A.kap, A.g, i0, k0, kv, A.M, &lds, tid, ti, tj, A.partials);
 }
 
@@ -108,11 +73,15 @@ __global__ __launch_bounds__(256) void thermal_opcorr_affine_kernel(const double
 int thermal_opcorr_limits(const char *who, int64_t n, int D, int dm, int M) {
     const int rc = sc_rows5_limits(who, "M", "operators", n, D, M, nullptr);
     if (rc != SC_OK) return rc;
-    if (dm < 1 || dm > D) return sc_fail(SC_ERR_UNSUPPORTED, "%s: d''=%d outside 1 <= d'' <= D=%d", who, dm, D);
-    return SC_OK;
+    return sc_thermal_modes_limit(who, D, dm);
 }
 
 }  // namespace
+
+int sc_thermal_modes_limit(const char *who, int D, int dm) {
+    if (dm < 1 || dm > D) return sc_fail(SC_ERR_UNSUPPORTED, "%s: d''=%d outside 1 <= d'' <= D=%d", who, dm, D);
+    return SC_OK;
+}
 
 extern "C" int64_t sc_hk_opcorr_thermal_rows(int64_t n, int64_t M) { return sc_rows5_bands(n, M); }
 

@@ -755,8 +755,9 @@ def run_semiclassical_dynamics(task, device='cuda', comm=None):
     targets = None if targets_file is None else _load_targets(targets_file, int(setup.q0.shape[0]))
     operators = None if operators_file is None else _load_operators(operators_file, int(setup.q0.shape[0]))
     if kelvin is not None and operators is not None and len(operators) > 4:
-        raise ConfigurationError("'operator_correlation' with bra_k or ket_k is not available with 'temperature': the thermal "
-                                 "operator correlation functions take linear operators")
+        raise ConfigurationError("'operator_correlation' with bra_k or ket_k is not available with 'temperature': the task's thermal "
+                                 "operator correlation functions take linear operators (from Python: "
+                                 "HermanKlukPropagator.thermal_quadratic_correlation / run(thermal_quadratic=...))")
 
     dt = task['time_step_fs'] / units.autime_to_fs
     nt = task['num_steps']

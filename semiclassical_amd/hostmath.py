@@ -229,13 +229,20 @@ def fold_thermal_linear_operators(c, m, G_traj, G_0, q0, tc, ket):
     elementwise products.  Returns real (M, D) twice, complex (M,), real (M, d'') twice; the refusals of
     ``fold_linear_operators``."""
     u, w, kappa = fold_linear_operators(c, m, G_traj, G_0, q0, torch.zeros_like(q0), ket)
+    ut, wt = _centre_vectors(w, G_0, tc, ket)
+    return u, w, kappa, ut, wt
+
+
+def _centre_vectors(w, G_0, tc, ket):
+    """(ut, wt), rows (., d''), of the rows w = -+ S m / hbar (., D) of ``fold_linear_operators``:  ut = map_q^T G_0 S m,
+    wt = -+ map_p^T S m / hbar"""
     sign = 1.0 if ket else -1.0
     SmG0 = (-sign * hbar * w) @ G_0                         # rows (G_0 S m_a)^T: w = -+ S m / hbar
     if tc.diag:
         ut, wt = SmG0 * tc.scale_q.unsqueeze(0), -w * tc.scale_p.unsqueeze(0)
     else:
         ut, wt = SmG0 @ tc.map_q, -w @ tc.map_p
-    return u, w, kappa, ut.contiguous(), wt.contiguous()
+    return ut.contiguous(), wt.contiguous()
 
 
 def _kept_eigenpairs(Ka, a, name):
@@ -298,6 +305,20 @@ def fold_quadratic_operators(c, m, K, G_traj, G_0, q0, p0, ket):
         u[a, 1:1 + r], w[a, 1:1 + r], kappa[a, 1:1 + r], lam_out[a, 1:1 + r] = ur[at:at + r], wr[at:at + r], kr[at:at + r], 0.5 * lam
         at += r
     return u, w, kappa, lam_out, R
+
+
+def fold_thermal_quadratic_operators(c, m, K, G_traj, G_0, q0, tc, ket):
+    """(u, w, kappa, lam, ut, wt, R): ``fold_quadratic_operators`` for a thermal ensemble, where the fixed
+    Gaussian is |a_i, b_i, G_0> with the trajectory's own centre (``tc``: the ThermalConstants) in the place of (q0, p0 = 0).  A
+    column is  z_col = kappa_col + u_col.q + i w_col.p + ut_col.Qc + i wt_col.Pc  and the element  sum_col lam_col z_col^(p_col):
+    (u, w, kappa, lam, R) are those of ``fold_quadratic_operators`` at p0 = 0 (1/2 tr(K S) inside kappa of column 0), (ut, wt)
+    those of ``fold_thermal_linear_operators`` for (c, m) in column 0 and for the linear operator (0, v_r) of every kept
+    eigenvector in the columns 1 ... R, zeros in the padding.  Returns real (M, 1 + R, D) twice, complex (M, 1 + R), real
+    (M, 1 + R), real (M, 1 + R, d'') twice and R; the refusals of ``fold_quadratic_operators``."""
+    u, w, kappa, lam, R = fold_quadratic_operators(c, m, K, G_traj, G_0, q0, torch.zeros_like(q0), ket)
+    M, C1, D = u.shape
+    ut, wt = _centre_vectors(w.reshape(M * C1, D), G_0, tc, ket)       # column by column: the padding stays zero
+    return u, w, kappa, lam, ut.reshape(M, C1, -1), wt.reshape(M, C1, -1), R
 
 
 def fold_expectation_operators(c, m, K, n, W, Gamma_t):

@@ -97,6 +97,12 @@ _OPERATOR_ROWS, _THERMAL_OPERATOR_ROWS = _ROW_FAMILIES[1], _ROW_FAMILIES[2]
 # The hook of a time-average accumulator in the same place: a terms launch after every correlate launch.
 # It fills no row (field None) and is not an argument family of run(): its "prepared dict" is the accumulator itself.
 _TIME_AVERAGE = _RowFamily("time_average", None, None, "time-average terms", None, "_launch_ta_terms", False)
+# The thermal correlation functions with quadratic operators: a row family of run() like those above, kept
+# outside _ROW_FAMILIES, whose names are pinned.  Its rows travel in the opcorr field as the thermal operators' do: one call takes
+# one of the two.
+_THERMAL_QUADRATIC_ROWS = _RowFamily("thermal_quadratic", "thermal_opquad", "M", "thermal quadratic-correlation",
+                                     "_prepare_thermal_quadratic", "_launch_thermal_opquad", True, "opcorr")
+_RUN_ROW_FAMILIES = _ROW_FAMILIES + (_THERMAL_QUADRATIC_ROWS,)
 
 
 class _StepRows(object):
@@ -257,6 +263,7 @@ class HermanKlukPropagator(object):
     _thermal_ok = True              # WM has another prefactor and per-trajectory widths: no thermal ensemble
     _thermal = None                 # the active thermal ensemble (constants, centres, sc_thermal_consts), None = one pure state
     _thermal_opcorr = None
+    _thermal_opquad = None
 
     def _thermal_constants(self, q0, p0, Gamma_0, masses, temperature):
         if not self._thermal_ok:
@@ -279,8 +286,8 @@ class HermanKlukPropagator(object):
         temperature 0 every centre is (q0, 0) and the estimator is that of ``initial_conditions``.
 
         While the ensemble is active ``autocorrelation``, ``ic_correlation``, ``autocorrelation_qp``, ``run`` (with standard
-        errors and blocks), ``standard_errors``, ``discard_nonsymplectic`` and ``thermal_operator_correlation`` /
-        ``run(thermal_operators=...)`` work; everything that describes ONE pure state or
+        errors and blocks), ``standard_errors``, ``discard_nonsymplectic``, ``thermal_operator_correlation`` /
+        ``run(thermal_operators=...)`` and ``thermal_quadratic_correlation`` / ``run(thermal_quadratic=...)`` work; everything that describes ONE pure state or
         has no thermal kernel is refused (see ``_refuse_thermal``).  ``initial_conditions`` / ``set_initial_conditions`` return
         to the zero-temperature path.  ``ValueError`` for p0 != 0, a negative temperature or masses of the wrong shape."""
         tc = self._thermal_constants(q0, p0, Gamma_0, masses, temperature)
@@ -412,6 +419,7 @@ class HermanKlukPropagator(object):
         self._cross = None            # constants and scratch of cross_correlation(): depend on Gamma_0 and n
         self._opcorr = None           # folded operators, g and scratch of operator_correlation(): depend on (zi, Gamma_0, q0, p0) and n
         self._thermal = None          # thermal ensemble (thermal_initial_conditions installs it after this): None = one pure state
+        self._thermal_opquad = None   # the same of thermal_quadratic_correlation()
         self._thermal_opcorr = None   # folded operators, g and scratch of thermal_operator_correlation(): as _opcorr, and the centres
 
         self._prepare()
@@ -827,7 +835,7 @@ class HermanKlukPropagator(object):
             raise ValueError("use_graph=True is not available with a thermal ensemble: the time of the state is an argument of the "
                              "correlate kernel, which a graph replay cannot change")
         for fam, _ in families:
-            if fam is not _THERMAL_OPERATOR_ROWS:
+            if fam is not _THERMAL_OPERATOR_ROWS and fam is not _THERMAL_QUADRATIC_ROWS:
                 raise NotImplementedError(f"{fam.arg} are not available with a thermal ensemble: their kernels take the one "
                                           "centre (q0, p0)")
         s, nac, th = self._stream(), self._nac, self._thermal
@@ -1145,7 +1153,8 @@ class HermanKlukPropagator(object):
         ket-side factors g [n][M] of the initial points on the device (_operator_pair, _fold_operators)"""
         refused = None if getattr(self, "_thermal", None) is None else NotImplementedError(
             "an operator correlation function is not available with a thermal ensemble: the folded operators take the one centre "
-            "(q0, p0); the trace over the ensemble is thermal_operator_correlation() / run(thermal_operators=...)")
+            "(q0, p0); the trace over the ensemble is thermal_operator_correlation() / run(thermal_operators=...), with a K "
+            "thermal_quadratic_correlation() / run(thermal_quadratic=...)")
         return self._operator_pair("_opcorr", bra, ket, refused, None, self._fold_operators, lib.sc_hk_opcorr_rows)
 
     def _fold_operators(self, A, B, M, g):
@@ -1226,8 +1235,9 @@ class HermanKlukPropagator(object):
         refused = None if self._thermal is not None else ValueError(
             "thermal operators need a thermal ensemble (thermal_initial_conditions): the expectation value in the one state phi_0 "
             "is operator_correlation() / run(operators=...)")
-        refused_k = NotImplementedError("quadratic operators (a K) are not available with a thermal ensemble: "
-                                        "thermal_operator_correlation() takes linear operators (c, m)")
+        refused_k = NotImplementedError("quadratic operators (a K) are not taken by thermal_operator_correlation() / "
+                                        "run(thermal_operators=...), whose operators are linear (c, m): "
+                                        "thermal_quadratic_correlation() / run(thermal_quadratic=...) takes them")
         return self._operator_pair("_thermal_opcorr", bra, ket, refused, refused_k, self._fold_thermal_operators,
                                    lib.sc_hk_opcorr_thermal_rows)
 
@@ -1274,8 +1284,68 @@ class HermanKlukPropagator(object):
         Gamma_i + Gamma_0 (ket); ``NotImplementedError`` for operators with a K."""
         return self._current_operator_rows(_THERMAL_OPERATOR_ROWS, self._thermal_operators(bra, ket), energy0_es, standard_errors)
 
+    # ---- ... and quadratic operators (not in the reference; DESIGN.md section 4.22) ----
+    def _thermal_quadratic(self, bra, ket=None):
+        """``_thermal_operators`` for operators that may carry a K: validated, folded into columns, and the ket-side factors g [n][M]
+        on the device (_operator_pair, _fold_thermal_quadratic)"""
+        refused = None if self._thermal is not None else ValueError(
+            "thermal quadratic operators need a thermal ensemble (thermal_initial_conditions): the expectation value in the one "
+            "state phi_0 is operator_correlation() / run(operators=...)")
+        return self._operator_pair("_thermal_opquad", bra, ket, refused, None, self._fold_thermal_quadratic,
+                                   lib.sc_hk_opquad_thermal_rows)
+
+    def _fold_thermal_quadratic(self, A, B, M, g):
+        """Without a K on either side: exactly _fold_thermal_operators (section 4.20); with one: the columns of hostmath.
+        fold_thermal_quadratic_operators -- (u, w, ut, wt, kappa, lambda) of the bra, then of the ket --, sc_hk_opquad_thermal_initial
+        and the ranks"""
+        if A[2] is None and B[2] is None:
+            return self._fold_thermal_operators(A, B, M, g)
+        th = self._thermal
+        tc = th["consts"]
+        *colsA, RA = hostmath.fold_thermal_quadratic_operators(*A, self._Gt, self._G0h, self._q0h, tc, ket=False)
+        *colsB, RB = hostmath.fold_thermal_quadratic_operators(*B, self._Gi, self._G0h, self._q0h, tc, ket=True)
+        order = (0, 1, 4, 5, 2, 3)                         # (u, w, kappa, lambda, ut, wt) -> (u, w, ut, wt, kappa, lambda)
+        bufs = [cols[i].to(self.device) for cols in (colsA, colsB) for i in order]
+        check(lib.sc_hk_opquad_thermal_initial(ptr(self._zi_t), ptr(th["centres"]), self.ntraj, self.dim, tc.dmodes, *map(ptr, bufs[6:]),
+                                               M, RB, ptr(g), self._stream()))
+        return bufs, {"RA": RA, "RB": RB}
+
+    def _prepare_thermal_quadratic(self, operators):
+        """run(thermal_quadratic=...): the prepared dict of _thermal_quadratic"""
+        return self._thermal_quadratic(*self._parse_operator_pair(operators, "(c, m) or (c, m, K) of arrays (M,), (M, D) and (M, D, D)"))
+
+    def _launch_thermal_opquad(self, operators, out_ptr, state=None, time=None, cursor=None):
+        """_launch_thermal_opcorr for the prepared dict of _thermal_quadratic: sc_hk_opquad_thermal when it carries columns ("RA"),
+        else that very launch, sc_hk_opcorr_thermal"""
+        if "RA" not in operators:
+            return self._launch_thermal_opcorr(operators, out_ptr, state=state, time=time, cursor=cursor)
+        assert cursor is None
+        b, th = operators["bufs"], self._thermal
+        with self._timed("hk_opquad_thermal"):
+            check(lib.sc_hk_opquad_thermal(self._state if state is None else state, float(self.t if time is None else time),
+                                           th["struct"], ptr(self._cq), *map(ptr, b[:6]), ptr(operators["g"]), operators["M"],
+                                           operators["RA"], ptr(self._kept), ptr(operators["partials"]), C_void(out_ptr), None,
+                                           self._stream()))
+
+    def thermal_quadratic_correlation(self, bra, ket=None, energy0_es=0.0, standard_errors=False):
+        """X_a(t) = e^{i t E0/hbar} Tr[rho e^{i H_es t/hbar} A_a e^{-i H_gs t/hbar} B_a] for the current step of a thermal ensemble
+        with M pairs of linear or QUADRATIC operators A_a = cA_a + mA_a.x + 1/2 x^T KA_a x, B_a likewise (not in the reference;
+        DESIGN.md section 4.22): a complex ndarray (M,) -- the energy-gap correlation function between two harmonic surfaces,
+        second-order Herzberg-Teller terms and thermal second moments <x_j x_k>, each with an error bar.  ``bra`` = (c, m) or
+        (c, m, K) as for ``operator_correlation`` (K_a the symmetric Hessian), ``ket`` likewise, None = the operators of the bra, K
+        included.  ``thermal_operator_correlation`` with the matrix elements of ``operator_correlation``: every trajectory's thermal
+        C_auto term times the Gaussian matrix element of A between its own centre, rotated to the current time, and its current
+        point, and of B between its initial point and its centre.  A K that is None or all zeros on both sides takes the path of
+        ``thermal_operator_correlation`` and gives its bits.  With ``standard_errors`` the result is ``(X, sigma)``.  Discarded
+        trajectories count as samples of value zero, N unchanged.  Synchronises; the state is not touched.
+        ``ValueError`` without a thermal ensemble, for operators of the wrong shape, with non-finite entries, M = 0, another M on
+        the ket, a K that is not symmetric, or a vector m or an eigenvector of K (eigenvalue above 1e-12 of the largest) outside the
+        range of Gamma_0 + Gamma_t (bra) or Gamma_i + Gamma_0 (ket)."""
+        return self._current_operator_rows(_THERMAL_QUADRATIC_ROWS, self._thermal_quadratic(bra, ket), energy0_es, standard_errors)
+
     def run(self, potential, dt, nt, energy0_es=0.0, slots=None, use_graph=False, moments=None, standard_errors=False, blocks=None,
-            targets=None, cross=None, operators=None, opcorr=None, time_average=None, thermal_operators=None, thermal_opcorr=None):
+            targets=None, cross=None, operators=None, opcorr=None, time_average=None, thermal_quadratic=None, thermal_opquad=None,
+            thermal_operators=None, thermal_opcorr=None):
         """The caller loop of cli.py:401-436 on the device: ``nt`` times (C_auto, k_ic, step), no host sync.
 
         Returns ``(autocorrelation[nt], ic_correlation[nt])`` as complex NumPy arrays.  With ``slots`` (a
@@ -1333,6 +1403,12 @@ class HermanKlukPropagator(object):
         every ``sc_hk_correlate_thermal`` launch, the intermediate states of pairs and visits included.  Everything said of
         operators holds with ``thermal_opcorr`` (>= nt, M, 5) in the place of ``opcorr``; ``ValueError`` without a thermal ensemble.
 
+        Thermal correlation functions with quadratic operators: ``thermal_quadratic`` = (bra, ket) or bra alone, each (c, m) or
+        (c, m, K) (``thermal_quadratic_correlation``): a ``sc_hk_opquad_thermal`` launch (``sc_hk_opcorr_thermal`` without a K) with
+        the state's own time follows every ``sc_hk_correlate_thermal`` launch.  Everything said of the thermal operators holds with
+        ``thermal_opquad`` (>= nt, M, 5) in the place of ``thermal_opcorr``.  Together with ``thermal_operators`` in one call:
+        ``ValueError`` -- linear operators go into the same set with K None.
+
         Time-averaged spectra: ``time_average`` = an accumulator of ``time_average()``: a ``sc_hk_ta_terms`` launch follows every
         correlate launch, the intermediate states of pairs and visits included, and every TB-th column one ``sc_hk_ta_accumulate``
         launch.  Columns that do not fill a block stay pending in the accumulator across calls (``spectrum()`` / ``raw_sums()``
@@ -1354,9 +1430,13 @@ class HermanKlukPropagator(object):
                 if arg is not None:
                     self._refuse_thermal(f"run({name}=...)", "its kernel takes the one centre (q0, p0)")
         given = {"targets": targets, "cross": cross, "operators": operators, "opcorr": opcorr,
-                 "thermal_operators": thermal_operators, "thermal_opcorr": thermal_opcorr}
+                 "thermal_operators": thermal_operators, "thermal_opcorr": thermal_opcorr,
+                 "thermal_quadratic": thermal_quadratic, "thermal_opquad": thermal_opquad}
+        if thermal_operators is not None and thermal_quadratic is not None:
+            raise ValueError("run(thermal_operators=..., thermal_quadratic=...): one set of thermal operators per call -- linear "
+                             "operators go into thermal_quadratic with K None")
         families, bufs, counts = [], {}, {}
-        for fam in _ROW_FAMILIES:
+        for fam in _RUN_ROW_FAMILIES:
             arg, buf = given[fam.arg], given[fam.field]
             if arg is None:
                 if buf is not None:
