@@ -546,6 +546,22 @@ int sc_pair_expect(const double *X1, const double *Y1, int32_t K1, const double 
                    const double *wk, int64_t ni, int64_t nj, const double *za, const double *zb, const double *lam,
                    const double *kap, int32_t M, int32_t R, double *partials, double *out, void *stream);
 
+/* sc_pair_expect with P product columns per operator next to the 1 + R sum columns, behind
+ * HermanKlukPropagator.expectation(ex=...) and anharmonic_energy_expectation() (not in the reference):
+ *   out[a] = sum_ij T_ij (kap[a] + sum_col lam[col] z_col^p + sum_{e < P} ea[a P + e][i] eb[a P + e][j]),  a < M,   out[M] = sum_ij T_ij.
+ * The matrix element of w exp(-a.x) between two Gaussians of one width, divided by their overlap, is such a product (the weight
+ * folded into ea by the caller); operators with fewer terms carry columns of zeros.
+ *   ea [M P][ni], eb [M P][nj] complex (trajectory index fastest); everything else, the scratch (sc_pair_expect_tiles) and the
+ *   shape of partials as in sc_pair_expect.
+ * Two launches, the guarantees of sc_pair_expect; summation order a function of (ni, nj, M, R, P) alone.  The limits of
+ * sc_pair_expect, 0 <= P <= 1024, M P < 2^24; beyond: SC_ERR_UNSUPPORTED.  P = 0: ea, eb may be NULL.  P > 0 with a NULL ea or eb,
+ * P < 0 and what sc_pair_expect refuses: SC_ERR_BAD_ARGUMENT.  ni <= 0 or nj <= 0: out = 0. */
+int sc_pair_expect_exp(const double *X1, const double *Y1, int32_t K1, const double *X2, const double *Y2, int32_t K2,
+                       const double *rs_i, const double *rs_j, const double *ib, const double *ik, const double *wb,
+                       const double *wk, int64_t ni, int64_t nj, const double *za, const double *zb, const double *lam,
+                       const double *kap, int32_t M, int32_t R, const double *ea, const double *eb, int32_t P, double *partials,
+                       double *out, void *stream);
+
 /* Cross-correlation of the Herman-Kluk wavepacket with K target coherent states |q_k, p_k, Gamma_0>, behind
  * HermanKlukPropagator.cross_correlation() and run(targets=...) (not in the reference, whose CoherentStatesOverlap,
  * propagators.py:181-240, defines the overlap).  With dq = q_k - q_i, dp = p_k - p_i and A, B, C, fac the

@@ -406,6 +406,49 @@ def fold_expectation_operators(c, m, K, n, W, Gamma_t):
     return uq.contiguous(), up.contiguous(), lam_out.contiguous(), kappa.contiguous(), R
 
 
+def fold_exponential_operators(w, a, Gamma_t):
+    """(uq, up, mu): the matrix element of the operators  sum_e w_a,e exp(-a_a,e . x)  between two Gaussians |q_i, p_i, Gamma_t>,
+    |q_j, p_j, Gamma_t> of ONE width, divided by their overlap, as P PRODUCT columns per operator.  With
+    B = (2 Gamma_t)^+ and the pair mean xbar of ``fold_expectation_operators`` the element of one term is
+        w exp(-a.xbar + 1/2 a^T B a) = mu exp(-alpha_i) conj(exp(-alpha_j)),    alpha_i = uq.q_i + up.p_i,
+        uq = a / 2,   up = -i B a / hbar,   mu = w exp(1/2 a^T B a)       (real a: a.xbar = alpha_i + conj(alpha_j)).
+    w (M, P) real or complex, a (M, P, D) real; returns complex (M, P, D) twice and complex (M, P).  A term with w = 0 is padding:
+    its forms are zero, whatever its a.  ValueError for shapes that do not agree, M < 1, a non-finite entry, and an a with w != 0
+    outside the range of Gamma_t (relative 1e-8, the test of ``fold_expectation_operators``), naming the operator and the term."""
+    Gamma_t = as_f64(Gamma_t)
+    D = Gamma_t.shape[0]
+    try:
+        w = torch.as_tensor(w)
+        w = w.detach().cpu().to(C128) if w.is_complex() else as_f64(w).to(C128)
+        a = as_f64(a)
+    except (TypeError, ValueError, RuntimeError) as err:
+        raise ValueError(f"operators: ex: a pair (w, a) of arrays, a real, is expected ({err})")
+    if w.dim() != 2 or a.dim() != 3 or tuple(a.shape) != tuple(w.shape) + (D,) or w.shape[0] < 1:
+        raise ValueError(f"operators: ex = (w, a) with w of shape (M, P), M >= 1, and a of shape (M, P, {D}) is expected, got "
+                         f"{tuple(w.shape)} and {tuple(a.shape)}")
+    if not bool(torch.isfinite(torch.view_as_real(w)).all()) or not bool(torch.isfinite(a).all()):
+        raise ValueError("operators: non-finite entry in ex")
+    e, V = _eigh(Gamma_t)
+    keep = abs(e) > ZERO
+    Vk = V[:, keep]
+    B = torch.einsum('ij,j,kj->ik', Vk, 0.5 / e[keep], Vk)          # (2 Gamma_t)^+
+    used = w != 0
+    a = a * used.unsqueeze(2)
+    outside = torch.linalg.norm(a - (a @ Vk) @ Vk.T, dim=2) > 1.0e-8 * torch.linalg.norm(a, dim=2)
+    if bool(outside.any()):
+        op, term = (int(t) for t in torch.nonzero(outside)[0])
+        raise ValueError(f"operators: a of term {term} of operator {op} of ex has a component outside the range of Gamma_t: the "
+                         "matrix element along a null direction does not exist")
+    aB = a @ B                                                       # rows (B a)^T, B symmetric
+    mu = w * torch.exp(0.5 * (aB * a).sum(2))
+    if not bool(torch.isfinite(torch.view_as_real(mu)).all()):
+        op, term = (int(t) for t in torch.nonzero(~torch.isfinite(torch.view_as_real(mu)).all(2))[0])
+        raise ValueError(f"operators: term {term} of operator {op} of ex: w exp(a^T B a / 2) is not finite")
+    uq = torch.complex(0.5 * a, torch.zeros_like(a))
+    up = torch.complex(torch.zeros_like(a), -aB / hbar)
+    return uq.contiguous(), up.contiguous(), mu.contiguous()
+
+
 def time_grid(nt, dt):
     """t_k of the propagator: t accumulates `t += dt` (propagators.py:655), not k*dt"""
     t, out = 0.0, np.empty(nt)

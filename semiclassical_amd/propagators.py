@@ -2167,7 +2167,7 @@ class HermanKlukPropagator(object):
         v = self.coefficients()
         return X1, Y1, X2, Y2, rs, ib, ik, (oc.fac * v.conj()).contiguous(), v.contiguous()
 
-    def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True):
+    def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True, ex=None):
         """Expectation values of M quadratic operators in the wavepacket (not in the reference):
 
             A_a = c_a + x_a.x + 1/2 x^T xx_a x + p_a.p + 1/2 p^T pp_a p        (p = -i hbar d/dx; no x-p cross terms),
@@ -2184,14 +2184,28 @@ class HermanKlukPropagator(object):
         non-symmetric xx or pp and non-finite entries.  The value is then the formula with the pseudo-inverse conventions of the
         overlaps.
 
+        ``ex=(w, a)`` adds  sum_e w_a,e exp(-a_a,e . x)  to operator a: ``w`` (M, P) real or complex, ``a``
+        (M, P, D) real, M as in the other parts (which may then all be None); an operator with fewer terms has w = 0 in the others.
+        Every a with w != 0 has to lie in the range of Gamma_t (``ValueError`` naming operator and term).  The exponentials of the
+        trajectories' own positions are formed on the device; one that is not finite -- a trajectory far out on the repulsive wall
+        -- is a ``ValueError`` naming the term.  The pair sum then runs in ``sc_pair_expect_exp``; without ``ex`` nothing changes.
+
         The pair sum runs in ``sc_pair_expect`` on the operands ``norm()`` packs.  Rank-local: this rank's trajectories with
         this rank's weights, no communication.  The discard mask (discard_nonsymplectic) is ignored: discarded trajectories
         contribute as ever.  No step is taken and the state is not touched.  The value is quadratic in the ensemble, not
         additive over batches: there is no hook in ``run()``."""
         self._refuse_thermal("expectation()", "it describes one pure state, the trajectories belong to a mixture")
         dev, d, n = self.device, self.dim, self.ntraj
+        if ex is not None:
+            if not isinstance(ex, (tuple, list)) or len(ex) != 2:
+                raise ValueError("operators: ex = (w, a) with w of shape (M, P) and a of shape (M, P, D) is expected")
+            euq, eup, mu = hostmath.fold_exponential_operators(ex[0], ex[1], self._Gt)
+            if all(t is None for t in (c, x, xx, p, pp)):
+                c = torch.zeros(mu.shape[0], dtype=F64)
         uq, up, lam, kap, R = hostmath.fold_expectation_operators(c, x, xx, p, pp, self._Gt)
         M = int(kap.shape[0])
+        if ex is not None and int(mu.shape[0]) != M:
+            raise ValueError(f"operators: the parts have to hold the same number M >= 1 of operators, got {M} and {int(mu.shape[0])} in ex")
         X1, Y1, X2, Y2, rs, ib, ik, wb, wk = self._pair_operands()
         # the columns a_i = uq.q_i + up.p_i from the actual positions, [M (1 + R)][n]; the kets take the conjugates
         qT, pT = self._qp[:, :d].T, self._qp[:, d:].T
@@ -2202,10 +2216,17 @@ class HermanKlukPropagator(object):
         tiles = lib.sc_pair_expect_tiles(n, n)
         partials = torch.empty((max(int(tiles), 1), M + 1, 2), dtype=F64, device=dev)
         out = torch.empty(M + 1, dtype=C128, device=dev)
+        if ex is not None:
+            ea, eb, P = self._exponential_columns(euq, eup, mu)
         with self._timed("expectation"):
-            check(lib.sc_pair_expect(ptr(X1), ptr(Y1), 2 * d, ptr(X2), ptr(Y2), 3 * d, ptr(rs), ptr(rs), ptr(ib), ptr(ik), ptr(wb),
-                                     ptr(wk), n, n, ptr(za), ptr(zb), ptr(lam_d), ptr(kap_d), M, R, ptr(partials), ptr(out),
-                                     self._stream()))
+            if ex is None:
+                check(lib.sc_pair_expect(ptr(X1), ptr(Y1), 2 * d, ptr(X2), ptr(Y2), 3 * d, ptr(rs), ptr(rs), ptr(ib), ptr(ik), ptr(wb),
+                                         ptr(wk), n, n, ptr(za), ptr(zb), ptr(lam_d), ptr(kap_d), M, R, ptr(partials), ptr(out),
+                                         self._stream()))
+            else:
+                check(lib.sc_pair_expect_exp(ptr(X1), ptr(Y1), 2 * d, ptr(X2), ptr(Y2), 3 * d, ptr(rs), ptr(rs), ptr(ib), ptr(ik),
+                                             ptr(wb), ptr(wk), n, n, ptr(za), ptr(zb), ptr(lam_d), ptr(kap_d), M, R, ptr(ea), ptr(eb),
+                                             P, ptr(partials), ptr(out), self._stream()))
         res = out.cpu().numpy()
         norm2 = float(res[M].real)
         return (res[:M] / norm2 if normalise else res[:M].copy()), norm2
@@ -2265,6 +2286,62 @@ class HermanKlukPropagator(object):
                              "projecting it is the caller's decision (expectation() with a projected pp)")
         W = torch.diag(1.0 / hostmath.as_f64(potential.masses()))
         vals, _ = self.expectation(c=torch.tensor([const], dtype=F64), x=lin.unsqueeze(0), xx=H.unsqueeze(0), pp=W.unsqueeze(0))
+        return float(vals[0].real)
+
+    def _exponential_columns(self, uq, up, mu):
+        """(ea, eb, P): the product columns of ``hostmath.fold_exponential_operators`` from the actual positions, [M P][n] complex on
+        the device: ea_i = mu exp(-alpha_i), eb_j = conj(exp(-alpha_j)), alpha_i = uq.q_i + up.p_i -- n M P exponentials, not n^2"""
+        dev, d = self.device, self.dim
+        M, P = int(mu.shape[0]), int(mu.shape[1])
+        if P == 0:
+            return None, None, 0
+        qT, pT = self._qp[:, :d].T, self._qp[:, d:].T
+        uq, up = uq.reshape(-1, d).to(dev), up.reshape(-1, d).to(dev)
+        alpha = torch.complex(uq.real @ qT + up.real @ pT, uq.imag @ qT + up.imag @ pT)
+        e = torch.exp(-alpha)
+        ea, eb = (mu.reshape(-1, 1).to(dev) * e).contiguous(), e.conj().resolve_conj().contiguous()
+        bad = ~torch.isfinite(torch.view_as_real(ea)).all(2).all(1)
+        if bool(bad.any()):
+            col = int(torch.nonzero(bad)[0])
+            raise ValueError(f"operators: term {col % P} of operator {col // P} of ex: exp(-a.x) is not finite at a trajectory's "
+                             "position (it has run far out on the repulsive wall)")
+        return ea, eb, P
+
+    def anharmonic_energy_expectation(self, potential):
+        """<psi| p^T m^-1 p / 2 + V(x) |psi> / norm()**2 on the separable anharmonic surfaces: a float, the
+        real part of one ``expectation`` value with ``ex``.  ``MorsePotential`` with chi != 0: V = sum_k D_k (1 - 2 exp(-a_k x_k) +
+        exp(-2 a_k x_k)) with the object's own a and D (modes with the 1e-4 fix-up included) -- D squared p-columns and 2 D
+        exponentials in one operator; ``NonHarmonicPotential``: the eps Morse part as two exponentials and a constant per
+        dimension, (1 - eps) x^2 / 2 as ``xx``.  For the potentials of ``energy_expectation`` its value.  sGDML and quartic force
+        fields: ``NotImplementedError``.  A singular Gamma_t is refused with ``ValueError`` as there.
+
+        V is a sum of terms of alternating sign that are each about D_k = omega / (4 chi): rounding is relative to the sum of the
+        absolute terms, about 50 <V> at chi = 0.02 and 1e4 <V> at the 1e-4 fix-up."""
+        from . import potentials as P
+        self._refuse_thermal("anharmonic_energy_expectation()", "it describes one pure state, the trajectories belong to a mixture")
+        d = self.dim
+        if isinstance(potential, P.MolecularHarmonicPotential) or (isinstance(potential, P.MorsePotential) and potential._is_harmonic()):
+            return self.energy_expectation(potential)
+        if isinstance(potential, P.MorsePotential):
+            depth, rate = hostmath.as_f64(potential.D), hostmath.as_f64(potential.a)
+            H = None
+        elif isinstance(potential, P.NonHarmonicPotential):
+            eps, rate = hostmath.as_f64(potential.eps), hostmath.as_f64(potential.b)
+            depth = 0.5 * eps / rate ** 2
+            H = torch.diag(1.0 - eps).unsqueeze(0)
+        else:
+            raise NotImplementedError(f"anharmonic_energy_expectation: {type(potential).__name__} is neither a Morse-type potential "
+                                      "(MorsePotential, NonHarmonicPotential) nor one with a constant Hessian: <V> has no closed form")
+        if potential.dimensions() != d:
+            raise ValueError(f"anharmonic_energy_expectation: the potential has {potential.dimensions()} dimensions, the propagator {d}")
+        if not self._width_has_full_rank():
+            raise ValueError("anharmonic_energy_expectation: Gamma_t is singular, the kinetic energy along its null directions does "
+                             "not exist; projecting it is the caller's decision (expectation() with a projected pp)")
+        # D_k (1 - exp(-a_k x_k))^2 = D_k - 2 D_k exp(-a_k x_k) + D_k exp(-2 a_k x_k)
+        w = torch.cat((-2.0 * depth, depth)).unsqueeze(0)
+        a = torch.cat((torch.diag(rate), torch.diag(2.0 * rate))).unsqueeze(0)
+        W = torch.diag(1.0 / hostmath.as_f64(potential.masses())).unsqueeze(0)
+        vals, _ = self.expectation(c=depth.sum().reshape(1), xx=H, pp=W, ex=(w, a))
         return float(vals[0].real)
 
     def wavefunction(self, x):
@@ -2640,7 +2717,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
-    def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True):
+    def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True, ex=None):
         raise NotImplementedError("expectation is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
