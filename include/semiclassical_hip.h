@@ -704,6 +704,34 @@ int sc_wm_pair_sum(const double *qp, const double *coef, const double *cqq, cons
                    const double *dvecp, const double *U, int64_t n, int32_t D, int32_t dprime, double *partials,
                    void *stream);
 
+/* Expectation values of M operators in the Walton-Manolopoulos wavepacket, behind WaltonManolopoulosPropagator.wm_expectation()
+ * (not in the reference), on the operands of sc_wm_pair_sum_rect:
+ *   out[a] = sum_ij T_ij F_a,ij  (a < M),   out[M] = sum_ij T_ij,   T_ij = conj(v_i) O_ij v_j the pair term of sc_wm_pair_sum_rect,
+ *   F_a,ij = kap_a + sum_col lam_col f_col over the 1 + R columns col = a (1 + R) ... of operator a,
+ *   f_col  = l_col for column 0 of an operator,  l_col^2 + s_col^T D'^-1 s_col for its columns 1 ... R,
+ *   l_col  = za[col][i] + zb[col][j] + g_col . b' + s_col^T D'^-1 b',
+ *   s_col  = sfix[col], plus sket[a][j] for column 0 of operator a when sket is not NULL,
+ * with D' = conj(C'_i) + C'_j, b' = U^T C_j dQ + conj(d'_i) + d'_j of the norm (Q_i + U D'^-1 b' is the mean of x under the product
+ * of the two Gaussians, U D'^-1 U^T its covariance).  za [C][ni], zb [C][nj] complex (trajectory index fastest), g, sfix [C][d']
+ * complex, sket NULL or [M][nj][d'] complex, lam [C] real, kap [M] complex, C = M (1 + R); out [M + 1] complex; partials: scratch of
+ * sc_wm_pair_expect_tiles(ni, nj) * (M + 1) * 2 doubles.
+ * One wavefront per pair for every shape: D' is eliminated once with partial pivoting, b' and the border vectors carried as extra
+ * columns and rows, det(D'/2pi) as mantissa x 2^e.  Two launches (tiles, then their sum); no atomics, nothing skipped by magnitude,
+ * summation order a function of (ni, nj, D, d', M, R) alone: the same bits in every call.
+ * The border columns of a launch share the LDS region of a pair with D': sc_wm_pair_expect_capacity(D, d') is the largest C of one
+ * call (4 at d' = 96; 0 for a shape outside the limits); the caller splits larger operator sets into several calls (columns of one
+ * operator may go to different calls: F is their sum).
+ * Limits: those of sc_wm_pair_sum_rect (D <= 512, d' <= 96, fewer than 2^31 tiles), 1 <= M <= 65535, M (1 + R) <= the capacity;
+ * beyond: SC_ERR_UNSUPPORTED, with the capacity in the text.  A NULL pointer other than sket, M < 1, R < 0: SC_ERR_BAD_ARGUMENT.
+ * ni <= 0 or nj <= 0: out = 0. */
+int64_t sc_wm_pair_expect_tiles(int64_t ni, int64_t nj);
+int32_t sc_wm_pair_expect_capacity(int32_t D, int32_t dprime);
+int sc_wm_pair_expect(const double *qp_i, const double *coef_i, const double *cqqp_i, const double *dvecp_i, int64_t ni,
+                      const double *qp_j, const double *coef_j, const double *cqq_j, const double *dvec_j, const double *cqqp_j,
+                      const double *dvecp_j, int64_t nj, const double *U, int32_t D, int32_t dprime, const double *za,
+                      const double *zb, const double *g, const double *sfix, const double *sket, const double *lam,
+                      const double *kap, int32_t M, int32_t R, double *partials, double *out, void *stream);
+
 /* Energy-conservation guard on the device, reference propagators.py:385-398 (check_energy_conservation).
  * elog[4] = { <T+V>(t-dt), <T+V>(t), largest |change| seen so far, number of steps logged }.
  * The mean of this step is formed from energy_partials; the host raises the reference's RuntimeError when

@@ -406,6 +406,123 @@ def fold_expectation_operators(c, m, K, n, W, Gamma_t):
     return uq.contiguous(), up.contiguous(), lam_out.contiguous(), kappa.contiguous(), R
 
 
+def fold_wm_expectation_operators(c, m, K, n, U):
+    """(vx, nvec, lam, kappa, R): the operators  c_a + m_a.x + 1/2 x^T K_a x + n_a.p  (p = -i hbar d/dx acting on the ket) between two
+    Walton-Manolopoulos Gaussians g_i, g_j of per-trajectory widths, divided by their overlap, as 1 + R columns per operator
+    (DESIGN.md section 4.24).  With the pair mean  xbar = Q_i + U D'^-1 b'  and the covariance  U D'^-1 U^T  the element is
+        kappa_a + sum_col lam_col f_col,    f_0 = l_0,    f_col = l_col^2 + (U^T v_col)^T D'^-1 (U^T v_col)  (col = 1 ... R),
+        l_0 = m.xbar - i hbar [ n.d_j - (C_j n).(xbar - Q_j) ],    l_col = v_col.xbar:
+    column 0 (lam = 1) is the x-form of m plus the p-form of n, columns 1 ... R (lam = lambda_r / 2) the kept eigenpairs of K by the
+    drop rule of ``fold_quadratic_operators``; kappa_a = c_a.  This part does not depend on the trajectories: ``vx`` (M, 1 + R, D)
+    holds m and the eigenvectors, ``nvec`` (M, D) the vectors n, or None without p; ``wm_expectation_columns`` makes the columns of
+    a state from them.  R is the largest number of columns kept by an operator, the others are padded with columns of zeros.
+    c (M,), m, n (M, D), K (M, D, D) real, any of them None (= zeros) but not all; U (D, d') real with orthonormal columns spans the
+    non-zero width modes.  ValueError for shapes that do not agree, a non-finite entry, a K that is not symmetric to 1e-12 of its
+    largest entry, and an m, n or kept eigenvector outside the range of U (relative 1e-8, the test of reduced_density), naming the
+    operator."""
+    U = as_f64(U)
+    D = U.shape[0]
+    parts = {}
+    for name, val, tail in (("c", c, ()), ("x", m, (D,)), ("xx", K, (D, D)), ("p", n, (D,))):
+        if val is None:
+            continue
+        try:
+            t = as_f64(val)
+        except (TypeError, ValueError, RuntimeError) as err:
+            raise ValueError(f"operators: {name}: a real array is expected ({err})")
+        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+            raise ValueError(f"operators: {name} of shape {('M',) + tail} is expected, got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"operators: non-finite entry in {name}")
+        parts[name] = t
+    if not parts:
+        raise ValueError("operators: at least one of c, x, xx, p has to be given")
+    counts = {name: int(t.shape[0]) for name, t in parts.items()}
+    M = next(iter(counts.values()))
+    if M < 1 or any(v != M for v in counts.values()):
+        raise ValueError(f"operators: the parts have to hold the same number M >= 1 of operators, got {counts}")
+
+    def in_range(vec, a, what):
+        outside = torch.linalg.norm(vec - (vec @ U) @ U.T, dim=1) > 1.0e-8 * torch.linalg.norm(vec, dim=1)
+        if bool(outside.any()):
+            raise ValueError(f"operators: {what} of operator {a} has a component outside the range of the widths: the matrix "
+                             "element along a null direction does not exist")
+
+    for name in ("x", "p"):
+        if name in parts:
+            for a in range(M):
+                in_range(parts[name][a:a + 1], a, name)
+    kept = []
+    if "xx" in parts:
+        for a in range(M):
+            lam, vec = _kept_eigenpairs(parts["xx"][a], a, "xx")
+            in_range(vec, a, "xx")
+            kept.append((0.5 * lam, vec))
+    R = max((int(lam.shape[0]) for lam, _ in kept), default=0)
+    vx = torch.zeros((M, 1 + R, D), dtype=torch.float64)
+    lam_out = torch.zeros((M, 1 + R), dtype=torch.float64)
+    lam_out[:, 0] = 1.0
+    if "x" in parts:
+        vx[:, 0] = parts["x"]
+    for a, (lam, vec) in enumerate(kept):
+        r = int(lam.shape[0])
+        lam_out[a, 1:1 + r], vx[a, 1:1 + r] = lam, vec
+    kappa = torch.zeros(M, dtype=C128)
+    if "c" in parts:
+        kappa += parts["c"]
+    nvec = parts["p"].contiguous() if "p" in parts else None
+    return vx.contiguous(), nvec, lam_out.contiguous(), kappa.contiguous(), R
+
+
+def wm_expectation_columns(vx, nvec, Qi, dvecp_i, Qj, cqq_j, dvec_j, dvecp_j, U):
+    """(za, zb, g, sfix, sket): the columns of ``fold_wm_expectation_operators`` for bras i and kets j, as sc_wm_pair_expect takes
+    them.  The linear form of column col is
+        l_col = za[col][i] + zb[col][j] + g_col . b' + s_col^T D'^-1 b',    s_col = sfix[col] (+ sket[a][j] for column 0 of operator a),
+    with D', b' of the pair (C_j dQ enters through b' alone: for n = U n',  (C_j n).(Q_i - Q_j) = -n'.(b' - conj d'_i - d'_j)):
+        x-form of v:   za = v.Q_i,   sfix = U^T v;
+        p-form of n:   za = i hbar n'.conj(d'_i),   zb = -i hbar n.d_j + i hbar n'.d'_j,   g = -i hbar n',   sket = i hbar U^T C_j n.
+    vx (M, 1 + R, D), nvec (M, D) or None on the host; Qi (ni, D), dvecp_i (ni, d'), Qj (nj, D), cqq_j (nj, D, D), dvec_j (nj, D),
+    dvecp_j (nj, d'), U (D, d') on one device.  Returns za (C, ni), zb (C, nj), g, sfix (C, d') complex, C = M (1 + R), and sket
+    (M, nj, d') complex or None (no p)."""
+    dev = Qi.device
+    M, C1, D = vx.shape
+    Uc = U.type(C128)
+    v = vx.reshape(M * C1, D).to(dev)
+    za = (v @ Qi.T).type(C128)
+    zb = torch.zeros((M * C1, Qj.shape[0]), dtype=C128, device=dev)
+    sfix = (v @ U).type(C128)
+    g = torch.zeros_like(sfix)
+    sket = None
+    if nvec is not None:
+        nv = nvec.to(dev).type(C128)                       # (M, D)
+        npr = nv @ Uc                                       # n' = U^T n
+        col0 = torch.arange(M, device=dev) * C1
+        za[col0] += 1j * hbar * (npr @ dvecp_i.conj().T)
+        zb[col0] += -1j * hbar * (nv @ dvec_j.T) + 1j * hbar * (npr @ dvecp_j.T)
+        g[col0] += -1j * hbar * npr
+        sket = (1j * hbar * torch.einsum('jab,mb,ak->mjk', cqq_j, nv, Uc)).contiguous()
+    return za.contiguous(), zb.contiguous(), g.contiguous(), sfix.contiguous(), sket
+
+
+def wm_expectation_launches(lam, cap):
+    """The operator set of ``fold_wm_expectation_operators`` cut into calls of sc_wm_pair_expect that hold at most ``cap`` >= 2
+    columns each.  A call carries operators of 1 + R' columns, R' = min(R, cap - 1); an operator of more squared columns is cut into
+    several such pieces (F is the sum of its columns: the first piece carries column 0 and kappa, the others a column 0 of zeros),
+    pieces whose lam are all zero are left out.  lam (M, 1 + R).  Returns (R', calls): every call a list of pieces
+    (operator, carries column 0, [indices of its squared columns in 1 ... R]), cap // (1 + R') pieces at the most."""
+    M, C1 = lam.shape
+    Rl = min(C1 - 1, cap - 1)
+    pieces = []
+    for a in range(M):
+        pieces.append((a, True, list(range(1, 1 + Rl))))
+        for r0 in range(1 + Rl, C1, max(Rl, 1)):
+            sq = list(range(r0, min(r0 + Rl, C1)))
+            if bool((lam[a, sq] != 0).any()):
+                pieces.append((a, False, sq))
+    per = cap // (1 + Rl)
+    return Rl, [pieces[k:k + per] for k in range(0, len(pieces), per)]
+
+
 def fold_exponential_operators(w, a, Gamma_t):
     """(uq, up, mu): the matrix element of the operators  sum_e w_a,e exp(-a_a,e . x)  between two Gaussians |q_i, p_i, Gamma_t>,
     |q_j, p_j, Gamma_t> of ONE width, divided by their overlap, as P PRODUCT columns per operator.  With

@@ -2540,6 +2540,51 @@ def _NULL_POT(dim):
     return _lib.sc_potential(kind=_lib.SC_POT_HARMONIC_SEP, dim=dim)
 
 
+def wm_pair_expect(bra, ket, U, za, zb, g, sfix, sket, lam, kap, stream=None):
+    """sum_ij T_ij F_a,ij of M operators and sum_ij T_ij through ``sc_wm_pair_expect`` (include/semiclassical_hip.h), in as many calls
+    as the columns need: one call holds ``sc_wm_pair_expect_capacity(D, d')`` columns (``hostmath.wm_expectation_launches``), the
+    pieces of an operator are added on the host in the order of the calls.  ``bra`` = (qp, coef, cqqp, dvecp), ``ket`` = (qp, coef,
+    cqq, dvec, cqqp, dvecp), U (D, d'), za (C, ni), zb (C, nj), g, sfix (C, d') complex, sket (M, nj, d') complex or None, lam
+    (M, 1 + R) real, kap (M,) complex: contiguous tensors on one device.  Returns the complex ndarray (M + 1,), entry M = sum T."""
+    dev = U.device
+    D, dp = U.shape
+    ni, nj = int(bra[0].shape[0]), int(ket[0].shape[0])
+    M, C1 = lam.shape
+    cap = int(lib.sc_wm_pair_expect_capacity(D, dp))
+    tiles = max(int(lib.sc_wm_pair_expect_tiles(ni, nj)), 1)
+    rows = [ptr(t) for t in bra] + [ni] + [ptr(t) for t in ket] + [nj, ptr(U), D, dp]
+
+    def call(za, zb, g, sfix, sket, lam, kap, m, r):
+        partials = torch.empty((tiles, m + 1, 2), dtype=F64, device=dev)
+        out = torch.empty(m + 1, dtype=C128, device=dev)
+        check(lib.sc_wm_pair_expect(*rows, ptr(za), ptr(zb), ptr(g), ptr(sfix), ptr(sket), ptr(lam), ptr(kap), m, r, ptr(partials),
+                                    ptr(out), stream))
+        return out.cpu().numpy()
+
+    if M * C1 <= cap or cap < 2:            # (a shape outside the limits has capacity 0: the library names the limits)
+        return call(za, zb, g, sfix, sket, lam.contiguous(), kap, M, C1 - 1)
+    Rl, calls = hostmath.wm_expectation_launches(lam.cpu(), cap)
+    # one more column and one more operator of zeros, for the padding and for column 0 of an operator's later pieces
+    pad = lambda t: torch.cat((t, torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)))
+    za, zb, g, sfix, lam_f = pad(za), pad(zb), pad(g), pad(sfix), pad(lam.reshape(-1))
+    kap_p = pad(kap)
+    sket = pad(sket) if sket is not None else None
+    res = np.zeros(M + 1, dtype=np.complex128)
+    for k, pieces in enumerate(calls):
+        cols, ops = [], []
+        for a, first, sq in pieces:
+            cols += [a * C1 if first else M * C1] + [a * C1 + r for r in sq] + [M * C1] * (Rl - len(sq))
+            ops.append(a if first else M)
+        ci, oi = torch.tensor(cols, device=dev), torch.tensor(ops, device=dev)
+        out = call(za[ci].contiguous(), zb[ci].contiguous(), g[ci].contiguous(), sfix[ci].contiguous(),
+                   sket[oi].contiguous() if sket is not None else None, lam_f[ci].contiguous(), kap_p[oi].contiguous(), len(pieces), Rl)
+        for e, (a, _, _) in enumerate(pieces):
+            res[a] += out[e]
+        if k == 0:
+            res[M] = out[len(pieces)]
+    return res
+
+
 class WaltonManolopoulosPropagator(HermanKlukPropagator):
     """Walton-Manolopoulos (Filinov-smoothed) propagator, reference propagators.py:1077-1719.
 
@@ -2691,12 +2736,8 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         from . import distributed as Dm
         group = self._norm_group(across_ranks, group)
         dev, n, d = self.device, self.ntraj, self.dim
-        coef, cqq, dvec = self._export()
-        U = self._wm_bufs["U"]                                   # (D, d') real
-        Uc = U.type(C128)
+        coef, cqq, dvec, cqqp, dvecp, U = self._wm_pair_operands()
         dp = U.shape[1]
-        cqqp = torch.einsum('ak,nab,bl->nkl', Uc, cqq, Uc).contiguous()      # U^T CQQ U per trajectory
-        dvecp = (dvec @ Uc).contiguous()
         flat = lambda t: torch.view_as_real(t.contiguous()).reshape(t.shape[0], -1)
         ket = torch.cat((self._qp, flat(coef.unsqueeze(1)), flat(cqq), flat(dvec), flat(cqqp), flat(dvecp)), 1)
         ket = Dm.all_gather_rows(ket, group)
@@ -2713,13 +2754,81 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         Dm.all_reduce_sum(slot, group)
         return float(torch.sqrt(slot[0]).item())
 
+    def _wm_pair_operands(self):
+        """(coef, cqq, dvec, cqqp, dvecp, U): the export of the current step and its projections U^T CQQ U, U^T dvec per trajectory,
+        the operands of the pair sums; U (D, d') real"""
+        coef, cqq, dvec = self._export()
+        U = self._wm_bufs["U"]
+        Uc = U.type(C128)
+        cqqp = torch.einsum('ak,nab,bl->nkl', Uc, cqq, Uc).contiguous()
+        dvecp = (dvec @ Uc).contiguous()
+        return coef, cqq, dvec, cqqp, dvecp, U
+
     def reduced_density(self, directions, s):
         raise NotImplementedError("reduced_density is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
 
     def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True, ex=None):
         raise NotImplementedError("expectation is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
-                                  "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them")
+                                  "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them "
+                                  "(wm_expectation and wm_wavepacket_moments solve a d' x d' system per pair instead)")
+
+    def wm_expectation(self, c=None, x=None, xx=None, p=None, normalise=True):
+        """Expectation values of M operators in the WM wavepacket (not in the reference):
+
+            A_a = c_a + x_a.x + 1/2 x^T xx_a x + p_a.p          (p = -i hbar d/dx; no quadratic momentum part),
+            E_a = <psi|A_a|psi> = sum_ij conj(v_i) O_ij v_j F_a,ij,      N2 = sum_ij conj(v_i) O_ij v_j = norm()**2,
+
+        O_ij the overlaps and v the coefficients of ``norm()``, F_a,ij the matrix element of A_a between the Gaussians of the
+        trajectories i and j divided by their overlap: with D' and b' of the pair, the mean of x is Q_i + U D'^-1 b' and its
+        covariance U D'^-1 U^T (``hostmath.fold_wm_expectation_operators``).  ``c`` (M,), ``x``, ``p`` (M, D), ``xx`` (M, D, D) real
+        symmetric; any of them may be None (= zeros), M is taken from the ones given.  Returns ``(values, norm2)``: the complex
+        ndarray (M,) of E_a / N2 -- of E_a with ``normalise=False`` -- and the float N2.  The imaginary part of the value of a
+        Hermitian operator is rounding.
+
+        Every x_a, p_a and eigenvector of xx_a (eigenvalues above 1e-12 of the largest) has to lie in the span of the non-zero
+        width modes: ``ValueError`` naming the operator otherwise, as for parts whose shapes do not agree, a non-symmetric xx and
+        non-finite entries.
+
+        The pair sum runs in ``sc_wm_pair_expect`` on the operands ``norm()`` packs, in as many calls as the operators' columns
+        need (``wm_pair_expect``).  Rank-local: this rank's trajectories with this rank's weights, no communication.  The discard
+        mask (discard_nonsymplectic) is ignored: discarded trajectories contribute as ever.  No step is taken and the state is
+        not touched.  The value is quadratic in the ensemble, not additive over batches: there is no hook in ``run()``."""
+        d = self.dim
+        vx, nvec, lam, kap, R = hostmath.fold_wm_expectation_operators(c, x, xx, p, self._wm_host.U)
+        coef, cqq, dvec, cqqp, dvecp, U = self._wm_pair_operands()
+        Q = self._qp[:, :d]
+        za, zb, g, sfix, sket = hostmath.wm_expectation_columns(vx, nvec, Q, dvecp, Q, cqq, dvec, dvecp, U)
+        with self._timed("wm_expectation"):
+            res = wm_pair_expect((self._qp, coef, cqqp, dvecp), (self._qp, coef, cqq, dvec, cqqp, dvecp), U, za, zb, g, sfix, sket,
+                                 lam.to(self.device), kap.to(self.device), self._stream())
+        M = int(kap.shape[0])
+        norm2 = float(res[M].real)
+        return (res[:M] / norm2 if normalise else res[:M].copy()), norm2
+
+    def wm_wavepacket_moments(self, directions=None):
+        """Centre and width of the WM wavepacket along chosen directions u: a dict with ``x`` = <u.x>, ``p`` = <u.p>, ``var_x`` =
+        <(u.x)^2> - <u.x>^2, real ndarrays (M,) of the values normalised with ``norm2`` = norm()**2, which comes along (no ``var_p``:
+        ``wm_expectation`` has no quadratic momentum part).  ``directions`` as in ``HermanKlukPropagator.reduced_density``: mode
+        indices or vectors of length D; None means the D axes, for widths of full rank only (``ValueError`` otherwise: give
+        directions in the span of the non-zero width modes).  One ``wm_expectation`` call with three operators per direction;
+        what is said there about ranks, the discard mask and the state holds here."""
+        d = self.dim
+        if directions is None:
+            if self._wm_host.dprime != d:
+                raise ValueError("wm_wavepacket_moments: the widths are singular, the moments along their null directions do not "
+                                 "exist: give directions in the span of the non-zero width modes")
+            U = torch.eye(d, dtype=F64)
+        else:
+            U = self._density_directions(directions)
+            if bool((torch.linalg.norm(U, dim=1) == 0).any()):
+                raise ValueError("directions: zero vector")
+        Md = U.shape[0]
+        zv, zm = torch.zeros((Md, d), dtype=F64), torch.zeros((Md, d, d), dtype=F64)
+        uu = 2.0 * U.unsqueeze(2) * U.unsqueeze(1)          # 1/2 x^T (2 u u^T) x = (u.x)^2
+        vals, norm2 = self.wm_expectation(x=torch.cat((U, zv, zv)), xx=torch.cat((zm, uu, zm)), p=torch.cat((zv, zv, U)))
+        ex, exx, ep = (vals[k * Md:(k + 1) * Md].real for k in range(3))
+        return {"x": ex, "p": ep, "var_x": exx - ex ** 2, "norm2": norm2}
 
     def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=()):
         # no pairs or visits; run(targets=...) and run(operators=...) are refused before the loop starts
