@@ -732,6 +732,25 @@ int sc_wm_pair_expect(const double *qp_i, const double *coef_i, const double *cq
                       const double *zb, const double *g, const double *sfix, const double *sket, const double *lam,
                       const double *kap, int32_t M, int32_t R, double *partials, double *out, void *stream);
 
+/* sc_wm_pair_expect with a kind and a slot of per-ket border vectors per column, behind wm_operator_expectation() and
+ * wm_energy_expectation() of the WaltonManolopoulosPropagator (not in the reference).  Operator a owns the
+ * columns col = a cols ... a cols + cols - 1, and  F_a,ij = kap_a + sum_col lam_col f_col  with l_col as above and
+ *   kind[col] = 0:  f = l,      1:  f = l^2 + s^T D'^-1 s,      2:  f = exp(-l + 1/2 s^T D'^-1 s),
+ *   s_col = sfix[col]  if ketcol[col] = -1,   sfix[col] + sket[p][j]  if ketcol[col] = p  (0 <= p < S).
+ * A quadratic momentum operator 1/2 p^T W p acting on the ket is a kind-1 column with a per-ket vector per eigenpair of W, the
+ * operator exp(-a.x) a kind-2 column with s = U^T a.  kind, ketcol [C] int32 on the device, C = M cols; sket [S][nj][d'] complex, NULL
+ * when S = 0; the other operands, partials and out as sc_wm_pair_expect.  A column that pads an operator has kind 0 and lam = 0
+ * (never kind 2: 0 x inf).  The entry reads kind and ketcol back to the host once and checks them (it synchronises the stream).
+ * Same kernel body, capacity (sc_wm_pair_expect_capacity), tiles, order of the sums and limits as sc_wm_pair_expect: M cols <= the
+ * capacity, beyond: SC_ERR_UNSUPPORTED with the capacity in the text.  A NULL pointer other than sket with S = 0, M < 1, cols < 1,
+ * S < 0, a kind outside 0 ... 2 and a ketcol outside -1 ... S - 1: SC_ERR_BAD_ARGUMENT. */
+int sc_wm_pair_expect_cols(const double *qp_i, const double *coef_i, const double *cqqp_i, const double *dvecp_i, int64_t ni,
+                           const double *qp_j, const double *coef_j, const double *cqq_j, const double *dvec_j, const double *cqqp_j,
+                           const double *dvecp_j, int64_t nj, const double *U, int32_t D, int32_t dprime, const double *za,
+                           const double *zb, const double *g, const double *sfix, const double *sket, int32_t S,
+                           const int32_t *ketcol, const int32_t *kind, const double *lam, const double *kap, int32_t M, int32_t cols,
+                           double *partials, double *out, void *stream);
+
 /* Energy-conservation guard on the device, reference propagators.py:385-398 (check_energy_conservation).
  * elog[4] = { <T+V>(t-dt), <T+V>(t), largest |change| seen so far, number of steps logged }.
  * The mean of this step is formed from energy_partials; the host raises the reference's RuntimeError when

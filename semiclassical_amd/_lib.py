@@ -207,6 +207,10 @@ SIGNATURES = {
                                     c_double_p, c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_int32, c_double_p,
                                     c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, C.c_int32,
                                     c_double_p, c_double_p, C.c_void_p]),
+    "sc_wm_pair_expect_cols": (C.c_int, [c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                         c_double_p, c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_int32, c_double_p,
+                                         c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                         c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_void_p]),
     "sc_hk_cross_rows": (C.c_int64, [C.c_int64, C.c_int64]),
     "sc_hk_cross": (C.c_int, [P(sc_state), c_double_p, c_double_p, c_double_p, C.c_int32, C.c_double, c_double_p, C.c_int32,
                               c_double_p, c_double_p, C.c_double, C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_void_p,

@@ -27,6 +27,11 @@
 //
 // A launch carries the columns that fit: nt <= 128 (two rows per lane) and nt * (nt | 1) complex within the LDS of a workgroup;
 // sc_wm_pair_expect_capacity(D, d') is that number (4 at d' = 96).
+//
+// wm_expect_cols_kernel (sc_wm_pair_expect_cols) is the same pair loop, wme_body<true>, with a kind and a
+// slot of per-ket border vectors per column: f_col = l_col (kind 0), l_col^2 + s_col^T D'^-1 s_col (1), exp(-l_col + 1/2 s_col^T
+// D'^-1 s_col) (2), s_col = sfix[col] (+ sket[ketcol[col]][j]) -- quadratic momentum operators acting on the ket and exp(-a.x).
+// Same region, capacity and order of the sums.
 #include <algorithm>
 
 #include "sc_expect_tile.h"
@@ -52,6 +57,11 @@ struct WmExpectArgs {
     double *partials;                   // [tiles][M + 1][2]
 };
 
+struct WmExpectColsArgs {
+    WmExpectArgs a;                     // R = cols - 1; sket [S][nj][d'] complex, indexed by ketcol
+    const int *kind, *ketcol;           // [C]
+};
+
 // LDS operations of one wavefront execute in order; the fences keep the compiler from moving them across the sync
 __device__ __forceinline__ void wme_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -67,7 +77,13 @@ __device__ __noinline__ cplx wme_pair_term(cplx ex, cplx mant, int expo, cplx vi
     return c_mul(c_mul(c_conj(vi), vj), ol);
 }
 
-__global__ __launch_bounds__(256) void wm_expect_kernel(WmExpectArgs A, int stride, int region) {
+// exp(z) of a kind-2 column; not inlined for the reason given at wme_pair_term (inlined, the kernel took 179 VGPRs against 138)
+__device__ __noinline__ cplx wme_col_exp(cplx z) { return c_exp(z); }
+
+// The pair loop of both kernels.  COLS = false: the columns of sc_wm_pair_expect (column 0 of an operator linear with the per-ket
+// border vector of its operator, the others squared); COLS = true: kind[col] and ketcol[col] of sc_wm_pair_expect_cols.
+template <bool COLS>
+__device__ __forceinline__ void wme_body(const WmExpectArgs &A, const int *kind, const int *ketcol, int stride, int region) {
     extern __shared__ double2 smem2[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, D = A.D, dp = A.dp;
     const int cols = 1 + A.R, nc = A.M * cols, nt = dp + 1 + nc;
@@ -123,8 +139,9 @@ __global__ __launch_bounds__(256) void wm_expect_kernel(WmExpectArgs A, int stri
             if (r < dp) { M[r * stride + dp] = bq[h]; M[dp * stride + r] = bq[h]; }
         }
         for (int c = 0; c < nc; ++c) {                        // the border vectors, as columns and as rows
-            const int op = c / cols;
-            const bool perket = A.sket != nullptr && c == op * cols;
+            int op = c / cols;
+            bool perket = A.sket != nullptr && c == op * cols;
+            if constexpr (COLS) { op = ketcol[c]; perket = op >= 0; }      // the slot of the column's per-ket vectors
             for (int r = lane; r < dp; r += 64) {
                 cplx s = ((const cplx *)A.sfix)[(int64_t)c * dp + r];
                 if (perket) s = c_add(s, ((const cplx *)A.sket)[((int64_t)op * A.n + j) * dp + r]);
@@ -204,7 +221,14 @@ __global__ __launch_bounds__(256) void wm_expect_kernel(WmExpectArgs A, int stri
                 const cplx zi = ((const cplx *)A.za)[(int64_t)c * A.ni + i], zj = ((const cplx *)A.zb)[(int64_t)c * A.n + j];
                 const cplx l = c_make(zi.x + zj.x + gb[h].x - sb.x, zi.y + zj.y + gb[h].y - sb.y);
                 cplx f = l;
-                if (c % cols != 0) f = c_sub(c_mul(l, l), M[(dp + 1 + c) * stride + dp + 1 + c]);
+                if constexpr (COLS) {
+                    const int kd = kind[c];
+                    const cplx ss = M[(dp + 1 + c) * stride + dp + 1 + c];          // -s_c^T D'^-1 s_c
+                    if (kd == 1) f = c_sub(c_mul(l, l), ss);
+                    if (kd == 2) f = wme_col_exp(c_make(-l.x - 0.5 * ss.x, -l.y - 0.5 * ss.y));
+                } else {
+                    if (c % cols != 0) f = c_sub(c_mul(l, l), M[(dp + 1 + c) * stride + dp + 1 + c]);
+                }
                 term[h] = c_scale(f, A.lam[c]);
             }
         }
@@ -241,6 +265,14 @@ __global__ __launch_bounds__(256) void wm_expect_kernel(WmExpectArgs A, int stri
         for (int v = 0; v < nw; ++v) s = c_add(s, smem2[(size_t)v * region + o]);
         ((double2 *)A.partials)[(size_t)blockIdx.x * (A.M + 1) + o] = s;
     }
+}
+
+__global__ __launch_bounds__(256) void wm_expect_kernel(WmExpectArgs A, int stride, int region) {
+    wme_body<false>(A, nullptr, nullptr, stride, region);
+}
+
+__global__ __launch_bounds__(256) void wm_expect_cols_kernel(WmExpectColsArgs A, int stride, int region) {
+    wme_body<true>(A.a, A.kind, A.ketcol, stride, region);
 }
 
 // rows of the bordered matrix with C border columns, its odd row stride and the LDS region of one wavefront (complex elements)
@@ -302,4 +334,58 @@ extern "C" int sc_wm_pair_expect(const double *qp_i, const double *coef_i, const
     }
     hipLaunchKernelGGL(expect_reduce_kernel, dim3((unsigned)(M + 1)), dim3(256), 0, s, partials, tiles, M + 1, out);
     return sc_check_launch("sc_wm_pair_expect (reduction)");
+}
+
+// sc_wm_pair_expect with a kind and a slot of per-ket border vectors per column: kind 0  f = l,  kind 1
+// f = l^2 + s^T D'^-1 s,  kind 2  f = exp(-l + 1/2 s^T D'^-1 s);  ketcol[col] = -1 or the slot p of  s_col = sfix[col] + sket[p][j].
+// kind and ketcol are read back once and checked here, the kernel indexes sket with them unchecked.
+extern "C" int sc_wm_pair_expect_cols(const double *qp_i, const double *coef_i, const double *cqqp_i, const double *dvecp_i, int64_t ni,
+                                      const double *qp_j, const double *coef_j, const double *cqq_j, const double *dvec_j,
+                                      const double *cqqp_j, const double *dvecp_j, int64_t nj, const double *U, int32_t D,
+                                      int32_t dprime, const double *za, const double *zb, const double *g, const double *sfix,
+                                      const double *sket, int32_t S, const int32_t *ketcol, const int32_t *kind, const double *lam,
+                                      const double *kap, int32_t M, int32_t cols, double *partials, double *out, void *stream) {
+    if (!qp_i || !coef_i || !cqqp_i || !dvecp_i || !qp_j || !coef_j || !cqq_j || !dvec_j || !cqqp_j || !dvecp_j || !U || !za || !zb ||
+        !g || !sfix || !ketcol || !kind || !lam || !kap || !partials || !out || (!sket && S != 0))
+        return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_wm_pair_expect_cols: null argument");
+    if (M < 1 || cols < 1 || S < 0) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_wm_pair_expect_cols: M=%d, cols=%d, S=%d", M, cols, S);
+    if (!wme_shape_ok(D, dprime))
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_wm_pair_expect_cols: D=%d d'=%d outside 1 <= d' <= D, D <= %d, d' <= %d", D, dprime,
+                       WME_MAXD, WME_MAXDP);
+    if (M > 65535) return sc_fail(SC_ERR_UNSUPPORTED, "sc_wm_pair_expect_cols: M=%d operators outside M <= 65535", M);
+    const int cap = wme_capacity(D, dprime);
+    if ((int64_t)M * cols > cap)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_wm_pair_expect_cols: M cols = %lld columns, one launch holds at most %d at D=%d d'=%d",
+                       (long long)M * cols, cap, D, dprime);
+    const int64_t tiles = sc_wm_pair_expect_tiles(ni, nj);
+    if (tiles > 0x7fffffff)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_wm_pair_expect_cols: %lld x %lld pairs need more than 2^31 tiles", (long long)ni,
+                       (long long)nj);
+    hipStream_t s = (hipStream_t)stream;
+    const int nc = M * cols;                                  // <= WME_MAXROWS
+    int32_t meta[2 * WME_MAXROWS];
+    if (hipMemcpyAsync(meta, kind, nc * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(meta + nc, ketcol, nc * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return sc_check_launch("sc_wm_pair_expect_cols (host copy of kind and ketcol)");
+    for (int c = 0; c < nc; ++c) {
+        if (meta[c] < 0 || meta[c] > 2) return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_wm_pair_expect_cols: kind[%d]=%d outside 0 ... 2", c, meta[c]);
+        if (meta[nc + c] < -1 || meta[nc + c] >= S)
+            return sc_fail(SC_ERR_BAD_ARGUMENT, "sc_wm_pair_expect_cols: ketcol[%d]=%d outside -1 ... S-1=%d", c, meta[nc + c], S - 1);
+    }
+    if (tiles > 0) {
+        WmExpectColsArgs a{{qp_i, coef_i, cqqp_i, dvecp_i, qp_j, coef_j, cqq_j, dvec_j, cqqp_j, dvecp_j, U, ni, nj, D, dprime,
+                            za, zb, g, sfix, sket, lam, kap, M, cols - 1, partials}, kind, ketcol};
+        const int nt = dprime + 1 + nc, stride = wme_stride(nt), region = wme_region(D, nt);
+        const size_t per_wave = (size_t)region * sizeof(cplx);
+        const int nw = (int)std::min<size_t>(4, WME_LDS / per_wave);
+        const size_t bytes = per_wave * nw;
+        if (hipFuncSetAttribute((const void *)wm_expect_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+            return sc_check_launch("sc_wm_pair_expect_cols (LDS attribute)");
+        hipLaunchKernelGGL(wm_expect_cols_kernel, dim3((unsigned)tiles), dim3(64 * nw), bytes, s, a, stride, region);
+        const int rc = sc_check_launch("sc_wm_pair_expect_cols");
+        if (rc != SC_OK) return rc;
+    }
+    hipLaunchKernelGGL(expect_reduce_kernel, dim3((unsigned)(M + 1)), dim3(256), 0, s, partials, tiles, M + 1, out);
+    return sc_check_launch("sc_wm_pair_expect_cols (reduction)");
 }

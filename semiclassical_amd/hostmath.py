@@ -523,6 +523,169 @@ def wm_expectation_launches(lam, cap):
     return Rl, [pieces[k:k + per] for k in range(0, len(pieces), per)]
 
 
+def fold_wm_operator_columns(c, m, K, n, W, ex, U):
+    """(vx, vp, kind, lam, kappa, cols): the operators  c_a + m_a.x + 1/2 x^T K_a x + n_a.p + 1/2 p^T W_a p + sum_e w_a,e exp(-a_a,e . x)
+    (p = -i hbar d/dx acting on the ket) between two Walton-Manolopoulos Gaussians g_i, g_j of per-trajectory widths, divided by their
+    overlap, as ``cols`` columns per operator.  With the pair mean xbar and the covariance B = U D'^-1 U^T of
+    ``fold_wm_expectation_operators`` and L_j(x) = d_j - C_j (x - Q_j), the ket's logarithmic derivative, the element is
+        kappa_a + sum_col lam_col f_col,     kind 0: f = l,     kind 1: f = l^2 + s^T D'^-1 s,     kind 2: f = exp(-l + 1/2 s^T D'^-1 s),
+        x-form of v:  l = v.xbar,  s = U^T v;          p-form of w:  l = -i hbar w.L_j(xbar),  s = i hbar U^T C_j w  (per ket):
+    column 0 (kind 0, lam = 1) is the x-form of m plus the p-form of n; then the kept eigenpairs of K (kind 1, x-forms, lam =
+    lambda_r / 2), the kept eigenpairs of W (kind 1, p-forms, lam = mu_r / 2: p^T W p g_j = -hbar^2 [L_j^T W L_j - tr(W C_j)] g_j; the
+    constant hbar^2 / 2 sum_r mu_r w_r^T C_j w_r is added by ``wm_operator_columns``), both by the drop rule of
+    ``fold_quadratic_operators``, and the exponential terms with w_e != 0 (kind 2, x-forms of a_e, lam = w_e); kappa_a = c_a.  cols is
+    1 + the largest number of such columns of an operator, the others are padded with columns of kind 0, lam = 0 and zero vectors.
+    c (M,), m, n (M, D), K, W (M, D, D) real, ex = (w (M, P), a (M, P, D)) real, any of them None (= zeros) but not all; U (D, d') real
+    with orthonormal columns spans the non-zero width modes.  Returns vx, vp (M, cols, D) real -- the vectors of the x-forms and of
+    the p-forms --, kind (M, cols) int32, lam (M, cols) real, kappa (M,) complex.  ValueError for shapes that do not agree, a
+    non-finite entry, a K or W that is not symmetric to 1e-12 of its largest entry, and an m, n, kept eigenvector or a_e outside the
+    range of U (relative 1e-8, the test of ``fold_wm_expectation_operators``), naming the operator and the part."""
+    U = as_f64(U)
+    D = U.shape[0]
+    parts = {}
+    for name, val, tail in (("c", c, ()), ("x", m, (D,)), ("xx", K, (D, D)), ("p", n, (D,)), ("pp", W, (D, D))):
+        if val is None:
+            continue
+        try:
+            t = as_f64(val)
+        except (TypeError, ValueError, RuntimeError) as err:
+            raise ValueError(f"operators: {name}: a real array is expected ({err})")
+        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+            raise ValueError(f"operators: {name} of shape {('M',) + tail} is expected, got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"operators: non-finite entry in {name}")
+        parts[name] = t
+    counts = {name: int(t.shape[0]) for name, t in parts.items()}
+    if ex is not None:
+        if not isinstance(ex, (tuple, list)) or len(ex) != 2:
+            raise ValueError("operators: ex = (w, a) with w of shape (M, P) and a of shape (M, P, D) is expected")
+        try:
+            ew, ea = as_f64(ex[0]), as_f64(ex[1])
+        except (TypeError, ValueError, RuntimeError) as err:
+            raise ValueError(f"operators: ex: a pair (w, a) of real arrays is expected ({err})")
+        if ew.dim() != 2 or ea.dim() != 3 or tuple(ea.shape) != tuple(ew.shape) + (D,):
+            raise ValueError(f"operators: ex = (w, a) with w of shape (M, P) and a of shape (M, P, {D}) is expected, got "
+                             f"{tuple(ew.shape)} and {tuple(ea.shape)}")
+        if not bool(torch.isfinite(ew).all()) or not bool(torch.isfinite(ea).all()):
+            raise ValueError("operators: non-finite entry in ex")
+        counts["ex"] = int(ew.shape[0])
+    if not counts:
+        raise ValueError("operators: at least one of c, x, xx, p, pp, ex has to be given")
+    M = next(iter(counts.values()))
+    if M < 1 or any(v != M for v in counts.values()):
+        raise ValueError(f"operators: the parts have to hold the same number M >= 1 of operators, got {counts}")
+
+    def in_range(vec, a, what):
+        outside = torch.linalg.norm(vec - (vec @ U) @ U.T, dim=1) > 1.0e-8 * torch.linalg.norm(vec, dim=1)
+        if bool(outside.any()):
+            raise ValueError(f"operators: {what} of operator {a} has a component outside the range of the widths: the matrix "
+                             "element along a null direction does not exist")
+
+    for name in ("x", "p"):
+        if name in parts:
+            for a in range(M):
+                in_range(parts[name][a:a + 1], a, name)
+    columns = []                                            # per operator: (kind, lam, x-form vector or None, p-form vector or None)
+    for a in range(M):
+        mine = []
+        for name in ("xx", "pp"):
+            if name in parts:
+                lam, vec = _kept_eigenpairs(parts[name][a], a, name)
+                in_range(vec, a, name)
+                for r in range(int(lam.shape[0])):
+                    mine.append((1, 0.5 * float(lam[r]), vec[r], None) if name == "xx" else (1, 0.5 * float(lam[r]), None, vec[r]))
+        if ex is not None:
+            used = torch.nonzero(ew[a] != 0).reshape(-1)
+            if used.numel():
+                in_range(ea[a, used], a, "a of ex")
+            mine += [(2, float(ew[a, e]), ea[a, e], None) for e in used]
+        columns.append(mine)
+    cols = 1 + max(len(mine) for mine in columns)
+    vx, vp = torch.zeros((M, cols, D), dtype=torch.float64), torch.zeros((M, cols, D), dtype=torch.float64)
+    kind, lam_out = torch.zeros((M, cols), dtype=torch.int32), torch.zeros((M, cols), dtype=torch.float64)
+    lam_out[:, 0] = 1.0
+    if "x" in parts:
+        vx[:, 0] = parts["x"]
+    if "p" in parts:
+        vp[:, 0] = parts["p"]
+    for a, mine in enumerate(columns):
+        for k, (kd, lm, xv, pv) in enumerate(mine):
+            kind[a, 1 + k], lam_out[a, 1 + k] = kd, lm
+            if xv is not None:
+                vx[a, 1 + k] = xv
+            if pv is not None:
+                vp[a, 1 + k] = pv
+    kappa = torch.zeros(M, dtype=C128)
+    if "c" in parts:
+        kappa += parts["c"]
+    return vx.contiguous(), vp.contiguous(), kind.contiguous(), lam_out.contiguous(), kappa.contiguous(), cols
+
+
+def wm_operator_columns(vx, vp, kind, lam, Qi, dvecp_i, Qj, cqq_j, dvec_j, dvecp_j, U):
+    """(za, zb, g, sfix, sket, ketcol, kind): the columns of ``fold_wm_operator_columns`` for bras i and kets j, as
+    sc_wm_pair_expect_cols takes them.  The linear form of column col is
+        l_col = za[col][i] + zb[col][j] + g_col . b' + s_col^T D'^-1 b',    s_col = sfix[col] (+ sket[ketcol[col]][j]),
+    with the x-forms and p-forms of ``wm_expectation_columns``, the p-form now on any column: every column with a non-zero p-form
+    vector w gets a slot p of  sket[p][j] = i hbar U^T C_j w  (the slots in the order of the columns).  zb of column 0 of operator a
+    takes the per-ket constant  hbar^2 sum_col lam_col w_col^T C_j w_col  over a's kind-1 p-form columns (lam = mu / 2): the tr(W C_j)
+    of the ket-side identity.  vx, vp (M, cols, D), kind, lam (M, cols) on the host; the trajectories' operands as in
+    ``wm_expectation_columns``, on one device.  Returns za (C, ni), zb (C, nj), g, sfix (C, d') complex, C = M cols, sket (S, nj, d')
+    complex or None (S = 0), ketcol, kind (C,) int32 on the device."""
+    dev = Qi.device
+    M, C1, D = vx.shape
+    Uc = U.type(C128)
+    v = vx.reshape(M * C1, D).to(dev)
+    za = (v @ Qi.T).type(C128)
+    zb = torch.zeros((M * C1, Qj.shape[0]), dtype=C128, device=dev)
+    sfix = (v @ U).type(C128)
+    g = torch.zeros_like(sfix)
+    wflat = vp.reshape(M * C1, D)
+    slots = torch.nonzero((wflat != 0).any(1)).reshape(-1)          # the columns with a p-form, on the host
+    ketcol = torch.full((M * C1,), -1, dtype=torch.int32)
+    ketcol[slots] = torch.arange(slots.numel(), dtype=torch.int32)
+    sket = None
+    if slots.numel():
+        sd = slots.to(dev)
+        w = wflat[slots].to(dev).type(C128)                 # (S, D)
+        wpr = w @ Uc                                        # w' = U^T w
+        za[sd] += 1j * hbar * (wpr @ dvecp_i.conj().T)
+        zb[sd] += -1j * hbar * (w @ dvec_j.T) + 1j * hbar * (wpr @ dvecp_j.T)
+        g[sd] += -1j * hbar * wpr
+        Cw = torch.einsum('jab,sb->sja', cqq_j, w)          # (S, nj, D)
+        sket = (1j * hbar * (Cw @ Uc)).contiguous()
+        squared = kind.reshape(-1)[slots] == 1
+        if bool(squared.any()):
+            wCw = torch.einsum('sa,sja->sj', w, Cw)[squared.to(dev)]                        # w^T C_j w
+            weight = (hbar ** 2 * lam.reshape(-1)[slots][squared]).to(dev).type(C128)
+            owner = (torch.div(slots[squared], C1, rounding_mode='floor') * C1).to(dev)      # column 0 of the column's operator
+            zb.index_add_(0, owner, weight.unsqueeze(1) * wCw)
+    return (za.contiguous(), zb.contiguous(), g.contiguous(), sfix.contiguous(), sket, ketcol.to(dev),
+            kind.reshape(-1).to(torch.int32).contiguous().to(dev))
+
+
+def wm_operator_launches(lam, kind, cap):
+    """The operator set of ``fold_wm_operator_columns`` cut into calls of sc_wm_pair_expect_cols that hold at most ``cap`` >= 2
+    columns each: the cut of ``wm_expectation_launches``, whatever the kinds of the columns 1 ... (F is the sum of its columns).
+    lam, kind (M, cols).  Returns (cols', calls), a call being (ops, owners, columns): ``owners`` the operators its pieces belong to
+    (the caller adds the pieces of an operator), ``ops`` the operators whose kappa they carry -- M, an operator of kappa = 0, for a
+    later piece --, ``columns`` the len(ops) cols' flat indices a cols + r of its columns, where M cols stands for a column of zeros
+    with kind 0 and lam = 0: column 0 of a later piece and every padding (never a kind-2 column: 0 x inf; ValueError for a set that
+    holds a kind-2 column with lam = 0 itself)."""
+    M, C1 = lam.shape
+    if bool(((kind == 2) & (lam == 0)).any()):
+        raise ValueError("operators: a kind-2 column with lam = 0 (0 x exp may be 0 x inf: leave the term out)")
+    Rl, cut = wm_expectation_launches(lam, cap)
+    calls = []
+    for pieces in cut:
+        ops, owners, columns = [], [], []
+        for a, first, sq in pieces:
+            ops.append(a if first else M)
+            owners.append(a)
+            columns += [a * C1 if first else M * C1] + [a * C1 + r for r in sq] + [M * C1] * (Rl - len(sq))
+        calls.append((ops, owners, columns))
+    return 1 + Rl, calls
+
+
 def fold_exponential_operators(w, a, Gamma_t):
     """(uq, up, mu): the matrix element of the operators  sum_e w_a,e exp(-a_a,e . x)  between two Gaussians |q_i, p_i, Gamma_t>,
     |q_j, p_j, Gamma_t> of ONE width, divided by their overlap, as P PRODUCT columns per operator.  With

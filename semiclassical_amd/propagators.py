@@ -2265,18 +2265,10 @@ class HermanKlukPropagator(object):
         and ``MorsePotential`` with all chi = 0 (``NotImplementedError`` for every other: V is not a quadratic operator).  A float:
         the real part of one ``expectation`` value.  A singular Gamma_t is refused with ``ValueError``: the kinetic energy along
         its null directions does not exist, and projecting it is the caller's decision (``expectation`` with a projected pp)."""
-        from . import potentials as P
         self._refuse_thermal("energy_expectation()", "it describes one pure state, the trajectories belong to a mixture")
         d = self.dim
-        if isinstance(potential, P.MolecularHarmonicPotential):
-            H, x0, g = (hostmath.as_f64(t) for t in (potential.hess0, potential.pos0, potential.grad0))
-            H = 0.5 * (H + H.T)
-            const = float(potential.energy0) - potential._origin - float(g @ x0) + 0.5 * float(x0 @ H @ x0)
-            lin = g - H @ x0
-        elif isinstance(potential, P.MorsePotential) and potential._is_harmonic():
-            H = torch.diag(hostmath.as_f64(potential.omega) ** 2)
-            const, lin = 0.0, torch.zeros(d, dtype=F64)
-        else:
+        quad = _constant_hessian_parts(potential)
+        if quad is None:
             raise NotImplementedError(f"energy_expectation: {type(potential).__name__} is not a potential with a constant Hessian "
                                       "(MolecularHarmonicPotential, MorsePotential with chi = 0): <V> is not a quadratic operator's")
         if potential.dimensions() != d:
@@ -2284,8 +2276,7 @@ class HermanKlukPropagator(object):
         if not self._width_has_full_rank():
             raise ValueError("energy_expectation: Gamma_t is singular, the kinetic energy along its null directions does not exist; "
                              "projecting it is the caller's decision (expectation() with a projected pp)")
-        W = torch.diag(1.0 / hostmath.as_f64(potential.masses()))
-        vals, _ = self.expectation(c=torch.tensor([const], dtype=F64), x=lin.unsqueeze(0), xx=H.unsqueeze(0), pp=W.unsqueeze(0))
+        vals, _ = self.expectation(**_hamiltonian_operator(potential, "energy_expectation"))
         return float(vals[0].real)
 
     def _exponential_columns(self, uq, up, mu):
@@ -2322,14 +2313,7 @@ class HermanKlukPropagator(object):
         d = self.dim
         if isinstance(potential, P.MolecularHarmonicPotential) or (isinstance(potential, P.MorsePotential) and potential._is_harmonic()):
             return self.energy_expectation(potential)
-        if isinstance(potential, P.MorsePotential):
-            depth, rate = hostmath.as_f64(potential.D), hostmath.as_f64(potential.a)
-            H = None
-        elif isinstance(potential, P.NonHarmonicPotential):
-            eps, rate = hostmath.as_f64(potential.eps), hostmath.as_f64(potential.b)
-            depth = 0.5 * eps / rate ** 2
-            H = torch.diag(1.0 - eps).unsqueeze(0)
-        else:
+        if _morse_parts(potential) is None:
             raise NotImplementedError(f"anharmonic_energy_expectation: {type(potential).__name__} is neither a Morse-type potential "
                                       "(MorsePotential, NonHarmonicPotential) nor one with a constant Hessian: <V> has no closed form")
         if potential.dimensions() != d:
@@ -2337,11 +2321,7 @@ class HermanKlukPropagator(object):
         if not self._width_has_full_rank():
             raise ValueError("anharmonic_energy_expectation: Gamma_t is singular, the kinetic energy along its null directions does "
                              "not exist; projecting it is the caller's decision (expectation() with a projected pp)")
-        # D_k (1 - exp(-a_k x_k))^2 = D_k - 2 D_k exp(-a_k x_k) + D_k exp(-2 a_k x_k)
-        w = torch.cat((-2.0 * depth, depth)).unsqueeze(0)
-        a = torch.cat((torch.diag(rate), torch.diag(2.0 * rate))).unsqueeze(0)
-        W = torch.diag(1.0 / hostmath.as_f64(potential.masses())).unsqueeze(0)
-        vals, _ = self.expectation(c=depth.sum().reshape(1), xx=H, pp=W, ex=(w, a))
+        vals, _ = self.expectation(**_hamiltonian_operator(potential, "anharmonic_energy_expectation"))
         return float(vals[0].real)
 
     def wavefunction(self, x):
@@ -2540,6 +2520,52 @@ def _NULL_POT(dim):
     return _lib.sc_potential(kind=_lib.SC_POT_HARMONIC_SEP, dim=dim)
 
 
+def _constant_hessian_parts(potential):
+    """(const, lin, H) of V = const + lin.x + 1/2 x^T H x for a potential whose Hessian is constant (``MolecularHarmonicPotential``,
+    ``MorsePotential`` with all chi = 0), None for every other"""
+    from . import potentials as P
+    if isinstance(potential, P.MolecularHarmonicPotential):
+        H, x0, g = (hostmath.as_f64(t) for t in (potential.hess0, potential.pos0, potential.grad0))
+        H = 0.5 * (H + H.T)
+        const = float(potential.energy0) - potential._origin - float(g @ x0) + 0.5 * float(x0 @ H @ x0)
+        return const, g - H @ x0, H
+    if isinstance(potential, P.MorsePotential) and potential._is_harmonic():
+        return 0.0, torch.zeros(potential.dimensions(), dtype=F64), torch.diag(hostmath.as_f64(potential.omega) ** 2)
+    return None
+
+
+def _morse_parts(potential):
+    """(depth, rate, H) of V = sum_k depth_k (1 - exp(-rate_k x_k))^2 + 1/2 x^T H[0] x on the separable anharmonic surfaces
+    (``MorsePotential`` with its own D and a, H None; ``NonHarmonicPotential``: the eps Morse part, (1 - eps) x^2 / 2 as H), None for
+    every other"""
+    from . import potentials as P
+    if isinstance(potential, P.MorsePotential):
+        return hostmath.as_f64(potential.D), hostmath.as_f64(potential.a), None
+    if isinstance(potential, P.NonHarmonicPotential):
+        eps, rate = hostmath.as_f64(potential.eps), hostmath.as_f64(potential.b)
+        return 0.5 * eps / rate ** 2, rate, torch.diag(1.0 - eps).unsqueeze(0)
+    return None
+
+
+def _hamiltonian_operator(potential, who):
+    """the one operator p^T m^-1 p / 2 + V(x) as the keyword arguments c, x, xx, pp, ex of ``expectation`` /
+    ``wm_operator_expectation``, from ``_constant_hessian_parts`` or ``_morse_parts``; NotImplementedError for every other potential"""
+    W = lambda: torch.diag(1.0 / hostmath.as_f64(potential.masses())).unsqueeze(0)
+    quad = _constant_hessian_parts(potential)
+    if quad is not None:
+        const, lin, H = quad
+        return dict(c=torch.tensor([const], dtype=F64), x=lin.unsqueeze(0), xx=H.unsqueeze(0), pp=W())
+    morse = _morse_parts(potential)
+    if morse is None:
+        raise NotImplementedError(f"{who}: {type(potential).__name__} is neither a Morse-type potential (MorsePotential, "
+                                  "NonHarmonicPotential) nor one with a constant Hessian: <V> has no closed form")
+    depth, rate, H = morse
+    # D_k (1 - exp(-a_k x_k))^2 = D_k - 2 D_k exp(-a_k x_k) + D_k exp(-2 a_k x_k)
+    w = torch.cat((-2.0 * depth, depth)).unsqueeze(0)
+    a = torch.cat((torch.diag(rate), torch.diag(2.0 * rate))).unsqueeze(0)
+    return dict(c=depth.sum().reshape(1), xx=H, pp=W(), ex=(w, a))
+
+
 def wm_pair_expect(bra, ket, U, za, zb, g, sfix, sket, lam, kap, stream=None):
     """sum_ij T_ij F_a,ij of M operators and sum_ij T_ij through ``sc_wm_pair_expect`` (include/semiclassical_hip.h), in as many calls
     as the columns need: one call holds ``sc_wm_pair_expect_capacity(D, d')`` columns (``hostmath.wm_expectation_launches``), the
@@ -2582,6 +2608,51 @@ def wm_pair_expect(bra, ket, U, za, zb, g, sfix, sket, lam, kap, stream=None):
             res[a] += out[e]
         if k == 0:
             res[M] = out[len(pieces)]
+    return res
+
+
+def wm_pair_expect_cols(bra, ket, U, za, zb, g, sfix, sket, ketcol, kind, lam, kap, stream=None):
+    """``wm_pair_expect`` through ``sc_wm_pair_expect_cols``: columns of the kinds 0, 1, 2 with per-ket border vectors on any of them
+    (DESIGN.md section 4.25), cut into calls by ``hostmath.wm_operator_launches``; a call takes along the slots of sket its columns
+    name.  Operands as ``wm_pair_expect``, and sket (S, nj, d') complex or None, ketcol, kind (C,) int32 on the device, lam (M, cols)
+    real.  Returns the complex ndarray (M + 1,), entry M = sum T."""
+    dev = U.device
+    D, dp = U.shape
+    ni, nj = int(bra[0].shape[0]), int(ket[0].shape[0])
+    M, C1 = lam.shape
+    cap = int(lib.sc_wm_pair_expect_capacity(D, dp))
+    tiles = max(int(lib.sc_wm_pair_expect_tiles(ni, nj)), 1)
+    rows = [ptr(t) for t in bra] + [ni] + [ptr(t) for t in ket] + [nj, ptr(U), D, dp]
+
+    def call(za, zb, g, sfix, sket, ketcol, kind, lam, kap, m, cols):
+        partials = torch.empty((tiles, m + 1, 2), dtype=F64, device=dev)
+        out = torch.empty(m + 1, dtype=C128, device=dev)
+        S = 0 if sket is None else int(sket.shape[0])
+        check(lib.sc_wm_pair_expect_cols(*rows, ptr(za), ptr(zb), ptr(g), ptr(sfix), ptr(sket), S, ptr(ketcol), ptr(kind), ptr(lam),
+                                         ptr(kap), m, cols, ptr(partials), ptr(out), stream))
+        return out.cpu().numpy()
+
+    if M * C1 <= cap or cap < 2:            # (a shape outside the limits has capacity 0: the library names the limits)
+        return call(za, zb, g, sfix, sket, ketcol, kind, lam.contiguous(), kap, M, C1)
+    cols, calls = hostmath.wm_operator_launches(lam.cpu(), kind.cpu().reshape(M, C1), cap)
+    # one more column and one more operator of zeros, for the padding and for column 0 of an operator's later pieces
+    pad = lambda t, fill=0: torch.cat((t, torch.full((1,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=dev)))
+    za, zb, g, sfix, lam_f, kind, ketcol = pad(za), pad(zb), pad(g), pad(sfix), pad(lam.reshape(-1)), pad(kind), pad(ketcol, -1)
+    kap_p = pad(kap)
+    res = np.zeros(M + 1, dtype=np.complex128)
+    for k, (ops, owners, columns) in enumerate(calls):
+        ci, oi = torch.tensor(columns, device=dev), torch.tensor(ops, device=dev)
+        kc = ketcol[ci].clone()
+        used = kc >= 0
+        slots = kc[used].long()                             # every slot belongs to one column: no duplicates
+        kc[used] = torch.arange(int(slots.numel()), dtype=torch.int32, device=dev)
+        out = call(za[ci].contiguous(), zb[ci].contiguous(), g[ci].contiguous(), sfix[ci].contiguous(),
+                   sket[slots].contiguous() if slots.numel() else None, kc, kind[ci].contiguous(), lam_f[ci].contiguous(),
+                   kap_p[oi].contiguous(), len(ops), cols)
+        for e, a in enumerate(owners):
+            res[a] += out[e]
+        if k == 0:
+            res[M] = out[len(ops)]
     return res
 
 
@@ -2771,7 +2842,7 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
     def expectation(self, c=None, x=None, xx=None, p=None, pp=None, normalise=True, ex=None):
         raise NotImplementedError("expectation is not available for the Walton-Manolopoulos propagator: its Gaussians carry "
                                   "per-trajectory widths, the closed form behind it needs one width Gamma_t for all of them "
-                                  "(wm_expectation and wm_wavepacket_moments solve a d' x d' system per pair instead)")
+                                  "(wm_expectation, wm_operator_expectation and their moments solve a d' x d' system per pair instead)")
 
     def wm_expectation(self, c=None, x=None, xx=None, p=None, normalise=True):
         """Expectation values of M operators in the WM wavepacket (not in the reference):
@@ -2829,6 +2900,84 @@ class WaltonManolopoulosPropagator(HermanKlukPropagator):
         vals, norm2 = self.wm_expectation(x=torch.cat((U, zv, zv)), xx=torch.cat((zm, uu, zm)), p=torch.cat((zv, zv, U)))
         ex, exx, ep = (vals[k * Md:(k + 1) * Md].real for k in range(3))
         return {"x": ex, "p": ep, "var_x": exx - ex ** 2, "norm2": norm2}
+
+    def wm_operator_expectation(self, c=None, x=None, xx=None, p=None, pp=None, ex=None, normalise=True):
+        """``wm_expectation`` with a quadratic momentum part and exponentials (not in the reference):
+
+            A_a = c_a + x_a.x + 1/2 x^T xx_a x + p_a.p + 1/2 p^T pp_a p + sum_e w_a,e exp(-a_a,e . x)        (no x-p cross terms),
+
+        shapes and conventions of ``wm_expectation`` and of ``HermanKlukPropagator.expectation``: ``pp`` (M, D, D) real symmetric,
+        ``ex = (w, a)`` with w (M, P) and a (M, P, D) real, an operator with fewer terms has w = 0 in the others.  Returns
+        ``(values, norm2)`` as there.  1/2 p^T pp p acts on the ket alone: with L_j(x) = d_j - C_j (x - Q_j) its element is
+        -hbar^2 / 2 [L_j^T pp L_j - tr(pp C_j)] under the pair's Gaussian, one squared column with a per-ket border vector per
+        eigenpair of pp; an exponential is exp(-a.xbar + 1/2 a^T B a), one column (``hostmath.fold_wm_operator_columns``).  A single
+        pair's momentum term is not Hermitian-symmetric, the sum over the pairs is.
+
+        Every x_a, p_a, a_e with w_e != 0 and eigenvector of xx_a, pp_a has to lie in the span of the non-zero width modes
+        (``ValueError`` naming the operator and the part).  A value that is not finite -- an exponential out of range: a trajectory
+        far out on the repulsive wall -- is a ``ValueError`` naming the operator; nothing is rescaled.  Sums of exponentials of
+        alternating sign (a Morse V) round relative to the sum of the absolute terms, as in section 4.23.
+
+        Without ``pp`` and ``ex`` this is ``wm_expectation``, bit for bit.  Otherwise the pair sum runs in
+        ``sc_wm_pair_expect_cols`` (``wm_pair_expect_cols``).  Rank-local, the discard mask ignored, no step taken and no state
+        touched, no hook in ``run()``: what ``wm_expectation`` says."""
+        if pp is None and ex is None:
+            return self.wm_expectation(c, x, xx, p, normalise)
+        d = self.dim
+        vx, vp, kind, lam, kap, _ = hostmath.fold_wm_operator_columns(c, x, xx, p, pp, ex, self._wm_host.U)
+        coef, cqq, dvec, cqqp, dvecp, U = self._wm_pair_operands()
+        Q = self._qp[:, :d]
+        za, zb, g, sfix, sket, ketcol, kind_d = hostmath.wm_operator_columns(vx, vp, kind, lam, Q, dvecp, Q, cqq, dvec, dvecp, U)
+        with self._timed("wm_operator_expectation"):
+            res = wm_pair_expect_cols((self._qp, coef, cqqp, dvecp), (self._qp, coef, cqq, dvec, cqqp, dvecp), U, za, zb, g, sfix,
+                                      sket, ketcol, kind_d, lam.to(self.device), kap.to(self.device), self._stream())
+        M = int(kap.shape[0])
+        bad = ~np.isfinite(res[:M])
+        if bad.any():
+            raise ValueError(f"operators: the value of operator {int(np.nonzero(bad)[0][0])} is not finite: an exponential is out of "
+                             "range at a pair of trajectories (one has run far out on the repulsive wall)")
+        norm2 = float(res[M].real)
+        return (res[:M] / norm2 if normalise else res[:M].copy()), norm2
+
+    def wm_phase_space_moments(self, directions=None):
+        """``wm_wavepacket_moments`` with the momentum variance: a dict with ``x``, ``p``, ``var_x``, ``var_p`` = <(u.p)^2> - <u.p>^2
+        and ``norm2``.  ``directions`` and the refusals as there.  One ``wm_operator_expectation`` call with four operators per
+        direction."""
+        d = self.dim
+        if directions is None:
+            if self._wm_host.dprime != d:
+                raise ValueError("wm_phase_space_moments: the widths are singular, the moments along their null directions do not "
+                                 "exist: give directions in the span of the non-zero width modes")
+            U = torch.eye(d, dtype=F64)
+        else:
+            U = self._density_directions(directions)
+            if bool((torch.linalg.norm(U, dim=1) == 0).any()):
+                raise ValueError("directions: zero vector")
+        Md = U.shape[0]
+        zv, zm = torch.zeros((Md, d), dtype=F64), torch.zeros((Md, d, d), dtype=F64)
+        uu = 2.0 * U.unsqueeze(2) * U.unsqueeze(1)          # 1/2 x^T (2 u u^T) x = (u.x)^2
+        vals, norm2 = self.wm_operator_expectation(x=torch.cat((U, zv, zv, zv)), xx=torch.cat((zm, uu, zm, zm)),
+                                                   p=torch.cat((zv, zv, U, zv)), pp=torch.cat((zm, zm, zm, uu)))
+        ex, exx, ep, epp = (vals[k * Md:(k + 1) * Md].real for k in range(4))
+        return {"x": ex, "p": ep, "var_x": exx - ex ** 2, "var_p": epp - ep ** 2, "norm2": norm2}
+
+    def wm_energy_expectation(self, potential):
+        """<psi| p^T m^-1 p / 2 + V(x) |psi> / norm()**2 of the WM wavepacket: a float, the real part of one
+        ``wm_operator_expectation`` value.  V as ``HermanKlukPropagator.energy_expectation`` and ``anharmonic_energy_expectation``
+        build it (``_hamiltonian_operator``): ``MolecularHarmonicPotential``; ``MorsePotential`` with its own D and a -- D squared
+        momentum columns and 2 D exponentials in one operator, or omega^2 as ``xx`` when every chi = 0 --; ``NonHarmonicPotential``.
+        sGDML and quartic force fields: ``NotImplementedError``.  Singular widths (d' < D) are refused with ``ValueError``: the
+        kinetic energy along their null directions does not exist.  On the Morse-type surfaces V is a sum of terms of alternating
+        sign that are each about D_k: rounding is relative to the sum of the absolute terms, as in section 4.23 (there is no
+        cancellation-free fold)."""
+        parts = _hamiltonian_operator(potential, "wm_energy_expectation")
+        if potential.dimensions() != self.dim:
+            raise ValueError(f"wm_energy_expectation: the potential has {potential.dimensions()} dimensions, the propagator {self.dim}")
+        if self._wm_host.dprime != self.dim:
+            raise ValueError("wm_energy_expectation: the widths are singular, the kinetic energy along their null directions does "
+                             "not exist; projecting it is the caller's decision (wm_operator_expectation() with a projected pp)")
+        vals, _ = self.wm_operator_expectation(**parts)
+        return float(vals[0].real)
 
     def _launch_correlate(self, row, state=None, cursor=None, per_trajectory=True, families=()):
         # no pairs or visits; run(targets=...) and run(operators=...) are refused before the loop starts
